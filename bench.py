@@ -1,6 +1,16 @@
 """bench.py -- HVO sequences/sec per train step (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (untimed steps until the GPU has run 1.5 s, parameters and step state restored after them, then the
+W warm-up steps), times EXACTLY K steps (one block between two device synchronises: `ms_per_step` is that
+block over K), writes the outputs of the last timed step if --dump-outputs is given, and prints the JSON line.  --full adds what the
+headline does not need: more timed blocks for the spread, the step with its batch copied from pinned host memory, the data-parallel
+overhead figures, the live per-kernel profile and roofline, and the CPU baseline.
+
+--dump-outputs DIR: what a caller of the timed step has after its last step, as float32 .npy files -- stats.npy (the 8-float stats
+train_step returns), hvo.npy (that step's forward output) and param.<state-dict name>.npy (every parameter after its update).  Inputs
+and initial parameters are seeded, so the same arguments give the same inputs on every run and build.
 
 N = 1 runs in this process.  N > 1: if the process was started by torch.distributed.run (WORLD_SIZE in the environment) it
 is one rank; from a bare shell it is the LAUNCHER -- it starts N rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*
@@ -32,7 +42,9 @@ WORK = dict(d_model=128, n_heads=4, dim_feedforward=512, num_encoder_layers=3, n
 BATCH, LR, PENALTY = 64, 0.07, 0.38
 FP32_MATRIX_PEAK_TFLOPS = 157.3                            # MI355X_MICROARCH.md "Peak FP32 (matrix)"
 PROFILE_STEPS = 20
-BLOCKS = 5                                                 # back-to-back timed blocks of --steps steps each: the median one is reported
+SETTLE_S = 1.5                                             # untimed steps ahead of the warm-up until the GPU has run this long ...
+SETTLE_CHUNK = 50                                          # ... checked every this many steps
+BLOCKS = 5                                                 # --full: back-to-back timed blocks of --steps steps each for the spread
 MIN_TIMED_S = 2.5                                          # ... and more blocks of the same length until this much timed GPU work has run
 MAX_BLOCKS = 4000                                          # (so that an outside sampler sees the GPU busy whatever --steps is)
 CPU_BASELINE_S = 18.0                                      # whole CPU-baseline leg: thread sweep + timed sample
@@ -118,12 +130,29 @@ def cpu_baseline(budget_s=CPU_BASELINE_S):
                       "whole leg %.1f s" % (n, BATCH, dt, torch.__version__, threads, swept, ncpu, time.perf_counter() - t_leg)}
 
 
+def dump_outputs(out_dir, eng, batch):
+    """What a caller of the timed step has after its last step, float32 .npy under out_dir: the returned stats, the step's forward
+    output (B x 32 x 27 HVO) and every parameter after the update, by state-dict name (2.5 MB at the headline shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    s = eng.slot(batch)
+    arrays = {"stats": s.stats, "hvo": s.hvo}
+    arrays.update(("param." + n, t) for n, t in eng.views().items())
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (stats, forward output, updated parameters) as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the spread over more timed blocks, the H2D-inclusive step, the data-parallel overhead figures, the live "
+                         "per-kernel profile / roofline and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-dp-tune", action="store_true", help="world > 1: keep the default data-parallel recipe instead of timing the four")
     ap.add_argument("--force-dp", action="store_true",
@@ -255,6 +284,31 @@ def run_rank(args):
             dt, ev, bad = float(t[0].item()), float(t[1].item()), float(t[2].item())
         return dt, ev, bad
 
+    def settle():
+        """Untimed steps until the GPU has been busy for SETTLE_S seconds: after 5 warm-up steps a GPU fresh from idle reads 0.211
+        ms/step, after 1 s 0.201.  Parameters and step state are put back afterwards, so what the warm-up and timed steps compute
+        depends on the arguments alone.  (world > 1: every rank takes the same decision -- the elapsed time is the maximum over ranks)"""
+        snap = (eng.params.clone(), eng.state.clone(), None if eng.m is None else (eng.m.clone(), eng.v.clone()))
+        sync()
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(SETTLE_CHUNK):
+                eng.train_step()
+            sync()
+            el = time.perf_counter() - t0
+            if world > 1:
+                t = torch.tensor([el], device=dev, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                el = float(t.item())
+            if el >= SETTLE_S:
+                break
+        eng.params.copy_(snap[0]); eng.state.copy_(snap[1]); eng.grads.zero_()
+        if snap[2] is not None:
+            eng.m.copy_(snap[2][0]); eng.v.copy_(snap[2][1])
+        eng.check_exchange(eng.slot(batch), "the settling steps of bench.py")
+
+    if not emu:
+        settle()
     for _ in range(args.warmup):
         eng.train_step()
     # world > 1: the first run on real ranks picks its own data-parallel recipe -- {one all-reduce, two overlapped buckets} x {eager
@@ -267,21 +321,34 @@ def run_rank(args):
         for _ in range(2 if emu else 5):
             eng.train_step()
     eng.check_exchange(eng.slot(batch), "the warm-up of bench.py")
-    # EXACTLY --steps steps per block, as the contract says; at least BLOCKS blocks, and more of the same until MIN_TIMED_S seconds of
-    # timed steps have run (every rank takes the same decision: the block times are already the maximum over ranks)
-    blocks = []
-    while len(blocks) < (1 if emu else BLOCKS) or (not emu and sum(b[0] for b in blocks) < MIN_TIMED_S and len(blocks) < MAX_BLOCKS):
-        blocks.append(timed_block(eng.train_step, args.steps))
-    discarded = sum(1 for b in blocks if b[2])
-    blocks = [b for b in blocks if not b[2]] or [timed_block(eng.train_step, args.steps)]
-    walls = sorted(b[0] for b in blocks)
-    dt = walls[len(walls) // 2]                                          # the median block
-    ev = sorted(b[1] for b in blocks)[len(blocks) // 2]
+    # the headline: EXACTLY --steps timed steps, one block.  A block in which a pair exchange timed out (its updates were skipped) does not
+    # count and is run once more (every rank takes the same decision: `bad` is already the maximum over ranks)
+    dt, ev, bad = timed_block(eng.train_step, args.steps)
+    discarded = 0
+    if bad:
+        discarded = 1
+        dt, ev, bad = timed_block(eng.train_step, args.steps)
     loss = float(eng.stats[0].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, batch)
+
+    # --full: more blocks of the same length for the spread -- at least BLOCKS in all, and more until MIN_TIMED_S seconds of timed steps
+    # have run; blocks with a timed-out exchange are left out of it
+    walls = [dt]
+    if args.full:
+        n = 1
+        while n < (1 if emu else BLOCKS) or (not emu and sum(walls) < MIN_TIMED_S and n < MAX_BLOCKS):
+            b = timed_block(eng.train_step, args.steps)
+            n += 1
+            if b[2]:
+                discarded += 1
+            else:
+                walls.append(b[0])
+    walls.sort()
 
     # the same steps with the batch coming from pinned host memory every step ("report both with / without H2D")
     h2d = None
-    if not emu:
+    if args.full and not emu:
         xh, yh = torch.from_numpy(x).pin_memory(), torch.from_numpy(y).pin_memory()
         for _ in range(min(args.warmup, 10)):
             eng.train_step(xh, yh)
@@ -290,7 +357,7 @@ def run_rank(args):
     # data-parallel step sequence vs the fused single-process step on the same GPU: what the split into
     # fwd+bwd / all-reduce / update costs besides the communication itself
     fused_dt = None
-    if (world > 1 or args.force_dp) and not emu:
+    if args.full and (world > 1 or args.force_dp) and not emu:
         e1 = StepEngine(batch_size=batch, optimizer="sgd", learning_rate=LR, hit_loss_penalty=PENALTY, seed=1234 | (rank << 32), device=dev,
                         world_size=1, use_graph=False if args.no_graph else "auto", **work)
         e1.load_named(layout.init_params(work, seed=0))
@@ -303,7 +370,7 @@ def run_rank(args):
     # what the first multi-GPU record needs to explain itself: every rank's exchange time-outs and skipped updates, and the gradient
     # all-reduce timed ALONE (20 back-to-back all-reduces of the flat gradient buffer, max over ranks)
     per_rank, ar_alone_us = None, None
-    if (world > 1 or args.force_dp) and dist.is_initialized():
+    if args.full and (world > 1 or args.force_dp) and dist.is_initialized():
         rep = eng.exchange_report()
         mine = torch.tensor([float(rep["exchange_timeouts"]), float(rep["skipped_updates"])], dtype=torch.float64, device=dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -329,9 +396,11 @@ def run_rank(args):
         out = {
             "metric": "HVO sequences/sec (32-step, d_model=128) per train step", "value": seq_s, "unit": "sequences/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            # BLOCKS back-to-back blocks of exactly `steps` steps, each bracketed by barrier + synchronize; value = the median block
+            # value / ms_per_step: ONE block of exactly `steps` steps bracketed by barrier + synchronize (--full: the spread over
+            # the blocks of the same length that follow it, the first included)
             "timing": {"blocks": len(walls), "timed_s": sum(walls), "ms_per_step_min": 1e3 * walls[0] / args.steps,
-                       "ms_per_step_max": 1e3 * walls[-1] / args.steps, "hip_event_ms_per_step": 1e3 * ev / args.steps},
+                       "ms_per_step_max": 1e3 * walls[-1] / args.steps, "ms_per_step_median": 1e3 * walls[len(walls) // 2] / args.steps,
+                       "hip_event_ms_per_step": 1e3 * ev / args.steps},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: InfillingClosedHH_training.yaml + overrides d_model=128/4 heads/3 layers, "
                                    "dim_feedforward=512, bs=64 per GPU, dropout=0.24, SGD lr=0.07, hit_loss_penalty=0.38, S=16, encoder-only",
@@ -363,7 +432,7 @@ def run_rank(args):
         if emu:
             out["config"]["workload"] = "HOST-EMULATOR TEST RUN (not a measurement): %s bs %d" % (json.dumps(work, sort_keys=True), batch)
         # dominant kernel, measured live: eager pass with HIP events around every launch on the launch stream
-        prof = eng.profile(PROFILE_STEPS)
+        prof = eng.profile(PROFILE_STEPS) if args.full else None
         if prof:
             dom = max(prof.items(), key=lambda kv: kv[1][1])
             cnt, ms, fl, by = dom[1]
@@ -377,7 +446,7 @@ def run_rank(args):
                                "share_of_kernel_time": ms / tot_ms}
             out["launches_per_step"] = sum(v[0] for v in prof.values()) / float(PROFILE_STEPS)
             out["kernel_classes_us_per_step"] = {k: round(1e3 * v[1] / PROFILE_STEPS, 2) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])}
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu:
             out["cpu_baseline"] = cpu_baseline()
     if dist.is_initialized():
         dist.barrier()

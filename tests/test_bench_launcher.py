@@ -10,7 +10,7 @@ import sys
 from harness import ROOT, emu_lib
 
 
-def _run(gpus, extra_env=None):
+def _run(gpus, extra_env=None, extra_args=()):
     emu_lib()                                                    # builds tests/emu/libgroove_emu.so if stale
     env = dict(os.environ, GT_BENCH_EMU_LIB=os.path.join(ROOT, "tests", "emu", "libgroove_emu.so"),
                GT_BENCH_EMU_WORK=json.dumps(dict(d_model=32, n_heads=4, dim_feedforward=16, num_encoder_layers=2, batch=2)))
@@ -18,14 +18,14 @@ def _run(gpus, extra_env=None):
         env.pop(k, None)
     env.update(extra_env or {})
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline"] + list(extra_args), env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     return json.loads(lines[-1]), lines
 
 
 def test_bare_shell_launch_of_two_ranks():
-    out, lines = _run(2)
+    out, lines = _run(2, extra_args=["--full"])
     assert len(lines) == 1                                       # the JSON line is the only thing on stdout
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["scaling"] == "weak"
     d = out["distributed"]
@@ -46,6 +46,26 @@ def test_single_rank_and_two_ranks_compute_the_same_kind_of_step():
     one, _ = _run(1)
     assert one["n_gpus"] == 1 and one["distributed"]["dist_world_size"] == 1
     assert 0 < one["final_loss"] < 20
+
+
+def test_plain_run_times_exactly_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run is one block of exactly --steps timed steps; --dump-outputs writes the last step's stats, forward output and updated
+    parameters as float32 .npy, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        out, lines = _run(1, extra_args=["--dump-outputs", str(tmp_path / run)])
+        assert len(lines) == 1 and out["steps"] == 3 and out["timing"]["blocks"] == 1
+        assert out["ms_per_step"] > 0 and "cpu_baseline" not in out and "roofline" not in out
+        outs.append({f: np.load(str(tmp_path / run / f)) for f in sorted(os.listdir(str(tmp_path / run)))})
+    a, b = outs
+    assert {"stats.npy", "hvo.npy", "param.OutputLayer.Linear.bias.npy"} <= set(a) and set(a) == set(b)
+    assert a["hvo.npy"].shape == (2, 32, 27) and a["stats.npy"].shape == (8,)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
+    assert abs(float(a["stats.npy"][0]) - out["final_loss"]) < 1e-6
 
 
 def test_bench_imports_the_oracle_only_in_the_cpu_baseline_leg():

@@ -41,13 +41,12 @@ def test_reference_yaml_keys_load_unchanged(tmp_path, name):
     assert p["training"] == {"learning_rate": hp["learning_rate"], "batch_size": hp["batch_size"], "hit_loss_penalty": hp["hit_loss_penalty"]}
 
 
-REF_CONFIGS = "/root/reference/configs"
+REF_CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_configs")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="the reference checkout is only present in the build container")
 def test_the_reference_s_own_yaml_files_load_in_place():
-    """Every *_training.yaml of the reference, read where it lies (never copied): the CLI takes it unchanged, the model parameters
-    follow ref:train.py:115-143, and the retyped table above agrees with the real files."""
+    """Every *_training.yaml of the reference (byte-for-byte copies under golden/reference_configs/): the CLI takes it unchanged, the
+    model parameters follow ref:train.py:115-143, and the retyped table above agrees with the real files."""
     import glob
     files = sorted(glob.glob(os.path.join(REF_CONFIGS, "*_training.yaml")))
     assert len(files) >= 4

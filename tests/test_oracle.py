@@ -1,4 +1,4 @@
-"""The oracle against its pins: the reference's demo checkpoint and the golden vectors that stock
+"""The oracle against its pins: the reference's demo checkpoint (a copy under golden/reference_demo/) and the golden vectors that stock
 torch modules produced (oracle/make_golden.py).  CPU only."""
 import glob
 import os
@@ -76,16 +76,18 @@ def test_numpy_oracle_vs_torch_golden(path):
         assert np.abs(pv - z["pred_v"]).max() < 2e-5 and np.abs(po - z["pred_o"]).max() < 2e-5
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/demo/transformer_run_171tyqit_Epoch_1.Model"),
-                    reason="reference checkpoint not present on this box")
 def test_reference_checkpoint_strict_loads_into_torch_restatement():
     import torch
     from oracle import torch_groove as tg
-    ck = torch.load("/root/reference/demo/transformer_run_171tyqit_Epoch_1.Model", weights_only=True, map_location="cpu")
+    ck = torch.load(os.path.join(GOLD, "reference_demo", "transformer_run_171tyqit_Epoch_1.Model"), weights_only=True, map_location="cpu")
     m = tg.build(dict(d_model=32, n_heads=4, dim_feedforward=16, num_encoder_layers=6, num_decoder_layers=0))
     res = m.load_state_dict(ck["model_state_dict"], strict=True)
     assert not res.missing_keys and not res.unexpected_keys
     assert len(list(m.parameters())) == len(ck["optimizer_state_dict"]["param_groups"][0]["params"]) == 78
+    z = np.load(os.path.join(GOLD, "demo_ckpt.npz"))                          # the weights demo_ckpt.npz was dumped from
+    assert sorted(k[3:] for k in z.files if k.startswith("sd/")) == sorted(ck["model_state_dict"])
+    for k, t in ck["model_state_dict"].items():
+        assert np.array_equal(t.numpy(), z["sd/" + k]), k
 
 
 def test_dropout_hash_statistics():

@@ -11,7 +11,7 @@ export GT_XCHG_STRICT=0
 for v in hip acct1 acct2 acct3 acct4; do
   export GT_LIB_PATH=$R/transformergrooveinfilling_amd/lib/libgroove_$v.so
   for c in WRITE_SIZE FETCH_SIZE; do
-    timeout 300 rocprofv3 --pmc $c --output-format csv -d $O/$v/$c -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-graph > $O/$v.$c.log 2>&1
+    timeout 300 rocprofv3 --pmc $c --output-format csv -d $O/$v/$c -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-graph > $O/$v.$c.log 2>&1
   done
 done
 cd $R && python3 tools/acct_writes.py $O | tee $O/summary.txt

@@ -31,13 +31,13 @@ done
 python tools/kbits_check.py > $O/kbits_check.txt 2>&1
 GT_ROW_FUSE_XCHG=0 python tools/shape_bench.py --only 5 --steps 100 2>/dev/null | tail -1 | sed 's/^/GT_ROW_FUSE_XCHG=0 (C3: row-owning LayerNorm tiles, the path until round 5) /' >> $O/shapes.txt
 GT_ROW_FUSE_BIG_MAX_D=0 GT_LN_XCHG=0 python tools/shape_bench.py --only 5 --steps 100 2>/dev/null | tail -1 | sed 's/^/GT_ROW_FUSE_BIG_MAX_D=0 GT_LN_XCHG=0 (C3: 64x64 ring tiles + LayerNorm row pass) /' >> $O/shapes.txt
-python bench.py --steps 300 --warmup 30 2> $O/bench.err | tail -1 > $O/bench.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline | tail -1 > $O/bench_driver_style_1.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline | tail -1 > $O/bench_driver_style_2.json 2>/dev/null
-python bench.py --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp.json 2>/dev/null
-GT_DP_GRAPH=1 python bench.py --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp_graph.json 2>/dev/null
-GT_DP_OVERLAP=1 python bench.py --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp_overlap.json 2>/dev/null
-GT_DP_GRAPH=1 GT_DP_OVERLAP=1 python bench.py --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp_overlap_graph.json 2>/dev/null
+python bench.py --full --steps 300 --warmup 30 2> $O/bench.err | tail -1 > $O/bench.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1 > $O/bench_driver_style_1.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1 > $O/bench_driver_style_2.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp.json 2>/dev/null
+GT_DP_GRAPH=1 python bench.py --full --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp_graph.json 2>/dev/null
+GT_DP_OVERLAP=1 python bench.py --full --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp_overlap.json 2>/dev/null
+GT_DP_GRAPH=1 GT_DP_OVERLAP=1 python bench.py --full --no-cpu-baseline --force-dp | tail -1 > $O/bench_force_dp_overlap_graph.json 2>/dev/null
 for i in 0 1; do GT_SEQ_SPLIT=1 GT_LIB_PATH=$L/libgroove_stamps.so python tools/seq_stamps.py $i > $O/seq_stamps_$i.txt 2>&1; done     # (the shipped path of these shapes: SPLIT)
 GT_SEQ_SPLIT=1 GT_LIB_PATH=$L/libgroove_stamps.so python tools/seq_stamps.py 2 > $O/seq_stamps_c2.txt 2>&1
 python tools/wg_unit_bench.py 64 > $O/wg_unit_bench.txt 2>&1
@@ -50,7 +50,7 @@ tail -3 $O/profile_rev.log
 cat $O/shapes.txt | tail -30
 # the bench lines again AFTER the PMC pass of this revision, so that roofline.traffic is this revision's own (bench.py refuses a traffic file of another csrc_sha)
 mkdir -p profiles && cp gpurun_out/profiles_$TAG/* profiles/ 2>/dev/null
-python bench.py --steps 300 --warmup 30 2> $O/bench.err | tail -1 > $O/bench.json
-python bench.py --steps 20 --warmup 5 | tail -1 > $O/bench_driver_style_full.json 2>/dev/null
+python bench.py --full --steps 300 --warmup 30 2> $O/bench.err | tail -1 > $O/bench.json
+python bench.py --full --steps 20 --warmup 5 | tail -1 > $O/bench_driver_style_full.json 2>/dev/null
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1
 tail -3 $O/pytest_gpu.txt

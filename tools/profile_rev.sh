@@ -16,7 +16,7 @@ mkdir -p $S
 cd /tmp && export TMPDIR=/tmp
 for w in $WL; do
   case $w in
-    c2) T="$R/bench.py --steps 100 --warmup 10 --no-cpu-baseline"; E="$R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-graph"; I=2 ;;
+    c2) T="$R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline"; E="$R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-graph"; I=2 ;;
     c3) T="$R/tools/shape_bench.py --only 5 --steps 30 --warmup 5"; E="$R/tools/shape_bench.py --only 5 --steps 10 --warmup 3 --no-graph"; I=5 ;;
     c4) T="$R/tools/shape_bench.py --only 7 --steps 30 --warmup 5"; E="$R/tools/shape_bench.py --only 7 --steps 10 --warmup 3 --no-graph"; I=7 ;;
     c5) T="$R/tools/shape_bench.py --only 11 --steps 30 --warmup 5"; E="$R/tools/shape_bench.py --only 11 --steps 10 --warmup 3 --no-graph"; I=11 ;;
