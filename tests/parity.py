@@ -82,7 +82,7 @@ def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=
     assert rel_err(d_hvo, np.concatenate(dpred, -1)) < 1e-5
     G = r.backward(train=p > 0)
     adopted = adopt_device_kinks(r, C, cfg)
-    assert adopted <= 4 + r.M * cfg["dim_feedforward"] * (len(C["enc"]) + len(C["dec"])) // 100000, adopted
+    assert adopted <= kink_bound(r, cfg), adopted
     Gr = ng.backward(P, cfg, C, dpred, dtype=np.float64)
     assert set(G) == set(Gr)
     for k in Gr:
@@ -531,31 +531,121 @@ def expected_packs(Pd, cfg):
     return np.concatenate(pf), np.concatenate(pb)
 
 
+def check_update(before, after, G, lr, adam=None, tag=None):
+    """One optimizer step of the device against the fp64 update of the oracle's gradients G, teacher-forced: the reference starts from the
+    device's own parameters `before` (and, for Adam, its own moments), so nothing of earlier steps propagates and the bar can be per element.
+    before / after / G: name -> array.  adam: None (SGD) or dict(m0, v0, m1, v1, t) -- the device's moments before / after the step and the
+    step number t the bias correction uses (beta1 0.9, beta2 0.999, eps 1e-8: the Runner's step state).
+    SGD: |dp_dev - dp_ref| <= GRAD_TOL * max(max |dp_ref|, lr 1e-5) + ulp_fp32(p_after), dp_ref = -lr G: the gradient bar of check_step
+    carried through the update, plus the fp32 rounding of p - lr g (it matters for LayerNorm gains near 1).
+    Adam: the moments within GRAD_TOL (m) / 2 GRAD_TOL (v) of the tensor's largest, the parameters within the live / strong bars of
+    check_train_step.  Raises AssertionError naming the step, the tensor and the element; returns the largest error / bar ratio."""
+    lr = float(np.float32(lr))
+    f64 = lambda a: np.asarray(a, np.float64)
+    ratio = 0.0
+    for k in G:
+        p0, p1, g = f64(before[k]), f64(after[k]), f64(G[k])
+
+        def worst(err, bar, what):
+            nonlocal ratio
+            ratio = max(ratio, float((err / bar).max(initial=0.0)))
+            excess = err - bar
+            if excess.max(initial=-1.0) > 0:
+                i = np.unravel_index(int(np.argmax(excess)), err.shape)
+                raise AssertionError("step %s %s%s element %s: |err| %.3g > bar %.3g (%d elements over)"
+                                     % (tag, k, what, tuple(int(j) for j in i), err[i], bar[i] if np.ndim(bar) else bar, int((excess > 0).sum())))
+
+        if adam is None:
+            d_ref = -lr * g
+            ulp = np.spacing(np.abs(np.asarray(after[k], np.float32))).astype(np.float64)
+            worst(np.abs((p1 - p0) - d_ref), GRAD_TOL * max(float(np.abs(d_ref).max()), lr * 1e-5) + ulp, "")
+            continue
+        b1, b2, eps, t = 0.9, 0.999, 1e-8, adam["t"]
+        m_ref = b1 * f64(adam["m0"][k]) + (1 - b1) * g
+        v_ref = b2 * f64(adam["v0"][k]) + (1 - b2) * g * g
+        # (floors: the moments of a gradient of 1e-5, check_step's floor for a numerically zero gradient tensor)
+        worst(np.abs(f64(adam["m1"][k]) - m_ref), GRAD_TOL * max(float(np.abs(m_ref).max()), (1 - b1) * 1e-5), " (first moment)")
+        worst(np.abs(f64(adam["v1"][k]) - v_ref), 2 * GRAD_TOL * max(float(np.abs(v_ref).max()), (1 - b2) * 1e-10), " (second moment)")
+        p_ref = p0 - (lr / (1 - b1 ** t)) * m_ref / (np.sqrt(v_ref) / np.sqrt(1 - b2 ** t) + eps)
+        scale = max(1.0, float(np.abs(p_ref).max()))
+        err = np.abs(p1 - p_ref)
+        live = np.abs(g) > 1e-6
+        worst(np.where(live, err, 0.0), 1e-3 * scale, " (live elements)")
+        strong = np.abs(g) > 0.1 * np.abs(g).max()
+        worst(np.where(strong, err, 0.0), 1e-4 * scale, " (well-conditioned elements)")
+    return ratio
+
+
+def kink_bound(r, cfg):
+    """How many ReLU decisions adopt_device_kinks may take from the device: about one per 1e6 pre-activations, at least 4."""
+    return 4 + r.M * cfg["dim_feedforward"] * (cfg["num_encoder_layers"] + cfg.get("num_decoder_layers", 0)) // 100000
+
+
+def check_decisions_current(r, C):
+    """The workspace tensors adopt_device_kinks reads (every layer's hact, the input layer's pre-activation a0) hold the values of the
+    forward that cache C describes -- after gt_train_step too, on whatever path ran it: a stale or never-written tensor would feed the
+    adoption decisions of another step."""
+    n_enc = len(C["enc"])
+    todo = [("hact", l, c["hact"]) for l, c in enumerate(C["enc"])] + [("hact", n_enc + l, c["hact"]) for l, c in enumerate(C["dec"])]
+    todo.append(("a0", 0, C["in_enc"]["a"]))
+    for name, l, ref in todo:
+        tol = 2.0 ** -8 if r.bf16_only(name, l) else 1e-4
+        err = rel_err(r.ws_get(name, l).reshape(-1), np.asarray(ref).reshape(-1))
+        assert err < tol, "%s of layer %d is not this step's: rel err %g" % (name, l, err)
+    return len(todo)
+
+
 def check_train_step(backend, cfg, B, p, algo=0, seq=True):
-    """gt_train_step == forward+loss+backward+update with the oracle's masks; second step uses step+1."""
+    """gt_train_step == forward+loss+backward+update with the oracle's masks, three steps; later steps use step+1.  Each step is checked
+    twice: teacher-forced (the fp64 oracle's step from the device's own parameters and moments before it, per element: check_update) and
+    along the free-running fp64 trajectory from the initial parameters.  Both oracle caches adopt the device's ReLU decisions at the kink."""
     cfg = dict(cfg, dropout=p)
     P = ng.init_params(cfg, seed=9, perturb=0.05)
     x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=4)
     Ld = cfg.get("num_decoder_layers", 0)
     tgt = shift_right(y) if Ld else None
-    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=0.05, seq=seq)
+    lr = 0.05
+    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=lr, seq=seq)
     r.set_params(P)
     cur = {k: v.astype(np.float64) for k, v in P.items()}
     folded = r.lib.cdll.gt_step_launches(ctypes.byref(r.c)) > 0     # sequence-resident path: the update writes the next step's weight packs
-    for step in range(3 if folded else 2):
+    bound = kink_bound(r, cfg)
+    f64 = lambda D: {k: np.asarray(v, np.float64) for k, v in D.items()}
+    steps = 3
+    for step in range(steps):
+        before = r.unflatten(r.params.numpy())
+        if algo == 1:
+            m0, v0 = ((r.unflatten(r.m.numpy()), r.unflatten(r.v.numpy())) if hasattr(r, "m")
+                      else ({k: np.zeros_like(a) for k, a in before.items()},) * 2)
         # from the second step on: GT_STEP_PACKS_CURRENT (4) -- the previous step's update left this step's fragment-ordered weights
         stats = r.train_step(x, y, 0.38, algo=algo, skip_update=4 if (folded and step > 0) else 0)
-        (h, v, o), C = ng.forward(cur, cfg, x, tgt=tgt, rng=(77, 5, step) if p > 0 else None, dtype=np.float64)
+        rng = (77, 5, step) if p > 0 else None
+        got = r.unflatten(r.params.numpy())
+        # teacher-forced: the oracle's step from where the device started it
+        (h, v, o), Ct = ng.forward(f64(before), cfg, x, tgt=tgt, rng=rng, dtype=np.float64)
+        tstats, dpt = ng.calculate_loss((h, v, o), y.astype(np.float64), 0.38)
+        assert abs(stats[0] - tstats[0]) < 2e-5 * max(1, abs(tstats[0])), (step, "teacher-forced loss", stats[0], tstats[0])
+        assert check_decisions_current(r, Ct) >= len(Ct["enc"]) + 1
+        adopted = adopt_device_kinks(r, Ct, cfg)
+        assert adopted <= bound, (step, adopted)
+        Gt = ng.backward(f64(before), cfg, Ct, dpt, dtype=np.float64)
+        adam = None
+        if algo == 1:
+            adam = dict(m0=m0, v0=v0, m1=r.unflatten(r.m.numpy()), v1=r.unflatten(r.v.numpy()), t=step + 1)
+        check_update(before, got, Gt, lr, adam=adam, tag=step)
+        # free-running fp64 trajectory
+        (h, v, o), C = ng.forward(cur, cfg, x, tgt=tgt, rng=rng, dtype=np.float64)
         rstats, dpred = ng.calculate_loss((h, v, o), y.astype(np.float64), 0.38)
         assert abs(stats[0] - rstats[0]) < 2e-5 * max(1, abs(rstats[0])), (step, stats[0], rstats[0])
+        adopted = adopt_device_kinks(r, C, cfg)
+        assert adopted <= bound, (step, adopted)
         G = ng.backward(cur, cfg, C, dpred, dtype=np.float64)
         if algo == 0:
-            cur = {k: cur[k] - 0.05 * G[k] for k in cur}
+            cur = {k: cur[k] - lr * G[k] for k in cur}
         else:
             if step == 0:
                 am, av = {k: np.zeros_like(v) for k, v in cur.items()}, {k: np.zeros_like(v) for k, v in cur.items()}
-            cur, am, av = ng.adam_step(cur, G, am, av, step + 1, 0.05)
-        got = r.unflatten(r.params.numpy())
+            cur, am, av = ng.adam_step(cur, G, am, av, step + 1, lr)
         for k in cur:
             # (adam: an element whose gradient is numerically zero moves by lr * g / (|g| + eps) -- its sign is noise; skip those)
             live = np.abs(G[k]) > 1e-6 if algo == 1 else np.ones(G[k].shape, bool)
@@ -572,7 +662,7 @@ def check_train_step(backend, cfg, B, p, algo=0, seq=True):
                 o, c = r.lib.ws_find(r.c, name)
                 assert c == want.size, (name, c, want.size)
                 assert np.array_equal(r.ws.numpy()[o:o + c].view(np.uint32), want.view(np.uint32)), (step, name)
-    assert r.step_state().step == (3 if folded else 2)
+    assert r.step_state().step == steps
     try:                                             # QUAD forward: no pair exchange timed out (error word of the region's header)
         o, _ = r.lib.ws_find(r.c, "seq_xchg")
         assert r.ws.numpy()[o:o + 1].view(np.uint32)[0] == 0

@@ -37,6 +37,22 @@ def test_train_step(cfg, p):
     parity.check_train_step("emu", cfg, 2, p)
 
 
+# two random shapes of the GPU fuzz (tools/fuzz_split_rule.py) whose third train step once missed the free-running bar on ONE element of
+# layers.2.linear1.weight: its row's fp64 pre-activation in layer 2 is 1e-8 / 3.4e-8 and the fp32 device lands on the other side of the
+# ReLU kink.  check_train_step adopts the device's decision there (adopt_device_kinks) as check_step does
+@pytest.mark.parametrize("seq", [True, "whole"])
+@pytest.mark.parametrize("cfg", [cfg_dict(64, 4, 128, 3, embedding_size_src=5), cfg_dict(64, 16, 320, 3)])
+def test_train_step_at_a_relu_kink(cfg, seq):
+    parity.check_train_step("emu", cfg, 2, 0.0, seq=seq)
+
+
+# Adam through the folded update + pack kernel (seq_update_pack_kernel) of the two-workgroups-per-sequence schedule: d_model 128 and the
+# vector-ALU attention of d_model 64 with 16 heads
+@pytest.mark.parametrize("cfg,p,seq", [(cfg_dict(128, 4, 32, 2), 0.1, "split"), (cfg_dict(64, 16, 256, 2), 0.2, True)])
+def test_train_step_adam_on_the_split_schedule(cfg, p, seq):
+    parity.check_train_step("emu", cfg, 2, p, algo=1, seq=seq)
+
+
 @pytest.mark.parametrize("cfg,use_thres", [(ENC, True), (ENC, False), (ENCDEC, True), (ENCDEC, False), (cfg_dict(64, 2, 24, 1, 2), True)])
 def test_predict(cfg, use_thres):
     parity.check_predict("emu", cfg, 2, use_thres)

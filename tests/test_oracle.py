@@ -97,3 +97,79 @@ def test_dropout_hash_statistics():
     assert np.allclose(m[m > 0], 1 / (1 - float(np.float32(0.24))))
     m2 = ng.keep_mask((1234, 99, 4), ng.layer_site(2, ng.S_FFN), 200000, 0.24)
     assert abs(((m > 0) == (m2 > 0)).mean() - (0.76 ** 2 + 0.24 ** 2)) < 0.01   # steps are independent
+
+
+def _synthetic_update(seed=0, lr=0.05):
+    """Parameters (a weight matrix, LayerNorm gains near 1, a bias) and fp64 gradients whose magnitudes spread over decades, the largest
+    update 3e-3 (150 times the old 2e-5 bar), like a real first step's"""
+    rnd = np.random.default_rng(seed)
+    P = {"w": (0.1 * rnd.standard_normal((64, 32))).astype(np.float32),
+         "norm.weight": (1 + 0.01 * rnd.standard_normal(32)).astype(np.float32),
+         "b": (0.05 * rnd.standard_normal(96)).astype(np.float32)}
+    G = {k: rnd.standard_normal(v.shape) * np.exp(rnd.standard_normal(v.shape)) for k, v in P.items()}
+    G = {k: g * 3e-3 / (lr * np.abs(g).max()) for k, g in G.items()}
+    return P, G, np.float32(lr)
+
+
+def _sgd(P, G, lr, which=None, fn=None):
+    """w - lr g in fp32 on the fp32-rounded gradient, as the device runs it; which = (tensor, flat index): that element computed by fn"""
+    out = {k: (P[k] - lr * G[k].astype(np.float32)).astype(np.float32) for k in P}
+    if which is not None:
+        k, i = which
+        out[k].reshape(-1)[i] = fn(P[k].reshape(-1)[i], G[k].reshape(-1), i)
+    return out
+
+
+def _old_bar_accepts(P, after, G, lr):
+    """check_train_step's free-running parameter bar before the per-step check existed: |p_dev - p_ref| < 2e-5 max(1, max |p|)"""
+    return all(np.abs(after[k] - (P[k].astype(np.float64) - float(lr) * G[k])).max() < 2e-5 * max(1.0, np.abs(P[k]).max()) for k in P)
+
+
+def test_update_check_catches_subtly_wrong_sgd_updates():
+    import parity
+    P, G, lr = _synthetic_update()
+    assert parity.check_update(P, _sgd(P, G, lr), G, lr) < 0.1               # the exact update passes with room
+    assert _old_bar_accepts(P, _sgd(P, G, lr), G, lr)
+    d = np.abs(float(lr) * G["w"]).reshape(-1)
+    # an element left where it was although its update (below the old bar) is not negligible
+    small = int(np.flatnonzero((d > 2e-6) & (d < 2e-5))[0])
+    frozen = _sgd(P, G, lr, ("w", small), lambda w, g, i: w)
+    # an element updated with its neighbour's gradient; the pair chosen so that the two updates differ by less than the old bar
+    dd = np.abs(np.diff(float(lr) * G["w"].reshape(-1)))
+    nb = int(np.flatnonzero((dd > 2e-6) & (dd < 2e-5))[0])
+    swapped = _sgd(P, G, lr, ("w", nb), lambda w, g, i: np.float32(w - lr * np.float32(g[i + 1])))
+    for bad in (frozen, swapped):
+        assert _old_bar_accepts(P, bad, G, lr)                                   # the gap the per-step check closes
+        with pytest.raises(AssertionError, match="w element"):
+            parity.check_update(P, bad, G, lr)
+    with pytest.raises(AssertionError):
+        parity.check_update(P, _sgd(P, G, np.float32(lr * 0.995)), G, lr)
+
+
+def _adam(P, G, m0, v0, t, lr):
+    """Adam in fp32 as the device runs it (seq_upd_elem / adam_kernel), on the fp32-rounded gradient"""
+    f = np.float32
+    b1, b2, eps = f(0.9), f(0.999), f(1e-8)
+    step_size, inv_sqrt_bc2 = f(lr) / (f(1) - b1 ** f(t)), f(1) / np.sqrt(f(1) - b2 ** f(t))
+    out, m1, v1 = {}, {}, {}
+    for k in P:
+        g = G[k].astype(f)
+        m1[k] = (b1 * m0[k] + (f(1) - b1) * g).astype(f)
+        v1[k] = (b2 * v0[k] + (f(1) - b2) * g * g).astype(f)
+        out[k] = (P[k] - step_size * m1[k] / (np.sqrt(v1[k]) * inv_sqrt_bc2 + eps)).astype(f)
+    return out, m1, v1
+
+
+def test_update_check_catches_adam_with_the_wrong_step():
+    import parity
+    P, G, lr = _synthetic_update(seed=1)
+    rnd = np.random.default_rng(2)
+    m0 = {k: (0.3 * g * rnd.random(g.shape)).astype(np.float32) for k, g in G.items()}          # mid-training moments
+    v0 = {k: (0.01 * g * g * rnd.random(g.shape)).astype(np.float32) for k, g in G.items()}
+    after, m1, v1 = _adam(P, G, m0, v0, 3, lr)
+    assert parity.check_update(P, after, G, lr, adam=dict(m0=m0, v0=v0, m1=m1, v1=v1, t=3)) < 0.1
+    after2, m2, v2 = _adam(P, G, m0, v0, 2, lr)                                                 # bias correction of step 2 at step 3
+    with pytest.raises(AssertionError, match="live elements"):
+        parity.check_update(P, after2, G, lr, adam=dict(m0=m0, v0=v0, m1=m2, v1=v2, t=3))
+    with pytest.raises(AssertionError, match="first moment"):                                   # moments from stale state
+        parity.check_update(P, after, G, lr, adam=dict(m0=m0, v0=v0, m1={k: 0.9 * m0[k] for k in m0}, v1=v1, t=3))
