@@ -254,6 +254,16 @@ int gt_set_xchg_spin_max(int polls);
  * Data-parallel hosts: grads[n_floats - 1] = 1 if this workspace's exchange error word is set, else 0 -- enqueue between the backward
  * (gt_train_step(skip_update = 1 / 2)) and the gradient all-reduce; a no-op for shapes without an exchange region. */
 int gt_dp_guard(const gt_config* cfg, float* grads, const float* ws, gt_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) over the flat gradient buffer of this configuration (no counterpart in the
+ * reference's step, which does not clip): total = grad_scale * ||grads[0 .. n_floats - 1)||_2 -- the guard element n_floats - 1 never
+ * counts, the alignment gaps between tensors hold zeros -- coef = min(1, max_norm / (total + 1e-6)) in fp32, grads *= coef over the same
+ * range.  Data-parallel: call it on the all-reduced sum; grad_scale (1/world) makes it the norm of the averaged gradient, as with DDP.
+ * Fixed summation order (fp64 across workgroups): bitwise reproducible, identical on every rank.  A NaN norm gives a NaN coefficient.
+ * out (device, 2 floats): [0] total norm before clipping, [1] the coefficient applied.  scratch: zero once, left zero.
+ * max_norm > 0 (+inf = measure only, never scales).  No host sync; capturable. */
+int64_t gt_clip_grad_norm_scratch_floats(const gt_config* cfg);
+int gt_clip_grad_norm(const gt_config* cfg, float* grads, const gt_step_state* state, float max_norm,
+                      float* out, float* scratch, gt_stream_t stream);
 /* LayerNorm inside the producing Linear / dgrad (csrc/gt_gemm64.h, round 5): at d_model 256 / 512, where the 64 x 64-tile kernels apply and
  * the whole grid is resident at once (a GPU's share of a data-parallel batch: 2048 tokens), the N / 64 workgroups of a row block exchange
  * their row partials inside the launch (tagged 8-byte granules, agent-scope stores / polling loads; "rowx" workspace region, zeroed once

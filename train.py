@@ -76,6 +76,9 @@ def build_parser():
     p.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "autocast"],
                    help="bf16: the Linear GEMMs take bf16 operands on the matrix cores (fp32 accumulate, fp32 master weights; BASELINE configs[4]); "
                         "autocast: ... and the encoder layers' Linear outputs are stored in bf16 (gt_config.precision = 2: what torch.autocast keeps in bf16)")
+    p.add_argument("--max_grad_norm", default=None, type=float,
+                   help="clip the gradients to this global 2-norm every step (torch.nn.utils.clip_grad_norm_; inf: only log the norm as "
+                        "train/grad_norm).  Also the YAML key max_grad_norm; the reference does not clip (default: off)")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible weight gradients (gt_set_deterministic: no token split in the weight-gradient kernels; +9-30 %% step time)")
     return p
@@ -97,6 +100,9 @@ def load_hyperparameters(args):
         hp[k] = yaml.safe_load(v)
     assert "experiment" in hp, "experiment not specified"
     hp.setdefault("load_model", None)          # InfillingRandom_test_large.yaml lacks the key
+    # gradient clipping: the YAML key, else --max_grad_norm (the reference's YAMLs lack the key: off, as there)
+    mgn = hp.get("max_grad_norm", args.max_grad_norm)
+    hp["max_grad_norm"] = None if mgn is None else float(mgn)
     return hp
 
 
@@ -238,7 +244,7 @@ def main(argv=None):
                        # test / validation LOSS after the epoch's batches, as the reference's train_loop arguments (ref:train.py:204-212)
                        test_inputs=test[0], test_gt=test[1], validation_inputs=val[0], validation_gt=val[1],
                        save=(rank == 0 and (ep in part or ep in full)), save_dir=save_dir,
-                       run_id=(wb.run.id if wb else "local"))
+                       run_id=(wb.run.id if wb else "local"), max_grad_norm=hp["max_grad_norm"])
         torch.cuda.synchronize()
         if rank == 0:
             n = min(len(loader) * hp["batch_size"], len(ds) // world) * world

@@ -86,7 +86,7 @@ extern "C" int gt_profile_report(char* buf, size_t buf_len, int max_rows) {
 #endif
   return n;
 }
-extern "C" int gt_version(void) { return 1; }
+extern "C" int gt_version(void) { return 2; }
 
 static int check_cfg(const gt_config* c) {
   if (!c) return gt_fail("gt_config is NULL");
@@ -1970,6 +1970,28 @@ extern "C" int gt_dp_guard(const gt_config* cfg, float* grads, const float* ws, 
   const PLayout P = param_layout(*cfg);
   gt_launch(dp_guard_kernel, dim3(1), dim3(64), (hipStream_t)stream, grads + P.total - 1, reinterpret_cast<const unsigned*>(ws + eo));
   return launch_status("gt_dp_guard");
+}
+
+// ------------------------------------------------------------------------------------ global-norm gradient clipping
+// Two launches over the whole flat gradient buffer but its guard element (gt_misc.h grad_norm_kernel / grad_scale_kernel), one workgroup
+// per GT_CLIP_CHUNK floats.  scratch = one partial per workgroup, then the ticket word; left all-zero by every call.
+extern "C" int64_t gt_clip_grad_norm_scratch_floats(const gt_config* cfg) {
+  if (check_cfg(cfg)) return 0;
+  return gt_clip_wgs(param_layout(*cfg).total) + 1;
+}
+extern "C" int gt_clip_grad_norm(const gt_config* cfg, float* grads, const gt_step_state* state, float max_norm, float* out, float* scratch,
+                                 gt_stream_t stream) {
+  if (check_cfg(cfg)) return -1;
+  if (!grads || !state || !out || !scratch) return gt_fail("gt_clip_grad_norm: grads / state / out / scratch must not be NULL");
+  if (!(max_norm > 0.f)) return gt_fail("gt_clip_grad_norm: max_norm %g must be > 0 (+inf: measure only)", (double)max_norm);
+  const int64_t n = param_layout(*cfg).total, nwg = gt_clip_wgs(n);
+  hipStream_t s = (hipStream_t)stream;
+  gt_prof_tag("clip_norm", 2.0 * (n - 1), 4.0 * (n - 1));
+  gt_launch(grad_norm_kernel, dim3((unsigned)nwg), dim3(256), s, (const float*)grads, n, state, max_norm, out, scratch,
+            reinterpret_cast<unsigned*>(scratch + nwg));
+  gt_prof_tag("clip_scale", 1.0 * (n - 1), 8.0 * (n - 1));
+  gt_launch(grad_scale_kernel, dim3((unsigned)nwg), dim3(256), s, grads, n, (const float*)out);
+  return launch_status("gt_clip_grad_norm");
 }
 
 // ------------------------------------------------------------------------------------ test aid: hold CUs

@@ -575,6 +575,102 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   }
 }
 
+// ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2): two passes over the flat gradient buffer --------
+// Both cover g[0, n - 1): the last float is the data-parallel guard element and never counts; the alignment gaps between tensors hold
+// zeros (the buffer's contract), so they add nothing.  Workgroup w owns the fixed chunk [w * GT_CLIP_CHUNK, (w + 1) * GT_CLIP_CHUNK): the
+// grid is a function of n alone, so the norm is bitwise the same run to run, on every data-parallel rank and in the host emulator.
+#define GT_CLIP_CHUNK 16384            // floats per workgroup: 256 threads x 16 float4
+static inline int64_t gt_clip_wgs(int64_t n) { return (n - 1 + GT_CLIP_CHUNK - 1) / GT_CLIP_CHUNK; }
+
+// Sum of squares: float4 loads in four fp32 chains per thread, the xor tree of gt_wave_sum per wave, the four waves through LDS, one
+// partial per workgroup published write-through.  The last arriver (gt_pub_ticket, as loss_kernel) adds the partials in index order in
+// fp64 (each lane a contiguous run, then the runs in order), times grad_scale^2 from the step state, and writes out[0] = total norm,
+// out[1] = min(1, max_norm / (total + 1e-6)) in fp32 as torch computes it (a NaN total gives a NaN coefficient; max_norm = +inf only
+// measures: 1).  It then zeroes the partials and re-arms the ticket, so the scratch is all-zero between launches.
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict__ g, int64_t n, const gt_step_state* st, float max_norm,
+                                                        float* __restrict__ out, float* __restrict__ part, unsigned* __restrict__ ticket) {
+  __shared__ float red[4];
+  __shared__ double run[256];
+  __shared__ int is_last;
+  const int64_t nu = n - 1;
+  const int64_t i0 = (int64_t)blockIdx.x * GT_CLIP_CHUNK + threadIdx.x * 4;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  if ((int64_t)(blockIdx.x + 1) * GT_CLIP_CHUNK <= nu) {
+    float4 v[GT_CLIP_CHUNK / 1024];
+#pragma unroll
+    for (int k = 0; k < GT_CLIP_CHUNK / 1024; ++k) v[k] = *reinterpret_cast<const float4*>(g + i0 + k * 1024);
+#pragma unroll
+    for (int k = 0; k < GT_CLIP_CHUNK / 1024; ++k) {
+      a0 += v[k].x * v[k].x; a1 += v[k].y * v[k].y; a2 += v[k].z * v[k].z; a3 += v[k].w * v[k].w;
+    }
+  } else {                                               // the last chunk: elements from nu on read as 0
+    for (int k = 0; k < GT_CLIP_CHUNK / 1024; ++k) {
+      const int64_t i = i0 + k * 1024;
+      if (i >= nu) break;
+      float4 v;
+      if (i + 4 <= nu) {
+        v = *reinterpret_cast<const float4*>(g + i);
+      } else {
+        v.x = g[i]; v.y = i + 1 < nu ? g[i + 1] : 0.f; v.z = i + 2 < nu ? g[i + 2] : 0.f; v.w = 0.f;
+      }
+      a0 += v.x * v.x; a1 += v.y * v.y; a2 += v.z * v.z; a3 += v.w * v.w;
+    }
+  }
+  const float s = gt_wave_sum((a0 + a1) + (a2 + a3));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    gt_pub_store(part + blockIdx.x, (red[0] + red[1]) + (red[2] + red[3]));
+    const unsigned t = gt_pub_ticket(ticket);               // (write-through partial, drained; no fences: gt_common.h)
+    is_last = (t == gridDim.x - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  const int nwg = (int)gridDim.x, len = (nwg + 255) / 256;
+  {
+    double acc = 0.0;
+    const int b = threadIdx.x * len, e = b + len < nwg ? b + len : nwg;
+    for (int w = b; w < e; ++w) acc += (double)gt_pub_load(part + w);
+    for (int w = b; w < e; ++w) part[w] = 0.f;
+    run[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sum = 0.0;
+    for (int r = 0; r * len < nwg; ++r) sum += run[r];
+    const float total = (float)(sqrt(sum) * fabs((double)st->grad_scale));
+    float coef = 1.0f;
+    if (!__builtin_isinf(max_norm)) {
+      const float c = max_norm / (total + 1e-6f);
+      coef = c > 1.0f ? 1.0f : c;                        // (torch.clamp(max=1): NaN stays NaN)
+    }
+    out[0] = total;
+    out[1] = coef;
+    *ticket = 0u;                                         // re-arm for the next call
+  }
+}
+
+// g[0, n - 1) *= out[1]; a coefficient of exactly 1 (no clipping this step) returns at once from every workgroup
+__global__ __launch_bounds__(256) void grad_scale_kernel(float* __restrict__ g, int64_t n, const float* __restrict__ out) {
+  const float c = out[1];
+  if (c == 1.0f) return;
+  const int64_t nu = n - 1;
+  const int64_t i0 = (int64_t)blockIdx.x * GT_CLIP_CHUNK + threadIdx.x * 4;
+  if ((int64_t)(blockIdx.x + 1) * GT_CLIP_CHUNK <= nu) {
+    float4 v[GT_CLIP_CHUNK / 1024];
+#pragma unroll
+    for (int k = 0; k < GT_CLIP_CHUNK / 1024; ++k) v[k] = *reinterpret_cast<const float4*>(g + i0 + k * 1024);
+#pragma unroll
+    for (int k = 0; k < GT_CLIP_CHUNK / 1024; ++k)
+      *reinterpret_cast<float4*>(g + i0 + k * 1024) = make_float4(v[k].x * c, v[k].y * c, v[k].z * c, v[k].w * c);
+    return;
+  }
+  for (int k = 0; k < GT_CLIP_CHUNK / 1024; ++k) {
+    const int64_t i = i0 + k * 1024;
+    for (int64_t j = i; j < i + 4 && j < nu; ++j) g[j] *= c;
+  }
+}
+
 // teacher forcing: tgt_in[b,t] = y[b,t-1], row 0 = zeros
 __global__ __launch_bounds__(256) void shift_right_kernel(const float* __restrict__ y, float* __restrict__ tgt, int n) {
   const int e = blockIdx.x * 256 + threadIdx.x;

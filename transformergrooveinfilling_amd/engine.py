@@ -15,6 +15,7 @@ all-reduce over the flat buffer and averaged inside the optimizer kernel (grad_s
 import ctypes
 import os
 import warnings
+import weakref
 
 import numpy as np
 import torch
@@ -31,6 +32,9 @@ MAX_GRAPHS = 4                         # captured step graphs kept per slot (lea
 MAX_SLOTS = 6                          # per-batch-size step slots kept (least recently created dropped first; the engine's own batch size stays)
 XCHG_POLL_EVERY = 16                   # train steps between two asynchronous reads of the in-launch exchanges' error word (see poll_exchange; the first
                                        # read starts with the slot's first step)
+
+
+_ENGINES = weakref.WeakSet()           # every live engine (clip_grad_norm_ in training.py finds the one that owns a parameter set)
 
 
 def _ptr(t):
@@ -85,7 +89,8 @@ class _LossSlot:
 class StepEngine:
     def __init__(self, d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_layers=0,
                  dropout=0.0, embedding_size_src=16, batch_size=None, optimizer="sgd", learning_rate=0.05,
-                 hit_loss_penalty=1.0, seed=0, device="cuda", world_size=1, use_graph="auto", lib=None, precision="fp32"):
+                 hit_loss_penalty=1.0, seed=0, device="cuda", world_size=1, use_graph="auto", lib=None, precision="fp32",
+                 max_grad_norm=None):
         self.device = torch.device(device)
         # The only way onto host memory is an EXPLICITLY passed library object (tests hand in the host-emulator build of
         # the same kernel sources to cover the multi-rank step sequence over gloo); nothing in the package does that.
@@ -112,6 +117,11 @@ class StepEngine:
         probe = _lib.make_config(1, embedding_size_src, d_model, n_heads, dim_feedforward, num_encoder_layers,
                                  num_decoder_layers, dropout)
         self.total, self.entries = self.lib.param_layout(probe)
+        self._probe_cfg = probe
+        # global-norm gradient clipping of every train step (torch.nn.utils.clip_grad_norm_ between backward and update); None = off: the
+        # step is the fused one, unchanged.  Settable at any time; the norm and the coefficient of a clipped step land in stats[6] / stats[7]
+        self.max_grad_norm = max_grad_norm
+        self._clip_scratch = None      # gt_clip_grad_norm's scratch (zeroed once; every call leaves it zero)
         self.names = layout.param_names(d_model, dim_feedforward, embedding_size_src, num_encoder_layers, num_decoder_layers)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.params = torch.zeros(self.total, **f32)
@@ -158,6 +168,7 @@ class StepEngine:
         self.B = int(batch_size) if batch_size else None
         if self.B:
             self.slot(self.B)
+        _ENGINES.add(self)
 
     cfg_flags = property(lambda self: self._flags_fallback | self._flags_recipe)
 
@@ -296,6 +307,51 @@ class StepEngine:
         self.lib.call("gt_optimizer_step", self.algo, _ptr(self.params), _ptr(self.grads), _ptr(self.m), _ptr(self.v),
                       ctypes.c_int64(self.total), _ptr(self.state), int(zero_grads), self.stream)
 
+    # ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) -------------------------------------------------
+    # A clipped step is the split sequence the data-parallel step already uses: forward + loss + backward (skip_update = 1), the two
+    # launches of gt_clip_grad_norm (norm into stats[6], coefficient into stats[7]; the loss kernels zero both, the 8-float stats copy
+    # carries them), then the update.  Single process it is one captured graph per max_norm.  The exchanges' fail-safe stays with the
+    # update: clipping never touches the guard element, and gt_optimizer_step_ws still refuses a step whose error word is set.
+    def _clip_norm(self, max_norm):
+        mn = float(max_norm)
+        if not mn > 0.0:
+            raise ValueError("max_grad_norm must be > 0 (inf: log the norm, never clip), got %r" % (max_norm,))
+        if self._clip_scratch is None:            # (zeroed once, outside any capture; every call leaves it zero)
+            n = int(self.lib.cdll.gt_clip_grad_norm_scratch_floats(ctypes.byref(self._probe_cfg)))
+            if n <= 0:
+                raise _lib.GrooveLibError("gt_clip_grad_norm_scratch_floats failed: %s" % self.lib.cdll.gt_last_error().decode())
+            self._clip_scratch = torch.zeros(n, dtype=torch.float32, device=self.device)
+        return mn
+
+    def _enqueue_clip(self, cfg, out, max_norm):
+        self.lib.call("gt_clip_grad_norm", ctypes.byref(cfg), _ptr(self.grads), _ptr(self.state), ctypes.c_float(max_norm), out,
+                      _ptr(self._clip_scratch), self.stream)
+
+    def _clip_step(self, s, max_norm):
+        self._enqueue_clip(s.cfg, ctypes.c_void_p(s.stats.data_ptr() + 6 * 4), max_norm)     # -> stats[6] norm, stats[7] coefficient
+
+    def _clipped_step(self, s, max_norm):
+        self._enqueue_step(s, 1)
+        self._clip_step(s, max_norm)
+        self.enqueue_update(slot=s)
+
+    def _graph_for_clip(self, s):
+        """graph_for for the clipped step: use_graph="auto" counts the split step's launches (the fused step's + 1: update and step_inc
+        apart) plus the two of the clip"""
+        if self.use_graph == "auto":
+            n = self.lib.cdll.gt_step_launches(ctypes.byref(s.cfg))
+            return not (0 < n and n + 3 <= EAGER_MAX_LAUNCHES)
+        return bool(self.use_graph)
+
+    def clip_grad_norm_(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) over the flat gradient buffer (module API: between loss.backward() and
+        opt.step()): the same two launches as a clipped step, no synchronisation.  -> the total norm before clipping, a 0-dim device
+        tensor.  Data-parallel: call it on the all-reduced sums (grad_scale = 1/world makes it the norm of the averaged gradient)."""
+        mn = self._clip_norm(max_norm)
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        self._enqueue_clip(self._probe_cfg, _ptr(out), mn)
+        return out[0]
+
     def graph_for(self, s):
         """Does slot s replay captured graphs?  (use_graph True / False / "auto": by the step's launch count)"""
         if self.use_graph == "auto":
@@ -305,11 +361,11 @@ class StepEngine:
             return s.use_graph
         return bool(self.use_graph)
 
-    def _replay(self, s, key, fn, aux=False, force=False):
+    def _replay(self, s, key, fn, aux=False, force=False, graph=None):
         """Replay the hipGraph captured for `key` on slot s (captured on first use).  aux=True: a graph that continues a
         step another graph began (second half of a bucketed backward) -- it keeps the slot's other graphs.  force=True: a graph
-        whatever graph_for says (the one-enqueue data-parallel step)."""
-        if not (force or self.graph_for(s)):
+        whatever graph_for says (the one-enqueue data-parallel step).  graph: the decision, when it is not graph_for's (clipped step)."""
+        if not (force or (self.graph_for(s) if graph is None else graph)):
             fn()
             return
         if key not in s.graphs:
@@ -462,6 +518,8 @@ class StepEngine:
         train_loop takes this path every `watch_log_freq` batches instead."""
         self._enqueue_step(s, 1)
         on_grads()
+        if self.max_grad_norm is not None:     # (the hooks see the gradients before clipping, as torch's backward hooks would)
+            self._clip_step(s, self._clip_norm(self.max_grad_norm))
         self.enqueue_update(slot=s)
 
     def train_step(self, x=None, y=None, B=None, on_grads=None):
@@ -477,6 +535,12 @@ class StepEngine:
             s.y.copy_(y, non_blocking=True)
         if self.world_size == 1 and not self.force_dp and on_grads is not None:
             self._watched_step(s, on_grads)
+        elif self.world_size == 1 and not self.force_dp and self.max_grad_norm is not None:
+            mn = self._clip_norm(self.max_grad_norm)
+            use = self._graph_for_clip(s)
+            if use:
+                self._note_fused_step(s)          # (the replay updates the parameters and writes the next step's weight copies)
+            self._replay(s, ("fused_clip", self.algo, self.penalty, mn), lambda: self._clipped_step(s, mn), graph=use)
         elif self.world_size == 1 and not self.force_dp:
             if self.graph_for(s):
                 self._note_fused_step(s)          # (a replay updates the parameters without running _enqueue_step)
@@ -494,6 +558,7 @@ class StepEngine:
             self._ar_plan = [tuple(b) for b in buckets] if two else [(0, self.total)]
             self._ar_issued = 0
             guard = self._guard_fn(s)
+            mn = None if self.max_grad_norm is None else self._clip_norm(self.max_grad_norm)     # clipping: after the last all-reduce, before the update
             if self.dp_graph and on_grads is None and not self.on_host:
                 # ONE enqueue per step: forward + backward, the all-reduce(s) and the update captured in one hipGraph -- the collectives are
                 # nodes of the graph (RCCL enqueues on its own stream: fork / join edges), nothing returns to Python between the halves
@@ -510,8 +575,11 @@ class StepEngine:
                         self._enqueue_step(s, 1)
                         guard()
                         self._ar(self.grads)
+                    if mn is not None:
+                        self._clip_step(s, mn)
                     self.enqueue_update(slot=s)
-                self._dp_whole(s, ("dp_whole", self.algo, self.penalty, len(buckets)), whole)
+                key = ("dp_whole", self.algo, self.penalty, len(buckets)) + (() if mn is None else (mn,))
+                self._dp_whole(s, key, whole)
                 self.poll_exchange(s)
                 return s.stats
             if two:
@@ -533,6 +601,8 @@ class StepEngine:
                 self._ar(self.grads)                         # RCCL sum over xGMI; averaged by grad_scale
             if on_grads is not None:
                 on_grads()                        # (data-parallel: the all-reduced sums; the update averages them by grad_scale)
+            if mn is not None:
+                self._clip_step(s, mn)
             self.enqueue_update(slot=s)
         self.poll_exchange(s)
         return s.stats
@@ -555,10 +625,18 @@ class StepEngine:
             gather()
             return self.train_step(B=s.B, on_grads=on_grads)
         if self.world_size == 1 and not self.force_dp:
-            gkey = ("fused_idx", self.algo, self.penalty) + key
-            if self.graph_for(s):
-                self._note_fused_step(s)
-            self._replay(s, gkey, lambda: (gather(), self._enqueue_step(s, 0)))
+            if self.max_grad_norm is not None:
+                mn = self._clip_norm(self.max_grad_norm)
+                gkey = ("fused_idx_clip", self.algo, self.penalty, mn) + key
+                use = self._graph_for_clip(s)
+                if use:
+                    self._note_fused_step(s)
+                self._replay(s, gkey, lambda: (gather(), self._clipped_step(s, mn)), graph=use)
+            else:
+                gkey = ("fused_idx", self.algo, self.penalty) + key
+                if self.graph_for(s):
+                    self._note_fused_step(s)
+                self._replay(s, gkey, lambda: (gather(), self._enqueue_step(s, 0)))
             if gkey in s.graphs:
                 s.keep[gkey] = (xs, ys)           # the captured graph holds their raw pointers: keep the tensors alive with it
                 for k in [k for k in s.keep if k not in s.graphs]:

@@ -254,18 +254,58 @@ def shift_right(y):
     return torch.cat([torch.zeros_like(y[:, :1]), y[:, :-1]], dim=1)
 
 
-def _metrics_dict(prefix, st):
-    return {prefix + "loss": st[0], prefix + "hit_accuracy": st[1], prefix + "hit_perplexity": math.exp(st[3]),
-            prefix + "bce_h": st[3], prefix + "mse_v": st[4], prefix + "mse_o": st[5]}
+def _metrics_dict(prefix, st, clipped=False):
+    d = {prefix + "loss": st[0], prefix + "hit_accuracy": st[1], prefix + "hit_perplexity": math.exp(st[3]),
+         prefix + "bce_h": st[3], prefix + "mse_v": st[4], prefix + "mse_o": st[5]}
+    if clipped:                                # a clipped step's gradient norm before clipping and the coefficient applied
+        d[prefix + "grad_norm"], d[prefix + "clip_coef"] = st[6], st[7]
+    return d
+
+
+# ------------------------------------------------------------------------------------------------ gradient clipping
+def _engine_owning(params):
+    """The StepEngine whose WHOLE parameter set `params` is (each one its Parameter view, each .grad its gradient view), else None."""
+    from .engine import _ENGINES
+    for eng in list(_ENGINES):
+        views, gviews = eng.views(), eng.views(eng.grads)
+        if len(params) != len(views):
+            continue
+        name_of = {v.data_ptr(): n for n, v in views.items()}
+        names = [name_of.get(p.data_ptr()) for p in params]
+        if None in names or len(set(names)) != len(names):
+            continue
+        if all(p.shape == views[n].shape and p.grad is not None and p.grad.data_ptr() == gviews[n].data_ptr()
+               and p.grad.shape == gviews[n].shape for p, n in zip(params, names)):
+            return eng
+    return None
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """Drop-in for torch.nn.utils.clip_grad_norm_.  When `parameters` are exactly one model's parameters (model.parameters()), the
+    norm type is 2 and error_if_nonfinite is off, the norm and the scaling run as two launches over the engine's flat gradient buffer
+    (StepEngine.clip_grad_norm_: no synchronisation; returns a 0-dim device tensor).  Anything else -- a subset, another norm type,
+    error_if_nonfinite, a max_norm <= 0 -- is torch's own function on the .grad tensors: slower, never different.  Data-parallel with
+    the package's optimizers: call it on the all-reduced gradients (train_loop does); it clips the averaged gradient, as with DDP."""
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    eng = None
+    if float(norm_type) == 2.0 and not error_if_nonfinite and float(max_norm) > 0.0:
+        eng = _engine_owning(params)
+        if eng is not None and eng.world_size > 1 and not eng._fused_opt:
+            eng = None                         # (a foreign optimizer has averaged the sums itself: grad_scale does not apply)
+    if eng is not None:
+        return eng.clip_grad_norm_(max_norm)
+    return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
 
 
 def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn, bce_fn, mse_fn, device,
                test_inputs=None, test_gt=None, validation_inputs=None, validation_gt=None, hit_loss_penalty=1,
-               save=False, save_dir=None, run_id=None, log_every=50, on_log=None):
+               save=False, save_dir=None, run_id=None, log_every=50, on_log=None, max_grad_norm=None):
     """One epoch (ref:train.py:195-215).  For every (x, y, idx) batch: forward, calculate_loss, backward, update.
     When model, loss_fn and optimizer are this package's, the whole batch body is ONE captured hipGraph replay
     (gt_train_step) and metrics leave the GPU as one 8-float copy every `log_every` batches; any other
-    combination takes the generic autograd path.  Returns the metrics of the last logged batch."""
+    combination takes the generic autograd path.  Returns the metrics of the last logged batch.
+    max_grad_norm (not in the reference): clip the gradients to this global 2-norm between backward and update
+    (torch.nn.utils.clip_grad_norm_; inf = only measure); the logged records then carry train/grad_norm and train/clip_coef."""
     model = groove_transformer
     _bind_engine(model)
     model.train()
@@ -285,6 +325,12 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
         eng.penalty = float(hit_loss_penalty)
         eng.algo = opt._algo
         opt._push_lr()
+    clipped = max_grad_norm is not None
+    if clipped:
+        max_grad_norm = float(max_grad_norm)
+    clip_keep = eng.max_grad_norm if fast else None
+    if fast and clipped:
+        eng.max_grad_norm = max_grad_norm      # the engine's clipped step (restored when the epoch ends)
     last, stats = None, None
     n_batches = 0
     # a dataset resident in HBM hands over INDICES: the gather is the first launch of the step's graph
@@ -306,53 +352,63 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
         if _wandb_active():
             wandb.log(rec, commit=False)
 
-    for batch, (X, y, _idx) in enumerate(batches):
-        n_batches += 1
-        model._watch_step = getattr(model, "_watch_step", 0) + 1
-        on_grads = watch_cb if (watch and model._watch_step % watch == 0) else None
-        if indexed:
-            stats = eng.train_step_indexed(dataloader.x, dataloader.y, _idx, on_grads=on_grads)
-            X = _idx                           # (only its length is used below)
-            if (batch + 1) % log_every == 0:
-                last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist())
-            if last is not None and (batch + 1) % log_every == 0:
+    try:
+        for batch, (X, y, _idx) in enumerate(batches):
+            n_batches += 1
+            model._watch_step = getattr(model, "_watch_step", 0) + 1
+            on_grads = watch_cb if (watch and model._watch_step % watch == 0) else None
+            if indexed:
+                stats = eng.train_step_indexed(dataloader.x, dataloader.y, _idx, on_grads=on_grads)
+                X = _idx                           # (only its length is used below)
+                if (batch + 1) % log_every == 0:
+                    last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped)
+                if last is not None and (batch + 1) % log_every == 0:
+                    rec = dict(last, epoch=epoch, batch=batch)
+                    if _wandb_active():
+                        wandb.log(rec, commit=True)
+                    if on_log:
+                        on_log(rec)
+                continue
+            X = X.to(device, torch.float32, non_blocking=True)
+            y = y.to(device, torch.float32, non_blocking=True)
+            if fast:
+                stats = eng.train_step(X, y, on_grads=on_grads)
+                if (batch + 1) % log_every == 0:
+                    last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped)
+            else:
+                opt.zero_grad()
+                pred = model(X) if encoder_only else model(X, shift_right(y))
+                out = loss_fn(pred, y, bce_fn, mse_fn, hit_loss_penalty)
+                out[0].backward()
+                if world > 1:
+                    if eng is not None:            # every .grad is a view of ONE flat buffer: one collective, not one per tensor
+                        torch.distributed.all_reduce(eng.grads)
+                        if not fused_opt:          # a foreign optimizer knows nothing of grad_scale: average here
+                            eng.grads /= world
+                    else:
+                        for p in model.parameters():
+                            torch.distributed.all_reduce(p.grad)
+                            p.grad /= world
+                if clipped:
+                    norm = clip_grad_norm_(model.parameters(), max_grad_norm)
+                opt.step()
+                last = {"train/loss": float(out[0]), "train/hit_accuracy": out[1], "train/hit_perplexity": out[2],
+                        "train/bce_h": out[3], "train/mse_v": out[4], "train/mse_o": out[5]}
+                if clipped:
+                    n32 = torch.tensor(float(norm), dtype=torch.float32)
+                    coef = torch.clamp(max_grad_norm / (n32 + 1e-6), max=1.0) if max_grad_norm != float("inf") else torch.tensor(1.0)
+                    last["train/grad_norm"], last["train/clip_coef"] = float(n32), float(coef)
+            if last is not None and ((batch + 1) % log_every == 0 or not fast):      # reference logs per batch; fast path every log_every
                 rec = dict(last, epoch=epoch, batch=batch)
                 if _wandb_active():
                     wandb.log(rec, commit=True)
                 if on_log:
                     on_log(rec)
-            continue
-        X = X.to(device, torch.float32, non_blocking=True)
-        y = y.to(device, torch.float32, non_blocking=True)
+    finally:
         if fast:
-            stats = eng.train_step(X, y, on_grads=on_grads)
-            if (batch + 1) % log_every == 0:
-                last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist())
-        else:
-            opt.zero_grad()
-            pred = model(X) if encoder_only else model(X, shift_right(y))
-            out = loss_fn(pred, y, bce_fn, mse_fn, hit_loss_penalty)
-            out[0].backward()
-            if world > 1:
-                if eng is not None:            # every .grad is a view of ONE flat buffer: one collective, not one per tensor
-                    torch.distributed.all_reduce(eng.grads)
-                    if not fused_opt:          # a foreign optimizer knows nothing of grad_scale: average here
-                        eng.grads /= world
-                else:
-                    for p in model.parameters():
-                        torch.distributed.all_reduce(p.grad)
-                        p.grad /= world
-            opt.step()
-            last = {"train/loss": float(out[0]), "train/hit_accuracy": out[1], "train/hit_perplexity": out[2],
-                    "train/bce_h": out[3], "train/mse_v": out[4], "train/mse_o": out[5]}
-        if last is not None and ((batch + 1) % log_every == 0 or not fast):      # reference logs per batch; fast path every log_every
-            rec = dict(last, epoch=epoch, batch=batch)
-            if _wandb_active():
-                wandb.log(rec, commit=True)
-            if on_log:
-                on_log(rec)
+            eng.max_grad_norm = clip_keep
     if fast and stats is not None:
-        last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist())
+        last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped)
     if isinstance(opt, GrooveAdam) and fast:
         for st in opt.state.values():
             st["step"] += n_batches
