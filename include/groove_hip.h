@@ -219,10 +219,6 @@ int gt_gather_batch(const float* xs, const float* ys, const int64_t* idx, int64_
  * HIP events on its own stream.  gt_profile_report synchronises and writes one text row per kernel
  * class: "label launches total_ms total_flops total_bytes".  Not graph-capturable while on. */
 int gt_profile_enable(int on);
-/* on: grouped weight-gradient dispatches run on an internal side stream (created once, on first use) and may overlap
- * the backward chain; recorded as fork/join edges when the call is being captured into a hipGraph.  off (default;
- * env GT_OVERLAP=1 switches the default): a single stream -- measured faster on ROCm 7.2, see DESIGN.md. */
-int gt_set_overlap(int on);
 /* Sequence-resident kernels (csrc/gt_seq.h): for encoder-only fp32 models with d_model <= 128 (% 16), dim_feedforward <= 512
  * (% 16), src_dim <= 32 and head_dim 16 / 32 / 64 or below 16, ONE workgroup per sequence runs the whole forward (and one the
  * whole backward) in a single launch -- or, in the SPLIT mode below, two workgroups per sequence and one launch per layer and

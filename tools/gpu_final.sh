@@ -10,8 +10,6 @@ python tools/shape_bench.py --steps 200 2>/dev/null > $O/shapes.txt
 for i in 0 1 2 3; do GT_SEQ=0 python tools/shape_bench.py --only $i --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_SEQ=0 (one kernel per op) /' >> $O/shapes.txt; done
 GT_SEQ_SPLIT=0 python tools/shape_bench.py --only 2 --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_SEQ_SPLIT=0 (one workgroup per sequence) /' >> $O/shapes.txt
 GT_SEQ_QUAD=0 python tools/shape_bench.py --only 2 --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_SEQ_QUAD=0 (two workgroups per sequence in every phase: round 3) /' >> $O/shapes.txt
-GT_SEQ_QUAD_BWD0=0 python tools/shape_bench.py --only 2 --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_SEQ_QUAD_BWD0=0 (four workgroups per sequence in the forward only) /' >> $O/shapes.txt
-GT_SEQ_FUSE_B0=0 python tools/shape_bench.py --only 2 --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_SEQ_FUSE_B0=0 (backward phase 0 as a launch of its own) /' >> $O/shapes.txt
 for l in 0 1 2; do GT_BF16_SHADOWS=$l python tools/shape_bench.py --only 11 --steps 30 --warmup 5 2>/dev/null | tail -1 | sed "s/^/GT_BF16_SHADOWS=$l /" >> $O/shapes.txt; done
 GT_SEQ_RIDE=0 python tools/shape_bench.py --only 2 --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_SEQ_RIDE=0 (grouped weight gradients at the end) /' >> $O/shapes.txt
 GT_PACK_FOLD=0 python tools/shape_bench.py --only 2 --steps 200 2>/dev/null | tail -1 | sed 's/^/GT_PACK_FOLD=0 (packing launch at the head of every step) /' >> $O/shapes.txt
@@ -29,8 +27,6 @@ for i in 7 11 13 5; do
   GT_FFN_KBITS=0 python tools/shape_bench.py --only $i --steps 40 --warmup 5 2>/dev/null | tail -1 | sed 's/^/GT_FFN_KBITS=0 (the FFN2 dgrad reads the activation instead of its keep bits) /' >> $O/shapes.txt
 done
 python tools/kbits_check.py > $O/kbits_check.txt 2>&1
-GT_ROW_FUSE_XCHG=0 python tools/shape_bench.py --only 5 --steps 100 2>/dev/null | tail -1 | sed 's/^/GT_ROW_FUSE_XCHG=0 (C3: row-owning LayerNorm tiles, the path until round 5) /' >> $O/shapes.txt
-GT_ROW_FUSE_BIG_MAX_D=0 GT_LN_XCHG=0 python tools/shape_bench.py --only 5 --steps 100 2>/dev/null | tail -1 | sed 's/^/GT_ROW_FUSE_BIG_MAX_D=0 GT_LN_XCHG=0 (C3: 64x64 ring tiles + LayerNorm row pass) /' >> $O/shapes.txt
 python bench.py --full --steps 300 --warmup 30 2> $O/bench.err | tail -1 > $O/bench.json
 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1 > $O/bench_driver_style_1.json 2>/dev/null
 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline | tail -1 > $O/bench_driver_style_2.json 2>/dev/null

@@ -70,7 +70,6 @@ _SIGS = {
     "gt_optimizer_step_ws": (ctypes.c_int, [_cfgp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "gt_grad_buckets": (ctypes.c_int, [_cfgp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "gt_profile_enable": (ctypes.c_int, [ctypes.c_int]),
-    "gt_set_overlap": (ctypes.c_int, [ctypes.c_int]),
     "gt_set_seq": (ctypes.c_int, [ctypes.c_int]),
     "gt_set_seq_split": (ctypes.c_int, [ctypes.c_int]),
     "gt_set_seq_quad": (ctypes.c_int, [ctypes.c_int]),

@@ -86,7 +86,7 @@ extern "C" int gt_profile_report(char* buf, size_t buf_len, int max_rows) {
 #endif
   return n;
 }
-extern "C" int gt_version(void) { return 2; }
+extern "C" int gt_version(void) { return 3; }
 
 static int check_cfg(const gt_config* c) {
   if (!c) return gt_fail("gt_config is NULL");
@@ -198,16 +198,11 @@ struct WLayout {
   int64_t kbits = -1, kbits_stride = 0;                // keep bits of the FFN activation, [layer][M / 32][F / 32][64] 16-bit words (gt_gemm32.h; round 6)
   int64_t wT = -1, wT_stride = 0;                      // precision = 1 without shadows: fp32 transposes of the encoder layers' matrices (dgrads as NT)
   struct TmpSet { int64_t dzA, dzAm, dzB, dzBm, dzC, dzCm, dhid, dqkv, dqkvx; };
-  std::vector<TmpSet> set;                           // 2 alternating sets, or one per layer (wgrad_deferred)
+  std::vector<TmpSet> set;                           // one per layer
 };
 // Every layer keeps its own backward temporaries, so ALL weight gradients of the step leave as one grouped dispatch per
 // tile class at the end of backward instead of one per layer: fewer kernel boundaries (~4 us each: C2 0.333 -> 0.319 ms)
-// and better-balanced launches (C4 bs512 11.0 -> 10.5 ms).  The macro bounds the token count up to which this applies
-// (default: always; the per-layer sets cost M*(7d+F) floats per layer, 1.6 GB at C4 bs512).
-#ifndef GT_WGRAD_DEFER_MAX_M
-#define GT_WGRAD_DEFER_MAX_M (1ll << 40)
-#endif
-static bool wgrad_deferred(const gt_config& c) { return (int64_t)c.batch * 32 <= GT_WGRAD_DEFER_MAX_M; }
+// and better-balanced launches (C4 bs512 11.0 -> 10.5 ms).
 static bool seq_supported(const gt_config& c);
 // bf16 SHADOWS of the GEMM operands (precision = 1): where the Linears of the encoder layers run on the big-tile kernel -- interior
 // 128-tiles, at least GT_T128H_MIN of them -- and the tensors' producers are the kernels that can write a bf16 copy (LayerNorm passes of d_model 256 /
@@ -240,19 +235,17 @@ static int bf16_shadow_level() {
   return g_bf16_shadows;
 }
 // precision = 1 where the shadows do not apply: fp32 W^T copies of the encoder layers' matrices, so that the dgrads run in the NT form
-// (GT_BF16_WT=0 switches it off; results: the same products, summed in the NT kernel's k order)
+// (results: the same products, summed in the NT kernel's k order)
 static bool bf16_shadows(const gt_config& c);
 static bool bf16_wt(const gt_config& c) {
-  static const int on = [] { const char* e = getenv("GT_BF16_WT"); return (e && e[0] == '0') ? 0 : 1; }();
-  return on && c.precision >= 1 && c.n_enc_layers > 0 && c.d_model % 32 == 0 && c.dim_ff % 32 == 0 && !bf16_shadows(c);
+  return c.precision >= 1 && c.n_enc_layers > 0 && c.d_model % 32 == 0 && c.dim_ff % 32 == 0 && !bf16_shadows(c);
 }
 static bool bf16_shadows(const gt_config& c) {
   const int on = bf16_shadow_level() > 0;
   const int64_t M = (int64_t)c.batch * 32;
   const int hd = c.n_heads > 0 ? c.d_model / c.n_heads : 0;
-  static const int attn_mfma = [] { const char* e = getenv("GT_ATTN_MFMA"); return (e && e[0] == '0') ? 0 : 1; }();      // (ctx / dqkv shadows)
   const int nmin = c.d_model < c.dim_ff ? c.d_model : c.dim_ff;            // every Linear of a layer on the big-tile kernel (its epilogue writes hact16 / dhid16)
-  return on && attn_mfma && wgrad_deferred(c) && c.precision >= 1 && c.n_enc_layers > 0 && (c.d_model == 256 || c.d_model == 512) && c.dim_ff % 128 == 0 &&
+  return on && c.precision >= 1 && c.n_enc_layers > 0 && (c.d_model == 256 || c.d_model == 512) && c.dim_ff % 128 == 0 &&
          M % 128 == 0 && (hd == 16 || hd == 32 || hd == 64 || hd == 128) && (M / 128) * (nmin / 128) >= GT_T128H_MIN;
 }
 // precision = 2 (round 5): bf16 where the bytes are.  On top of precision 1's operand-only tensors (level 2 of the shadows: ctx, hact, dhid,
@@ -269,14 +262,10 @@ extern "C" int gt_precision_in_force(const gt_config* cfg) {
   if (check_cfg(cfg)) return -1;
   return p2(*cfg) ? 2 : (cfg->precision ? 1 : 0);
 }
-#ifndef GT_WS_SKEW
-#define GT_WS_SKEW 0
-#endif
 static WLayout ws_layout(const gt_config& c) {
   WLayout W;
   int64_t cur = 0;
-  static const int64_t skew = [] { const char* e = getenv("GT_WS_SKEW"); return e ? (int64_t)atoll(e) / 64 * 64 : (int64_t)GT_WS_SKEW; }();   // floats between consecutive buffers
-  auto add = [&](int64_t n) { int64_t o = cur; cur += (n + 63) / 64 * 64 + skew; return o; };
+  auto add = [&](int64_t n) { int64_t o = cur; cur += (n + 63) / 64 * 64; return o; };
   const int64_t M = (int64_t)c.batch * 32, d = c.d_model, F = c.dim_ff, BH = (int64_t)c.batch * c.n_heads;
   W.x0 = add(M * d); W.a0 = add(M * d);
   const int nl = c.n_enc_layers + c.n_dec_layers;
@@ -308,9 +297,8 @@ static WLayout ws_layout(const gt_config& c) {
   W.ln_part = add(W.ln_part_stride * (2 * c.n_enc_layers + 3 * c.n_dec_layers + 2));
   W.dctx = add(M * d);
   W.da0_dec = c.n_dec_layers > 0 ? add(M * d) : -1;
-  // Backward temporaries: one set per layer (deferred weight gradients read them at the end of backward), or two
-  // alternating sets when the weight gradients leave layer by layer.
-  W.set.resize(wgrad_deferred(c) ? nl : 2);
+  // Backward temporaries: one set per layer (the weight gradients read them at the end of backward)
+  W.set.resize(nl);
   for (size_t k = 0; k < W.set.size(); ++k) {
     WLayout::TmpSet& t = W.set[k];
     t.dzA = add(M * d); t.dzAm = add(M * d); t.dzB = add(M * d); t.dzBm = add(M * d);
@@ -420,7 +408,7 @@ extern "C" int gt_ws_find(const gt_config* cfg, const char* name, int layer, int
   else if (n == "dzA" || n == "dzAm" || n == "dzB" || n == "dzBm" || n == "dzC" || n == "dzCm" || n == "dhid" || n == "dqkv" || n == "dqkvx") {
     // backward temporaries of one layer (kept per layer while the weight gradients are deferred to the end of backward)
     if (layer < 0 || layer >= (int)W.layers.size()) return gt_fail("gt_ws_find: layer %d out of range", layer);
-    const WLayout::TmpSet& t = W.set[(size_t)layer % W.set.size()];
+    const WLayout::TmpSet& t = W.set[layer];
     if (n == "dzA") set(t.dzA, M * d); else if (n == "dzAm") set(t.dzAm, M * d); else if (n == "dzB") set(t.dzB, M * d);
     else if (n == "dzBm") set(t.dzBm, M * d); else if (n == "dzC") set(t.dzC, M * d); else if (n == "dzCm") set(t.dzCm, M * d);
     else if (n == "dhid") set(t.dhid, M * F); else if (n == "dqkv") set(t.dqkv, M * 3 * d); else set(t.dqkvx, M * 3 * d);
@@ -459,8 +447,6 @@ struct Ctx {
   bool drop;                 // train mode with p > 0
   hipStream_t s;
   WgradBatch* wb;            // weight gradients queue up here and leave as grouped dispatches
-  hipStream_t side;          // stream the grouped wgrad dispatches run on (nullptr: the main stream)
-  hipEvent_t pending[2];     // last side-stream event that reads temporaries set 0 / 1 (nullptr: none)
   LnJobs* ln;                // LayerNorm parameter-gradient partials to be summed at the end of backward
 };
 // next partials block for a LayerNorm backward launched with `nwg` workgroups; registers the reduction job
@@ -518,7 +504,7 @@ static const uint16_t* sh_w(const Ctx& x, const float* W, bool transposed) {
 }
 struct Tmp { float *dzA, *dzAm, *dzB, *dzBm, *dzC, *dzCm, *dhid, *dqkv, *dqkvx; };
 static Tmp tmp_set(const Ctx& x, int gl) {
-  const WLayout::TmpSet& t = x.W.set[(size_t)gl % x.W.set.size()];
+  const WLayout::TmpSet& t = x.W.set[gl];
   float* ws = x.ws;
   Tmp r;
   r.dzA = ws + t.dzA; r.dzAm = x.drop ? ws + t.dzAm : r.dzA;
@@ -570,62 +556,8 @@ static void wgrad(const Ctx& x, const float* dY, int ldy, const float* X, int ld
   if (x.wb) wgrad_queue(*x.wb, g, x.s);
   else gemm_launch<true, true, EPI_ATOMIC>(g, x.s);
 }
-// ---- side stream for weight gradients ------------------------------------------------------------------------
-// Weight gradients are off the critical path (nothing in the backward chain reads them), so their grouped dispatches
-// run on a second stream and overlap the dgrad chain, which alone cannot fill 256 CUs at these sizes.  The stream and
-// a pool of events are created once, on first use (outside any capture: the engine's warm-up call); under hipGraph
-// capture the record/wait pairs become fork/join edges of the captured graph.
-// Measured on MI355X / ROCm 7.2: captured into a hipGraph the fork/join did NOT buy concurrency -- the step got 7 % slower,
-// 14 % once the chain kernels had shrunk -- so the default is OFF (GT_OVERLAP=1 or gt_set_overlap(1) turns it on for
-// experiments; it only has an effect when the weight gradients leave layer by layer, see wgrad_deferred).
-static int g_overlap = -1;
-#ifndef GT_EMU
-static hipStream_t g_side = nullptr;
-static std::vector<hipEvent_t> g_events;
-static size_t g_event_next = 0;
-static hipStream_t side_stream() {
-  if (g_overlap < 0) { const char* e = getenv("GT_OVERLAP"); g_overlap = (e && e[0] == '1') ? 1 : 0; }
-  if (!g_overlap) return nullptr;
-  if (!g_side) {
-    if (hipStreamCreateWithFlags(&g_side, hipStreamNonBlocking) != hipSuccess) { g_side = nullptr; return nullptr; }
-    g_events.resize(512);
-    for (auto& e : g_events) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-  }
-  return g_side;
-}
-static hipEvent_t next_event() { return g_events[g_event_next++ % g_events.size()]; }
-#else
-static hipStream_t side_stream() { return nullptr; }
-#endif
-extern "C" int gt_set_overlap(int on) { g_overlap = on != 0; return 0; }
 extern "C" int gt_set_deterministic(int on) { g_deterministic = on != 0; return 0; }
 
-// launch everything queued so far for the layer whose temporaries live in set `set` (call after the last producer of a
-// queued wgrad's inputs has been enqueued)
-static void wgrad_sync(Ctx& x, int set) {
-  if (!x.wb || x.wb->empty()) return;
-  if (wgrad_deferred(x.c)) return;                  // everything leaves at the end of the (phase of) backward: finish()
-#ifndef GT_EMU
-  if (x.side && !g_prof.on) {
-    hipEvent_t ready = next_event(), done = next_event();
-    (void)hipEventRecord(ready, x.s);
-    (void)hipStreamWaitEvent(x.side, ready, 0);
-    wgrad_flush(*x.wb, x.side);
-    (void)hipEventRecord(done, x.side);
-    x.pending[set & 1] = done;
-    return;
-  }
-#endif
-  wgrad_flush(*x.wb, x.s);
-}
-// before the main stream writes into temporaries set `set`: wait for the side-stream reader of that set
-static void acquire_set(Ctx& x, int set) {
-#ifndef GT_EMU
-  if (x.pending[set & 1]) { (void)hipStreamWaitEvent(x.s, x.pending[set & 1], 0); x.pending[set & 1] = nullptr; }
-#else
-  (void)x; (void)set;
-#endif
-}
 // dX = dY W   ("NN")
 // out16 (precision = 2): the result stored in bf16 ALONE at out16 (dense rows of N); dX is then not written
 static void dgrad_store(const Ctx& x, const float* dY, int ldy, const float* W, int ldw, float* dX, int N, int K, int accumulate,
@@ -685,9 +617,7 @@ static int ln_xchg_mode() {
   static const int env = [] { const char* e = getenv("GT_LN_XCHG"); return !e ? 1 : e[0] == '0' ? 0 : 2; }();
   return env;
 }
-// (never beside the side-stream weight gradients, GT_OVERLAP=1: their workgroups hold the LDS the rest of a row block's workgroups wait for -- measured:
-//  the exchange then runs into its polling bound, seconds per step)
-static bool ln_xchg(const Ctx& x) { return ln_xchg_mode() != 0 && !(x.c.flags & GT_CFG_NO_LN_XCHG) && x.W.rowx >= 0 && x.side == nullptr; }
+static bool ln_xchg(const Ctx& x) { return ln_xchg_mode() != 0 && !(x.c.flags & GT_CFG_NO_LN_XCHG) && x.W.rowx >= 0; }
 static void ln_xchg_args(const Ctx& x, GemmArgs& g) {
   g.rowx = reinterpret_cast<unsigned*>(x.ws + x.W.rowx);
   g.spin_max = g_xchg_spin_max > 0 ? g_xchg_spin_max : GT_ROWX_SPIN_MAX;
@@ -739,14 +669,12 @@ static bool ln_xchg_rows(const Ctx& x) {
   return ln_xchg_tile(g) != 0;
 }
 // Round 5: where the row exchange applies the 64x64 ring tiles + the norm in their epilogue beat the row-owning tiles too (d_model 256 at 8192 tokens,
-// C3: 5.20 ms with the row-owning tiles, 5.06 with 64x64 tiles + exchange -- 5.29 with 64x64 tiles and the norm as a row pass); GT_ROW_FUSE_XCHG=0
-// or GT_LN_XCHG=0 keeps the row-owning tiles
+// C3: 5.20 ms with the row-owning tiles, 5.06 with 64x64 tiles + exchange -- 5.29 with 64x64 tiles and the norm as a row pass); GT_LN_XCHG=0
+// keeps the row-owning tiles
 static bool row_fused(const Ctx& x) {
-  static const int big_max_d = [] { const char* e = getenv("GT_ROW_FUSE_BIG_MAX_D"); return e ? atoi(e) : GT_ROW_FUSE_BIG_MAX_D; }();     // (A/B switch)
-  static const bool over_xchg = [] { const char* e = getenv("GT_ROW_FUSE_XCHG"); return e && e[0] == '0'; }();
   if (x.c.precision) return false;
   if (x.d <= GT_ROW_FUSE_MAX_D) return true;
-  return x.M >= GT_ROW_FUSE_MIN_M && x.d <= big_max_d && (over_xchg || !ln_xchg_rows(x));
+  return x.M >= GT_ROW_FUSE_MIN_M && x.d <= GT_ROW_FUSE_BIG_MAX_D && !ln_xchg_rows(x);
 }
 static void ln_bwd(const Ctx& x, const float* dy, const float* res, const float* xhat, const float* rstd, int64_t gamma_off, float* dz,
                    float* dzm, int site, const uint16_t* dy16 = nullptr);
@@ -865,9 +793,8 @@ static int linear_res_ln(const Ctx& x, const float* in, int K, int64_t w_off, in
     if (t16 != nullptr) {
       // (precision 2 on the big tile: the pre-norm output never leaves the registers -- rounded to bf16 there, round16: the numbers of the
       //  bf16-stored form without its round trip.  At 2048 tokens the stored form + row pass stays: measured 0.866 / 0.867 ms against
-      //  0.870 / 0.870 fused (profiles/r06_ab_p2_fused_forward.txt); GT_P2_LN_FUSE=1 fuses there too)
-      static const bool p2fuse = [] { const char* e = getenv("GT_P2_LN_FUSE"); return e && e[0] == '1'; }();
-      if ((ln_xchg_tile(g) == 128 || p2fuse) && try_fused()) return 0;
+      //  0.870 / 0.870 fused (profiles/r06_ab_p2_fused_forward.txt))
+      if (ln_xchg_tile(g) == 128 && try_fused()) return 0;
       g.C = nullptr; g.C16 = t16; g.ldc16 = x.d;
       need16(gemm_on_big_kernel<false, EPI_STORE>(g), "Linear (+ LayerNorm) with a bf16-only output (precision 2)");
       gemm_launch<false, false, EPI_STORE>(g, x.s);
@@ -909,11 +836,9 @@ static int linear_res_ln(const Ctx& x, const float* in, int K, int64_t w_off, in
   }
   return 0;
 }
-// head dims served by the MFMA attention kernels (0: use the generic LDS/VALU kernels); GT_ATTN_MFMA=0 forces the generic ones
+// head dims served by the MFMA attention kernels (0: use the generic LDS/VALU kernels)
 static int attn_mfma_hd(const Ctx& x) {
-  static const int enabled = [] { const char* e = getenv("GT_ATTN_MFMA"); return (e && e[0] == '0') ? 0 : 1; }();
   const int hd = x.d / x.H;
-  if (!enabled) return 0;
   if (hd == 16 || hd == 32 || hd == 64 || hd == 128) return hd;
   return hd < 16 ? -16 : 0;                         // -16: the 16-wide kernels with zero-padded operands (head_dim 1..15)
 }
@@ -926,9 +851,8 @@ static int attn_mfma_hd(const Ctx& x) {
 #define GT_ATTN_CS_MAX_PAIRS 256
 #endif
 static bool attn_col_split(const Ctx& x, int pairs) {
-  static const int on = [] { const char* e = getenv("GT_ATTN_CS"); return (e && e[0] == '0') ? 0 : 1; }();
   const int hd = attn_mfma_hd(x);
-  return on && (hd == 64 || hd == 128) && pairs < GT_ATTN_CS_MAX_PAIRS;
+  return (hd == 64 || hd == 128) && pairs < GT_ATTN_CS_MAX_PAIRS;
 }
 // in16 (precision = 2): q / k / v are bf16 tensors at the same ELEMENT offsets (the qkv buffer holds bf16 in its first half)
 static void attention_fwd(const Ctx& x, const float* q, int ldq, const float* k, const float* v, int ldkv, float* P, float* ctx,
@@ -1017,8 +941,6 @@ static int make_ctx(Ctx& x, const gt_config* cfg, const float* params, float* gr
   x.drop = train && st != nullptr && cfg->dropout > 0.f;
   x.s = (hipStream_t)stream;
   x.wb = nullptr;
-  x.side = nullptr;
-  x.pending[0] = x.pending[1] = nullptr;
   x.ln = nullptr;
   return 0;
 }
@@ -1215,9 +1137,7 @@ static thread_local bool g_seq_packs_current = false;
 // between replaying a captured graph and plain launches: below ~25 nodes the graph's per-node cost exceeds what it saves.
 // the fused train step's last forward launch goes on into backward phase 0 (seq_fb_kernel): QUAD schedule, riders, head_dim 32
 static bool seq_fuse_b0(const gt_config& c) {
-  static const int fuse_env = [] { const char* e = getenv("GT_SEQ_FUSE_B0"); return (e && e[0] == '0') ? 0 : 1; }();
-  static const int quad_bwd0 = [] { const char* e = getenv("GT_SEQ_QUAD_BWD0"); return (e && e[0] == '0') ? 0 : 1; }();
-  return fuse_env && quad_bwd0 && seq_split(c) && seq_quad(c) && seq_ride(c) && c.d_model / c.n_heads == 32;
+  return seq_split(c) && seq_quad(c) && seq_ride(c) && c.d_model / c.n_heads == 32;
 }
 extern "C" int gt_step_launches(const gt_config* cfg) {
   if (check_cfg(cfg)) return -1;
@@ -1267,7 +1187,7 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
     gt_seq_launch_pack(a, (unsigned)((frags + 3) / 4), x.s);
   }
   const int hc = x.hd < 16 ? 0 : x.hd;             // head-dim class (one instantiation each: the attention bodies' registers differ 4x)
-  // fused train step on the QUAD schedule: the last phase's launch goes on into backward phase 0 (seq_fb_kernel; GT_SEQ_FUSE_B0=0: off)
+  // fused train step on the QUAD schedule: the last phase's launch goes on into backward phase 0 (seq_fb_kernel)
   const bool fuse_b0 = seq_fuse_b0(x.c) && a.loss_y != nullptr;
   // (its dgrad products -- output layer, FFN2, FFN1, out-proj of the last layer -- are counted where they run)
   gt_prof_tag("seq_fwd", fl + (fuse_b0 ? seq_b0_flops(x) : 0.0), 4.0 * x.M * (x.c.src_dim + x.c.n_enc_layers * (9.0 * x.d + x.F) + 27.0));
@@ -1415,8 +1335,7 @@ static void decoder_step(const Ctx& x, const float* pe, const float* tgt, int t,
 }
 static void output_layer_fwd(const Ctx& x, float* hvo_out) {
   const float* fin = x.ws + (x.c.n_dec_layers > 0 ? x.W.dec_final : x.W.memory);
-  static const bool skinny = [] { const char* e = getenv("GT_HEADS_KERNEL"); return !(e && e[0] == '0'); }();     // (A/B switch: 0 = the generic GEMM)
-  if (skinny && heads_fwd_ok(x.M, x.d, x.d, fin, x.prm + x.P.out_w)) {
+  if (heads_fwd_ok(x.M, x.d, x.d, fin, x.prm + x.P.out_w)) {
     // the fused train step hands the loss over as well (g_seq_loss, as for the sequence-resident launches): one launch for OutputLayer + loss
     HeadsLoss hl = {nullptr, 0.f, nullptr, nullptr, nullptr, nullptr};
     if (g_seq_loss.y != nullptr) {
@@ -1563,12 +1482,9 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
   const PLayout& P = x.P;
   if (!accumulate) (void)hipMemsetAsync(grads, 0, (size_t)P.total * sizeof(float), x.s);
   // Weight gradients are queued and leave as ONE grouped dispatch per tile class at the end of the (phase of) backward
-  // (finish()); every layer keeps its own temporaries (W.set) for that.  Only with GT_WGRAD_DEFER_MAX_M lowered below the
-  // token count do they leave layer by layer (wgrad_sync; two alternating sets; optionally on the side stream, where
-  // acquire_set() orders the reuse of a set behind its side-stream reader).
+  // (finish()); every layer keeps its own temporaries (W.set) for that.
   WgradBatch wbatch;
   x.wb = &wbatch;
-  x.side = side_stream();
   LnJobs lnjobs;
   lnjobs.n = 0; lnjobs.N = d; lnjobs.bump = nullptr;
   { const int64_t eo = x.W.rowx >= 0 ? x.W.rowx : x.W.seq_xchg; lnjobs.err = eo >= 0 ? reinterpret_cast<unsigned*>(ws + eo) : nullptr; }
@@ -1579,11 +1495,9 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     if (phase == 2) return 0;
     phase = 0;
   }
-  // end of a phase: join the side stream, sum the LayerNorm parameter-gradient partials queued so far
+  // end of a phase: the queued weight gradients leave, the LayerNorm parameter-gradient partials queued so far are summed
   auto finish = [&]() -> int {
-    if (!wbatch.empty()) wgrad_flush(wbatch, x.s);  // deferred weight gradients (wgrad_deferred): one grouped dispatch per tile class
-    acquire_set(x, 0);                              // join: every side-stream dispatch is ordered before what follows
-    acquire_set(x, 1);
+    if (!wbatch.empty()) wgrad_flush(wbatch, x.s);  // one grouped dispatch per tile class
     if (lnjobs.n > 0) {                             // LayerNorm dgamma/dbeta: one launch, fixed order
       lnjobs.bump = bump_state;
       gt_prof_tag("ln_param_reduce", 0, 4.0 * lnjobs.n * W.ln_part_stride);
@@ -1595,7 +1509,6 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
   if (use_seq(*cfg)) {
     // ---- sequence-resident path (gt_seq.h): the whole backward chain of every sequence in ONE launch; the weight gradients
     // (contractions over all sequences) and the LayerNorm parameter gradients leave as the grouped dispatch / the reduce
-    x.side = nullptr;
     if (d_hvo != nullptr) {
       gt_prof_tag("heads_bwd", 0, 12.0 * M * GT_TGT);
       gt_launch(heads_bwd_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, d_hvo, hvo, ws + W.dlogits, M * GT_TGT);
@@ -1623,9 +1536,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
         const int R = idle < busiest ? (idle > 0 ? idle : 1) : busiest;
         // the last phase's sequence work is short (attention backward + in-proj dgrad of layer 0): its riders take only the first
         // GT_SEQ_RIDE_LAST_PCT % of the tokens of each tile, the tail launch -- the whole chip -- adds the rest
-        static const int last_pct = [] { const char* e = getenv("GT_SEQ_RIDE_LAST_PCT"); const int v = e ? atoi(e) : GT_SEQ_RIDE_LAST_PCT; return v < 0 ? 0 : v > 100 ? 100 : v; }();
-        a.ride_last_k = (int)((int64_t)M * last_pct / 100) / 64 * 64;
-        if (last_pct == 100) a.ride_last_k = M;
+        a.ride_last_k = (int)((int64_t)M * GT_SEQ_RIDE_LAST_PCT / 100) / 64 * 64;
         fl += 2.0 * M * ((L - 1) * 3.0 * d * d + L * ((double)d * d + 2.0 * d * x.F))
               - 2.0 * (M - a.ride_last_k) * (per_layer + (L > 1 ? win : 0)) * 2048.0;
         if (g_seq_b0_fused) fl -= seq_b0_flops(x);                  // (phase 0 ran, and was counted, in the forward's last launch)
@@ -1634,8 +1545,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
         const int pcut = L - split_.split_layer + 1;                 // last backward phase of the first half (split_.nb == 2)
         const int p_lo = phase == 2 ? pcut + 1 : 0, p_hi = phase == 1 ? pcut : L;
         a.ln_nwg = nwg;
-        static const int quad_bwd0 = [] { const char* e = getenv("GT_SEQ_QUAD_BWD0"); return (e && e[0] == '0') ? 0 : 1; }();
-        const bool quad0 = quad_bwd0 && seq_quad(*cfg);
+        const bool quad0 = seq_quad(*cfg);
         const bool b0_done = g_seq_b0_fused && quad0;                // (phase 0 ran inside the forward's last launch)
         g_seq_b0_fused = false;
         for (int p = p_lo; p <= p_hi; ++p) {
@@ -1655,11 +1565,9 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
         }
         a.out_early = phase == 2 ? 1 : 0;
         // the tail: the rest of the last phase's tiles, then in-proj of layer 0 + input layer (token range split in two: two partial
-        // tiles adding onto zero commute, so this stays reproducible; GT_SEQ_TAIL_KS for experiments), the step-counter bump
-        static const int tail_ks = [] { const char* e = getenv("GT_SEQ_TAIL_KS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > 16 ? 16 : v; }();
+        // tiles adding onto zero commute, so this stays reproducible), the step-counter bump
         const int tiles = win + gt_seq_wg_tiles(d, cfg->src_dim) + (a.out_early ? 0 : gt_seq_wg_tiles(GT_TGT, d));
-        int ks = (gt_deterministic() && tail_ks > 2) ? 2 : tail_ks;
-        if (ks > M / 8) ks = M / 8;
+        const int ks = M / 8 < 2 ? M / 8 : 2;
         a.phase = L + 1; a.tail_phase = L + 1; a.tail_ksplit = ks; a.bump = bump_state;
         const int nrest = a.ride_last_k < M ? per_layer + (L > 1 ? win : 0) : 0;
         gt_prof_tag("seq_tail", 2.0 * M * (3.0 * d * d + (a.out_early ? 0.0 : 27.0 * d) + (double)d * cfg->src_dim) + 2.0 * (M - a.ride_last_k) * nrest * 2048.0,
@@ -1712,7 +1620,6 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     if (!row_fused(x)) {
       const LayerW& w = W.layers[top];
       Tmp t = tmp_set(x, top);
-      acquire_set(x, top);
       dgrad_store(x, ws + W.dlogits, GT_TGT, params + P.out_w, d, ws + W.dctx, d, GT_TGT, 0);
       ln_bwd2(x, ws + W.dctx, xh, rs, gfin, ws + W.dctx, ws + w.xhat2, ws + w.rstd2, Ld > 0 ? P.dec[Ld - 1].n3w : P.enc[L - 1].n2w,
               t.dzA, t.dzAm, lsite(top, GT_SITE_DROPF));
@@ -1754,16 +1661,13 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
         return -1;
       self_attn_bwd(x, p, w, t, yin, t.dzCm, gl);
       if (l > 0) {
-        wgrad_sync(x, gl);
         const LayerW& wp = W.layers[gl - 1];
         const Tmp tn = tmp_set(x, gl - 1);
-        acquire_set(x, gl - 1);
         if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzC, ws + wp.xhat2, ws + wp.rstd2, P.dec[l - 1].n3w, tn.dzA,
                         tn.dzAm, lsite(gl - 1, GT_SITE_DROPF)))
           return -1;
       } else {
         input_layer_bwd(x, p, t, t.dzC, ws + W.b0, tgt_in, GT_TGT, P.din_w, P.din_b, GT_SITE_PE_DEC, ws + W.da0_dec);
-        wgrad_sync(x, gl);
       }
     }
   }
@@ -1773,13 +1677,11 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     // encoder final norm backward (input: accumulated dmem) and the last encoder layer's closing norm: one row pass
     const LayerW& w = W.layers[L - 1];
     const Tmp t = tmp_set(x, L - 1);
-    acquire_set(x, L - 1);
     ln_bwd2(x, ws + W.dmem, ws + W.enc_xhat, ws + W.enc_rstd, P.encn_w, ws + W.dctx, ws + w.xhat2, ws + w.rstd2, P.enc[L - 1].n2w,
             t.dzA, t.dzAm, lsite(L - 1, GT_SITE_DROPF));
   } else if (phase != 2 && !top_norm_done) {
     const LayerW& w = W.layers[L - 1];
     const Tmp t = tmp_set(x, L - 1);
-    acquire_set(x, L - 1);
     ln_bwd(x, ws + W.dctx, nullptr, ws + w.xhat2, ws + w.rstd2, P.enc[L - 1].n2w, t.dzA, t.dzAm, lsite(L - 1, GT_SITE_DROPF));
   }
   for (int l = (phase == 2 && Ld == 0) ? split.split_layer - 1 : L - 1; l >= 0; --l) {
@@ -1790,17 +1692,14 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     if (ffn_bwd(x, p, w, t, ws + w.x1, t.dzA, t.dzAm, ws + w.xhat1, ws + w.rstd1, p.n1w, t.dzB, t.dzBm, lsite(l, GT_SITE_DROP1))) return -1;
     self_attn_bwd(x, p, w, t, lin, t.dzBm, l);
     if (l > 0) {
-      wgrad_sync(x, l);
       const LayerW& wp = W.layers[l - 1];
       const Tmp tn = tmp_set(x, l - 1);
-      acquire_set(x, l - 1);
       if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzB, ws + wp.xhat2, ws + wp.rstd2, P.enc[l - 1].n2w, tn.dzA, tn.dzAm,
                       lsite(l - 1, GT_SITE_DROPF)))
         return -1;
       if (phase == 1 && Ld == 0 && l == split.split_layer) return finish();   // layers >= split are final; (dzA, dzAm) of l-1 handed over
     } else {
       input_layer_bwd(x, p, t, t.dzB, ws + W.a0, xin, cfg->src_dim, P.in_w, P.in_b, GT_SITE_PE_ENC, ws + W.dctx);
-      wgrad_sync(x, l);
     }
   }
   return finish();
@@ -2074,26 +1973,17 @@ static int predict_impl(const gt_config* cfg, const float* params, const float* 
   if (!tgt_scratch) return gt_fail("gt_predict: encoder-decoder model needs tgt_scratch");
   // greedy decode: tgt row 0 = zeros, row t+1 = thresholded step t.  The encoder memory and every layer's cross-attention
   // K/V are computed once; step t then touches only row t of each sequence (decoder_step; the self-attention K/V rows of
-  // the earlier steps are the cache).  GT_PREDICT_FULL=1 keeps the plain form -- the whole decoder stack over all 32
-  // positions at every step, 20-30x the work -- for A/B runs and tests.
+  // the earlier steps are the cache).
   float* tmp = ws + x.W.hvo_tmp;
   (void)hipMemsetAsync(tgt_scratch, 0, (size_t)M * GT_TGT * sizeof(float), x.s);
-  static const int full = [] { const char* e = getenv("GT_PREDICT_FULL"); return (e && e[0] == '1') ? 1 : 0; }();
-  if (!full) {
-    const int d = x.d, L = cfg->n_enc_layers;
-    for (int l = 0; l < cfg->n_dec_layers; ++l) {
-      const LayerP& p = x.P.dec[l];
-      const LayerW& w = x.W.layers[L + l];
-      linear_fwd(x, ws + x.W.memory, d, x.prm + p.xa.in_w + (int64_t)d * d, x.prm + p.xa.in_b + d, ws + w.kvx, 2 * d, 2 * d, d);
-    }
+  const int d = x.d, L = cfg->n_enc_layers;
+  for (int l = 0; l < cfg->n_dec_layers; ++l) {
+    const LayerP& p = x.P.dec[l];
+    const LayerW& w = x.W.layers[L + l];
+    linear_fwd(x, ws + x.W.memory, d, x.prm + p.xa.in_w + (int64_t)d * d, x.prm + p.xa.in_b + d, ws + w.kvx, 2 * d, 2 * d, d);
   }
   for (int t = 0; t < 32; ++t) {
-    if (full) {
-      if (decoder_fwd(x, pe, tgt_scratch)) return -1;
-      output_layer_fwd(x, tmp);
-    } else {
-      decoder_step(x, pe, tgt_scratch, t, tmp);
-    }
+    decoder_step(x, pe, tgt_scratch, t, tmp);
     gt_launch(predict_head_kernel, dim3((B * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)tmp, hvo_out, tgt_scratch, thres,
               use_thres, t, B, seed, idx0);
   }

@@ -129,9 +129,6 @@ __device__ static inline uint32_t gt_drop_key(const DropArgs& d) {
 // multiplier for element idx: scale if kept, 0 if dropped
 __device__ static inline float gt_drop_mul(const DropArgs& d, uint32_t key, uint32_t idx) {
   if (d.thr == 0u || d.st == nullptr) return 1.0f;
-#if defined(GT_ACCT_NOHASH)
-  return (idx ^ key) == 0x12345u ? 0.0f : d.scale;      // (measurement build, WRONG RESULTS: what the per-element hash costs the one-kernel-per-op path)
-#endif
   return ((gt_fmix32((idx * 0x9E3779B1u) ^ key) >> 8) >= d.thr) ? d.scale : 0.0f;
 }
 

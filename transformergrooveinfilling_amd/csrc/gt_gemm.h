@@ -29,9 +29,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#ifndef GT_MIDSLAB_STORE
-#define GT_MIDSLAB_STORE 1
-#endif
 enum {
   EPI_STORE = 0,          // C = acc + bias (+ C if accumulate)
   EPI_ATOMIC = 1,         // atomicAdd(C, acc)            (split-K wgrad; + bias-grad column sums of A)
@@ -411,7 +408,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bx, const
       //  accumulators VGPR<->AGPR around every few MFMAs, exposing the LDS latency each time)
 #pragma unroll
       for (int kk = 0; kk < BK / 16; ++kk) {
-        if (GT_MIDSLAB_STORE && BK / 16 >= 2 && TM * TN >= 16 && kk == BK / 32 && kt + 1 < nk) {
+        if (BK / 16 >= 2 && TM * TN >= 16 && kk == BK / 32 && kt + 1 < nk) {
           // mid-slab hand-over: the next slab goes into the other LDS buffer while half of this slab's MFMAs are still to
           // come (that buffer was last read before the previous barrier), so the barrier below waits on nothing
           la.store(smem + (cur ^ 1) * SA_SZ, SA_STR, tid);
@@ -455,7 +452,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bx, const
           for (int kk = 0; kk < BK; ++kk) bsum += sA[kk * SA_STR + tid];
         }
       }
-      if (kt + 1 < nk && !(GT_MIDSLAB_STORE && BK / 16 >= 2 && TM * TN >= 16)) {
+      if (kt + 1 < nk && !(BK / 16 >= 2 && TM * TN >= 16)) {
         la.store(smem + (cur ^ 1) * SA_SZ, SA_STR, tid);
         lb.store(smem + 2 * SA_SZ + (cur ^ 1) * SB_SZ, SB_STR, tid);
       }
@@ -718,7 +715,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN >= 16 && TN 
   // (the two input-layer epilogues hold a second and third 64-register operand set next to the accumulators: under the
   //  256-register cap of two waves per SIMD they spilled 380 / 12 bytes per lane -- they run once per step, one wave is fine)
   __shared__ __attribute__((aligned(16))) float smem[GemmCfg<WM, WN, TM, TN, BK_, AKM, BKM, EPI, PREC>::SMEM];
-#ifndef GT_NO_XCD_REMAP
   if (gridDim.z == 1) {
     // XCD-aware placement (as in wgrad_group_kernel): workgroups are dealt round-robin over the 8 XCDs in dispatch order
     // (x fastest), so the tiles of one A row-panel would land in 8 different L2s and the panel would cross the fabric 8
@@ -730,7 +726,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 && TM * TN >= 16 && TN 
     gemm_body<WM, WN, TM, TN, BK_, AKM, BKM, EPI, PREC>(g, b % gx, b / gx, 0, smem);
     return;
   }
-#endif
   gemm_body<WM, WN, TM, TN, BK_, AKM, BKM, EPI, PREC>(g, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 

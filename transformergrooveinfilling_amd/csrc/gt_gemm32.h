@@ -96,9 +96,6 @@ __device__ __forceinline__ void gemm32_store_epilogue(const GemmArgs& g, const f
         const int row = m0 + wm * (32 * TA) + ta * 32 + r32;
         rin[ta][q4] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (EPI == EPI_STORE && g.accumulate) rin[ta][q4] = *reinterpret_cast<const f32x4*>(g.C + (size_t)row * g.ldc + col);
-#if defined(GT_ACCT_NOMASK)
-        if (EPI == EPI_MASK_NZ) { rin[ta][q4] = f32x4{1.f, 1.f, 1.f, 1.f}; continue; }    // (measurement build, WRONG RESULTS: the FFN2 dgrad without its mask read)
-#endif
         if (EPI == EPI_MASK_NZ && g.kbits != nullptr) continue;       // (the mask comes as bits: kb below)
         if (EPI == EPI_MASK_NZ && g.res16 != nullptr) {      // the mask source (hact) lives in bf16 only: zero / non-zero is all that is asked
           const uint2 hb = *reinterpret_cast<const uint2*>(g.res16 + (size_t)row * g.ldres + col);

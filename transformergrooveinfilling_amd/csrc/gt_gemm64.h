@@ -18,12 +18,6 @@
 #pragma once
 // (included at the end of gt_gemm.h, after gt_gemm32.h)
 
-#ifndef GT_G64_DEEP
-#define GT_G64_DEEP 0           /* fp32 MFMA loop: 1 = a three-deep register ring (slab t + 4 requested in the second half of slab t), 0 = the
-                                   two-deep ring of gt_gemm32.h.  Measured (round 5, gemm_bench, M 2048): three-deep 13.6 / 32.5 / 34.6 us against
-                                   12.8 / 31.2 / 33.4 us (N 512 K 512 / N 512 K 1536 / N 1536 K 512): bytes in flight are not what holds the loop at
-                                   1.15 us per 64-wide slab (MFMA issue 0.85 us at 2.4 GHz -- ~0.97 us at the ~2.1 GHz the chip holds under this load) */
-#endif
 struct Gemm64Cfg {
   static constexpr int BM = 64, BN = 64, BK = 64, NT = 256;
   static constexpr int STR = 64 + 4, SZ = 64 * STR;           // floats: [64 rows][BK + 4] or [BK k][64 + 4]
@@ -799,14 +793,9 @@ __global__ __launch_bounds__(256, 2) void gemm64_kernel(GemmArgs g) {
   const int offa = (wm * 32 + r32) * STR + 4 * h;
   const int offb = 2 * SZ + (BKM ? (4 * h) * STR + wn * 32 + r32 : (wn * 32 + r32) * STR + 4 * h);
 
-  // (GT_G64_DEEP: the third register set of the three-deep ring -- slab t + 1 waits in registers, t + 2 and t + 3 are in flight)
-  f32x4 ua[PER], ub[PER];
-  auto kof = [&](const int t) { return (t < nk ? t : nk - 1) * BK; };
   G64_LD(va, vb, 0)
   G64_LD(wa, wb, BK)
-  if constexpr (PREC == 0 && GT_G64_DEEP) { G64_LD(ua, ub, kof(2)) }
   G64_ST(va, vb, 0)
-  if constexpr (PREC == 0 && GT_G64_DEEP) { G64_LD(va, vb, kof(3)) }
   __syncthreads();
 
   if constexpr (PREC == 1) {
@@ -899,39 +888,10 @@ __global__ __launch_bounds__(256, 2) void gemm64_kernel(GemmArgs g) {
     G64_GRPW3() G64_GRPW3() G64_GRPW2() GT_SCHED_FENCE()                                       \
     __syncthreads();                                                                           \
     G64_RD(fa0, fb0, (CUR) ^ 1, 0) G64_MM(fa1, fb1) G64_GRP0() GT_SCHED_FENCE()
-    // the same slab on the three-deep ring.  CUR: LDS buffer holding slab t; (NA, NB): registers holding slab t + 1 -- written to the other
-    // buffer behind groups 0-2, then reloaded with slab t + 4 behind groups 3-5
-#define G64_SLAB3(CUR, NA, NB, t)                                                              \
-    if ((t) < nk) {                                                                            \
-    G64_STA(NA, (CUR) ^ 1, 0) G64_STB(NB, (CUR) ^ 1, 0) G64_STA(NA, (CUR) ^ 1, 1)              \
-    G64_RD(fa1, fb1, CUR, 1) G64_MM(fa0, fb0)                                                  \
-    G64_STB(NB, (CUR) ^ 1, 1) G64_STA(NA, (CUR) ^ 1, 2) G64_STB(NB, (CUR) ^ 1, 2)              \
-    G64_RD(fa0, fb0, CUR, 2) G64_MM(fa1, fb1)                                                  \
-    G64_STA(NA, (CUR) ^ 1, 3) G64_STB(NB, (CUR) ^ 1, 3)                                        \
-    G64_RD(fa1, fb1, CUR, 3) G64_MM(fa0, fb0)                                                  \
-    G64_GRPW3() G64_GRPW3() G64_GRPW2() GT_SCHED_FENCE()                                       \
-    { const int k4_ = kof((t) + 4);                                                            \
-      G64_LD(NA, NB, k4_) }                                                                    \
-    G64_RD(fa0, fb0, CUR, 4) G64_MM(fa1, fb1)                                                  \
-    G64_RD(fa1, fb1, CUR, 5) G64_MM(fa0, fb0)                                                  \
-    G64_RD(fa0, fb0, CUR, 6) G64_MM(fa1, fb1)                                                  \
-    G64_RD(fa1, fb1, CUR, 7) G64_MM(fa0, fb0)                                                  \
-    G64_GRP3(0x20) G64_GRP3(0x20) G64_GRP2(0x20) G64_GRP0() GT_SCHED_FENCE()                   \
-    __syncthreads();                                                                           \
-    G64_RD(fa0, fb0, (CUR) ^ 1, 0) G64_MM(fa1, fb1) G64_GRP0() GT_SCHED_FENCE()                \
+    for (int kt = 0; kt < nk; kt += 2) {
+      G64_SLAB(0, wa, wb, va, vb, kt)
+      G64_SLAB(1, va, vb, wa, wb, kt + 1)
     }
-    if constexpr (GT_G64_DEEP) {
-      for (int kt = 0; kt < nk; kt += 6) {
-        G64_SLAB3(0, wa, wb, kt) G64_SLAB3(1, ua, ub, kt + 1) G64_SLAB3(0, va, vb, kt + 2)
-        G64_SLAB3(1, wa, wb, kt + 3) G64_SLAB3(0, ua, ub, kt + 4) G64_SLAB3(1, va, vb, kt + 5)
-      }
-    } else {
-      for (int kt = 0; kt < nk; kt += 2) {
-        G64_SLAB(0, wa, wb, va, vb, kt)
-        G64_SLAB(1, va, vb, wa, wb, kt + 1)
-      }
-    }
-#undef G64_SLAB3
 #undef G64_SLAB
 #undef G64_RD
 #undef G64_MM

@@ -60,27 +60,6 @@ __shared__ long long* gt_sub_ptr;      // sub-stage stamps of ONE matmul stage (
 // Stage hand-overs inside these kernels go through LDS only (the global stores are copies for LATER kernels: saved activations,
 // weight-gradient operands), so the stage barrier is GT_BARRIER(): it waits for this wave's LDS traffic, not for its
 // outstanding global stores.
-// Byte accounting (diagnostic builds only, tools/acct_writes.sh; WRONG RESULTS, measured with rocprofv3 --pmc WRITE_SIZE): GT_SEQ_ACCT bit 0 = the
-// forward keeps only what the next launch reads (layer output, q / k / v) and skips the stores saved for the backward alone (P, ctx, x1, xhat1,
-// hact, xhat2); bit 1 = the pair exchange's consumer does not re-zero what it read; bit 2 = no pair-exchange stores at all.
-// Result (profiles/r06_c2_write_accounting.txt): of the 24.7 MB a forward launch of the headline step writes, 9.5 are saved activations, 4.2 the
-// exchange's granules, 4.2 their re-zeroing, 6.8 the hand-over to the next launch (layer output, q / k / v) and the rest.
-#ifndef GT_SEQ_ACCT
-#define GT_SEQ_ACCT 0
-#endif
-#ifndef GT_SEQ_PFB_LN
-#define GT_SEQ_PFB_LN 1    /* ... and the backward chain's LayerNorm operands at the phase's start (A/B switch) */
-#endif
-#ifndef GT_SEQ_PFLN128
-#define GT_SEQ_PFLN128 0   /* d_model 128, SPLIT / QUAD kernels: the LayerNorm passes' small operands (bias / gamma / beta; backward: x-hat / rstd / gamma) requested ahead, as at
-                              d_model 32 -- measured 0.3-0.5 % SLOWER on the headline (0.1991 vs 0.1982 ms, three interleaved bench pairs, profiles/r06_ab_pfln128.txt): off */
-#endif
-#ifndef GT_SEQ_PF64
-#define GT_SEQ_PF64 1      /* ... and of d_model 64 (the reference CLI's default shape: 16 heads of 4) */
-#endif
-#ifndef GT_SEQ_PF32
-#define GT_SEQ_PF32 1      /* d_model 32, SPLIT kernels: every stage's global operands requested a stage ahead (round 6); 0: as before */
-#endif
 #define GT_SEQ_WAVES 8
 #define GT_SEQ_NT (GT_SEQ_WAVES * 64)
 #define GT_SEQ_NT_WG GT_SEQ_NT
@@ -146,7 +125,7 @@ __device__ __forceinline__ void seq_xchg_put(unsigned long long* slot, const f32
 #ifdef GT_EMU
     slot[j * GT_SEQ_NT + tid] = w;
 #else
-    if (!(GT_SEQ_ACCT & 4)) __hip_atomic_store(slot + j * GT_SEQ_NT + tid, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slot + j * GT_SEQ_NT + tid, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
   }
 }
@@ -166,15 +145,13 @@ __device__ __forceinline__ f32x4 seq_xchg_get(unsigned long long* slot, const in
       w[j] = __hip_atomic_load(slot + j * GT_SEQ_NT + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       ok = ok && (uint32_t)(w[j] >> 32) == GT_XTAG;
     }
-    if (__all(ok) || (GT_SEQ_ACCT & 4)) break;                 // (wave-uniform exit: the lanes of a wave leave together)
+    if (__all(ok)) break;                 // (wave-uniform exit: the lanes of a wave leave together)
     if (spins == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) spins = spin_max;       // (looked at only once the first poll failed)
     if (++spins > spin_max) { if ((tid & 63) == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
     __builtin_amdgcn_s_sleep(1);
   }
-  if (!(GT_SEQ_ACCT & 6)) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) __hip_atomic_store(slot + j * GT_SEQ_NT + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  for (int j = 0; j < 4; ++j) __hip_atomic_store(slot + j * GT_SEQ_NT + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
   return f32x4{gt_u2f((uint32_t)w[0]), gt_u2f((uint32_t)w[1]), gt_u2f((uint32_t)w[2]), gt_u2f((uint32_t)w[3])};
 }
@@ -704,7 +681,7 @@ __device__ __forceinline__ void seq_ln_fwd(ZFun zfun, float* sY, const int str, 
     SeqVec<CW>::st(sY + row * str + c0, y);
     if (gy != nullptr) {                                      // (wave-uniform; nullptr: another workgroup saves these rows -- QUAD)
       SeqVec<CW>::st(gy + o, y);
-      if (!(GT_SEQ_ACCT & 1)) SeqVec<CW>::st(gxhat + o, xh);
+      SeqVec<CW>::st(gxhat + o, xh);
     }
   }
   if (seg == 0 && gy != nullptr) grstd[row] = rs;
@@ -900,28 +877,12 @@ __device__ __forceinline__ void seq_attn_fwd(const SeqAttn& a, float* ctx, const
     for (int r = 0; r < 4; ++r) { if (!PAD || 16 * ct + l16 < hdr) orow[r * ldc + 16 * ct] = o[ct][r]; }
 }
 
-// The P values a wave's two backward roles read (its query tile's rows as 16-byte runs, its key tile's columns), for a caller that
-// requests them ahead of the attention backward: P was written a forward phase ago through another L2 and is the coldest operand of the
-// stage (SPLIT phases: requested before the state tiles, seq_attn_p_load).
-struct SeqPPre { float4 pv[2]; float pc[8]; };
-__device__ __forceinline__ SeqPPre seq_attn_p_load(const float* P, const int w, const int lane) {
-  SeqPPre r;
-  const int l16 = lane & 15, g = lane >> 4, i = 16 * w + l16;
-#pragma unroll
-  for (int tj = 0; tj < 2; ++tj) r.pv[tj] = *reinterpret_cast<const float4*>(P + (unsigned)(i * 32 + 16 * tj + 4 * g));
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) r.pc[4 * ti + q] = P[(unsigned)((16 * ti + 4 * g + q) * 32 + i)];
-  return r;
-}
 // Backward, two roles per wave with a workgroup barrier between them (gt_attn.h): role 1 (query tile w) -> dq in registers and
 // the row sums rd -> srd (32 floats of LDS per head); role 2 (key tile w) -> dk, dv in registers; after another barrier
 // seq_attn_bwd_store writes dq / dk / dv over q / k / v of the head (the dqkv tile IS the qkv tile).
 template <int HD, bool PAD>
 __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dctx, const int lddc, const SeqDropK& dk, const uint32_t key,
-                                              const int w, const int lane, float* srd, f32x4 (&dq_out)[HD / 16],
-                                              const bool have_p = false, const SeqPPre& pp = SeqPPre()) {
+                                              const int w, const int lane, float* srd, f32x4 (&dq_out)[HD / 16]) {
   constexpr int NQ = HD / 16;
   const int hdr = PAD ? a.hd : HD;
   const int l16 = lane & 15, g = lane >> 4;
@@ -945,7 +906,7 @@ __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dct
       for (int c = 0; c < 4; ++c) kb[ct][tj][c] = seq_ld1<PAD>(kcol + (16 * tj + c) * a.ldq + 16 * ct, 16 * ct + l16, hdr);
   float4 pv[2];
 #pragma unroll
-  for (int tj = 0; tj < 2; ++tj) { if (have_p) pv[tj] = pp.pv[tj]; else pv[tj] = *reinterpret_cast<const float4*>(a.P + (unsigned)(i * 32 + 16 * tj + 4 * g)); }
+  for (int tj = 0; tj < 2; ++tj) pv[tj] = *reinterpret_cast<const float4*>(a.P + (unsigned)(i * 32 + 16 * tj + 4 * g));
   f32x4 dt[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};           // dPd^T tiles [tj]
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -983,8 +944,7 @@ __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dct
 }
 template <int HD, bool PAD>
 __device__ __forceinline__ void seq_attn_bwd2(const SeqAttn& a, const float* dctx, const int lddc, const SeqDropK& dk, const uint32_t key,
-                                              const int w, const int lane, const float* srd, f32x4 (&dk_out)[HD / 16], f32x4 (&dv_out)[HD / 16],
-                                              const bool have_p = false, const SeqPPre& pp = SeqPPre()) {
+                                              const int w, const int lane, const float* srd, f32x4 (&dk_out)[HD / 16], f32x4 (&dv_out)[HD / 16]) {
   constexpr int NQ = HD / 16;
   const int hdr = PAD ? a.hd : HD;
   const int l16 = lane & 15, g = lane >> 4;
@@ -1016,7 +976,7 @@ __device__ __forceinline__ void seq_attn_bwd2(const SeqAttn& a, const float* dct
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = 16 * ti + 4 * g + r;
-      pvv[ti][r] = have_p ? pp.pc[4 * ti + r] : a.P[(unsigned)(i * 32 + j)];
+      pvv[ti][r] = a.P[(unsigned)(i * 32 + j)];
       rdv[ti][r] = srd[i];
     }
   f32x4 dd[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};           // dPd tiles [ti]
@@ -1293,23 +1253,14 @@ __device__ __forceinline__ void seq_attn_bwd_small_store(const SeqAttnSmallG<HD>
     for (int c = 0; c < HD; ++c) dst[c] = pb ? G.dvv.v[c] : G.dkk.v[c];
   }
 }
-#ifndef GT_SEQ_PPRE
-#define GT_SEQ_PPRE 0           /* 1: SPLIT backward phases request the MFMA attention backward's P values ahead of the state tiles (measured: slower, tools/rejected/README.md) */
-#endif
-#ifndef GT_SEQ_VATTN
-#define GT_SEQ_VATTN 1          /* 0: head_dim < 16 stays on the zero-padded MFMA form */
-#endif
 
 // SPLIT / QUAD kernels: which (sequence, part) a block is.  Blocks are dealt round-robin over the 8 XCDs (observed, speed only), so with
 // the plain order the 2 / 4 workgroups of one sequence -- which all load the same q / k / v tile at the start of a phase, and in QUAD
-// swap partial tiles -- sit on different L2s.  GT_SEQ_XCD_MAP: block x -> XCD x % 8, slot x / 8; the sequence's workgroups take
+// swap partial tiles -- sit on different L2s.  The map: block x -> XCD x % 8, slot x / 8; the sequence's workgroups take
 // consecutive slots of one XCD (its state crosses the fabric once per launch, not 2 / 4 times).  Any batch: nper x 8 x ceil(B / 8) is
 // not the grid size, so the map applies when B % 8 == 0 and the plain order otherwise.  Returns sequence * nper + part.
-#ifndef GT_SEQ_XCD_MAP
-#define GT_SEQ_XCD_MAP 1
-#endif
 __device__ __forceinline__ int seq_vblock(const int bid, const int nper, const int B) {
-  if (!GT_SEQ_XCD_MAP || (B & 7) != 0 || bid >= nper * B) return bid;
+  if ((B & 7) != 0 || bid >= nper * B) return bid;
   const int xcd = bid & 7, slot = bid >> 3;
   return ((slot / nper) * 8 + xcd) * nper + slot % nper;
 }
@@ -1374,8 +1325,8 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
   // operands -- weight fragments, bias / gamma / beta -- are requested one stage AHEAD, so that a phase pays the L2 round trip (1.8-2 k cycles)
   // once at its head instead of once per stage; the fragments are 8 ... 48 registers here (64 per stage at d_model 128, where the same was
   // measured slower in round 3).  Round 6.
-  constexpr bool PF32 = SPLIT && !QUAD && EXACT && (DP == 32 || (DP == 64 && GT_SEQ_PF64)) && GT_SEQ_PF32;
-  constexpr bool PFLN = PF32 || (SPLIT && EXACT && DP == 128 && GT_SEQ_PFLN128);     // the LayerNorm parameters alone: at d_model 128 too (24 registers per norm)
+  constexpr bool PF32 = SPLIT && !QUAD && EXACT && (DP == 32 || DP == 64);
+  constexpr bool PFLN = PF32;
   SeqB<NK> ipre = SeqB<NK>();                                 // the next layer's in-proj fragment + bias chunk (requested in layer_rest)
   float4 ipre_b = make_float4(0.f, 0.f, 0.f, 0.f);
   bool have_ipre = false;
@@ -1486,16 +1437,11 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
     if (save_qkv && sv0) seq_tile_out(wl + a.w0.qkv + r0 * 3 * d, sQ, SQ, 3 * d, tid, rb, NROW);
     SeqLnPre<CW> ln1p, ln2p;                                  // (PF32) the two norms' gamma / beta and the bias in front of them
     if constexpr (PFLN) seq_ln_pre<CW>(ln1p, pl + a.p0.out_b, pl + a.p0.n1w, pl + a.p0.n1b, tid);
-#ifndef GT_SEQ_NO_PRE2
     const bool preo = SPLIT && EXACT && (DP > 64 || PF32);    // the out-proj's fragment: in flight under the attention (which loads nothing)
     SeqB<NK> bopre = SeqB<NK>();
     if (preo) bopre = seq_tiles_first<NK>(kf_out, d, d, wave, lane);
-#else
-    const bool preo = false;
-    const SeqB<NK> bopre = SeqB<NK>();
-#endif
     bool vattn = false;
-    if constexpr (PAD && SPLIT && GT_SEQ_VATTN && (DP == 32 || DP == 64)) {        // (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
+    if constexpr (PAD && SPLIT && (DP == 32 || DP == 64)) {        // (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
       vattn = a.hd == DP / 16 && a.H == 16;                   // (16 heads of 2 at d_model 32, of 4 at d_model 64: the backward's P staging is written for 16 heads)
       if (vattn) {
         const uint32_t key = seq_key(dk, site0 + GT_SITE_ATTN);
@@ -1512,7 +1458,7 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
         if (h < a.H) {
           SeqAttn at;
           at.q = sQ + h * a.hd; at.k = at.q + d; at.v = at.q + 2 * d; at.ldq = SQ; at.hd = a.hd; at.scale = ascale;
-          at.pidx = (uint32_t)((b * a.H + h) * 1024); at.P = (sv0 && !(GT_SEQ_ACCT & 1)) ? wl + a.w0.P + (size_t)(b * a.H + h) * 1024 : nullptr;
+          at.pidx = (uint32_t)((b * a.H + h) * 1024); at.P = sv0 ? wl + a.w0.P + (size_t)(b * a.H + h) * 1024 : nullptr;
           seq_attn_fwd<HD, PAD>(at, sC + h * a.hd, SX, dk, key, HALF ? (rb >> 4) : (wave & 1), lane);
         }
       }
@@ -1526,7 +1472,7 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
     SeqTilesAll<NK, F1T> f1p;
     if constexpr (PF32) seq_tiles_all_load<NK, F1T>(f1p, kf_w1, d, F, pl + a.p0.b1, wave, lane);
     {
-      if (sv1 && !(GT_SEQ_ACCT & 1)) seq_tile_out(wl + a.w0.ctx + r0 * d, sC, SX, d, tid, rb, NROW);
+      if (sv1) seq_tile_out(wl + a.w0.ctx + r0 * d, sC, SX, d, tid, rb, NROW);
       if (DP <= 64 && !SPLIT) seq_mm_square(sC, SX, d, kf_out, sR, SRS, wave, lane);
       else
         seq_mm_tiles<NK, 1, EXACT, HALF>(sC + rb * SX, SX, d, kf_out, d, nullptr, wave, lane, [&](int n0, const f32x4& c0, const f32x4& c1, const float4&) {
@@ -1549,7 +1495,7 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
         } else SeqVec<CW>::ld(bi, bo + c0);
 #pragma unroll
         for (int e = 0; e < CW; ++e) z[e] = (z[e] + bi[e]) * seq_dmul(dk, key, idxd + (uint32_t)(row * d + c0 + e)) + xr[e];
-      }, sX1, SX, d, pl + a.p0.n1w, pl + a.p0.n1b, ((sv1 || fzl) && !(GT_SEQ_ACCT & 1)) ? wl + a.w0.x1 + r0 * d : nullptr, wl + a.w0.xhat1 + r0 * d, wl + a.w0.rstd1 + r0, tid, rb,
+      }, sX1, SX, d, pl + a.p0.n1w, pl + a.p0.n1b, (sv1 || fzl) ? wl + a.w0.x1 + r0 * d : nullptr, wl + a.w0.xhat1 + r0 * d, wl + a.w0.rstd1 + r0, tid, rb,
          PFLN ? &ln1p : nullptr);
     }
     GT_BARRIER();
@@ -1588,17 +1534,12 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
       else seq_mm_tiles<NK, F1T, EXACT, HALF>(sX1 + rb * SX, SX, d, kf_w1 + (size_t)(fc0 >> 4) * (d >> 4) * 256, fcn, pl + a.p0.b1 + fc0, wave, lane, ffn1_epi);
     }
     const int nkf = F >> 4, kq0 = QUAD ? cpart * (nkf >> 1) : 0;            // QUAD: this partner's k-steps of FFN2, kq0 .. kq0 + nkf / 2
-#ifndef GT_SEQ_NO_PRE
     const bool pre2 = QUAD ? ((nkf >> 1) & 7) == 0 : (SPLIT && seq_splitk_pre_ok(F, d));
     SeqB<8> b2pre = SeqB<8>();
     if (pre2) {                                                      // FFN2's first chunk: in flight across the barrier and the tile store
       if (QUAD) seq_b_load<8, true>(b2pre, kf_w2, nkf, wave, kq0, 8, lane);
       else b2pre = seq_splitk_first(kf_w2, F, d, wave, lane);
     }
-#else
-    const bool pre2 = false;
-    const SeqB<8> b2pre = SeqB<8>();
-#endif
     GT_BARRIER();
     GT_SUBSET(false);
     GT_STAMP(sb + 5);
@@ -1606,7 +1547,7 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
     if constexpr (QUAD) {
       // this partner's K half, one column tile per wave; its partial tile goes to the partner (and to sR part `cpart`), the partner's
       // arrives as part 1 - cpart: both sum part 0 + part 1, in that order, and continue on identical values
-      if (!(GT_SEQ_ACCT & 1)) seq_tile_out_cols(wl + a.w0.hact + r0 * F, F, sH, SH, fc0, fcn, tid, rb, NROW);
+      seq_tile_out_cols(wl + a.w0.hact + r0 * F, F, sH, SH, fc0, fcn, tid, rb, NROW);
       f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
       seq_mm_krange<true>(acc0, acc1, sH + rb * SH + l16 * SH + 4 * lg, SH, kf_w2, nkf, wave, kq0, kq0 + (nkf >> 1), lane, pre2, b2pre);
       GT_STAMP(300 + 4 * l);
@@ -1898,8 +1839,8 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     GT_STAMP(101);
   };
   // d_model 32, SPLIT (round 6, as in the forward): the chain's saved LayerNorm operands are requested at the phase's start
-  constexpr bool PFB = SPLIT && !QUAD && EXACT && (DP == 32 || (DP == 64 && GT_SEQ_PF64)) && GT_SEQ_PF32;
-  constexpr bool PFBLN = PFB || (SPLIT && !QUAD && EXACT && DP == 128 && GT_SEQ_PFLN128);    // the LayerNorm operands alone: at d_model 128 too (17 registers per norm)
+  constexpr bool PFB = SPLIT && !QUAD && EXACT && (DP == 32 || DP == 64);
+  constexpr bool PFBLN = PFB;
   SeqLnBwdPre<CW> lb2p, lb1p;
   bool have_lbp = false;                                     // (set by chain_prefetch, at the start of a phase > 0)
   constexpr int F2T = GT_SEQ_FMAX / (QUAD ? 256 : 128);      // FFN2 dgrad tiles per wave
@@ -1969,17 +1910,12 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     if constexpr (PFB) seq_mm_tiles_all<NK, F2T, HALF>(sC + rb * SX, SX, d, fcn, wave, lane, f2p, ffn2d_epi);
     else seq_mm_tiles<NK, F2T, EXACT, HALF>(sC + rb * SX, SX, d, kb_w2 + (size_t)(fc0 >> 4) * (d >> 4) * 256, fcn, nullptr, wave, lane, ffn2d_epi);
     const int nkf = F >> 4, kq0 = QUAD ? cpart * (nkf >> 1) : 0;            // QUAD: this partner's k-steps of the FFN1 dgrad
-#ifndef GT_SEQ_NO_PRE
     const bool pre1 = QUAD ? ((nkf >> 1) & 7) == 0 : (SPLIT && seq_splitk_pre_ok(F, d));
     SeqB<8> b1pre = SeqB<8>();
     if (pre1) {                                                      // FFN1 dgrad's first chunk: in flight across the barrier and the tile store
       if (QUAD) seq_b_load<8, true>(b1pre, kb_w1, nkf, wave, kq0, 8, lane);
       else b1pre = seq_splitk_first(kb_w1, F, d, wave, lane);
     }
-#else
-    const bool pre1 = false;
-    const SeqB<8> b1pre = SeqB<8>();
-#endif
     GT_BARRIER();
     GT_STAMP(sb + 1);
     SeqB<NK> bodpre = SeqB<NK>();                             // (PFB) the out-proj dgrad's fragment: in flight under the FFN1 dgrad and the norm1 backward
@@ -2065,21 +2001,15 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     }
   };
   SeqPRow prow = SeqPRow();                                  // head_dim-2 attention: this thread's P row, requested at the start of the phase
-  SeqPPre ppre = SeqPPre();                                  // MFMA attention: the wave's P values of the first round of heads, likewise
-  bool have_ppre = false;
   auto attn_inproj = [&](const int l) {
     const float* kb = ws + a.pack_b + (int64_t)l * a.kstride;
     float* wl = ws + (int64_t)l * a.wstride;
     float* tl = ws + (int64_t)l * a.tstride;
     const int sb = 102 + 10 * (a.L - 1 - l);
-#ifndef GT_SEQ_NO_PRE4
     const bool preq = SPLIT && seq_splitk_pre_ok(3 * d, d);
-#else
-    const bool preq = false;
-#endif
     SeqB<8> bqpre = SeqB<8>();
     bool vattn = false;
-    if constexpr (PAD && SPLIT && GT_SEQ_VATTN && (DP == 32 || DP == 64)) {        // (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
+    if constexpr (PAD && SPLIT && (DP == 32 || DP == 64)) {        // (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
       vattn = a.hd == DP / 16 && a.H == 16;
       if (vattn) {                                              // (sR is free here: H x 32 row sums)
         static_assert(G::FFN >= 16 * 1024 && G::RES >= 2 * 16 * 32 && !ALIAS, "head_dim-2 attention backward: P image in the FFN tile, row sums + keep bits in sR");
@@ -2091,9 +2021,7 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
         GT_BARRIER();
         GT_STAMP(400 + 4 * a.phase + 2);
         seq_attn_bwd_small_store<DP / 16>(G, sQ, SQ, d, a.H, rb, NROW, tid);
-#ifndef GT_SEQ_NO_PRE4
         if (preq) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
-#endif
       }
     }
     if (!vattn) {
@@ -2105,14 +2033,11 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
         at.q = sQ + h * a.hd; at.k = at.q + d; at.v = at.q + 2 * d; at.ldq = SQ; at.hd = a.hd; at.scale = ascale;
         at.pidx = (uint32_t)((b * a.H + h) * 1024); at.P = wl + a.w0.P + (size_t)(b * a.H + h) * 1024;
         f32x4 dq_out[HD / 16], dk_out[HD / 16], dv_out[HD / 16];
-        const bool hp = have_ppre && h4 == 0;                          // (the first round's P values were requested at the start of the phase)
-        if (active) seq_attn_bwd1<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dq_out, hp, ppre);
+        if (active) seq_attn_bwd1<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dq_out);
         GT_BARRIER();
-        if (active) seq_attn_bwd2<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dk_out, dv_out, hp, ppre);
-#ifndef GT_SEQ_NO_PRE4
+        if (active) seq_attn_bwd2<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dk_out, dv_out);
         // the in-proj dgrad's first chunk: in flight across the two barriers, the dq / dk / dv store and the dqkv tile's way to global
         if (preq && h4 + GT_SEQ_WAVES / 2 >= a.H) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
-#endif
         GT_BARRIER();
         if (active) seq_attn_bwd_store<HD, PAD>(sQ + h * a.hd, SQ, d, a.hd, wave & 1, lane, dq_out, dk_out, dv_out);
       }
@@ -2166,13 +2091,7 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     const int l = a.L - a.phase;
     GT_STAMP(160 + 2 * a.phase);
     const int64_t hand = (int64_t)a.B * 32 * d;                                                             // floats per hand-over buffer
-    bool vpre = false;
-    if constexpr (PAD && SPLIT && GT_SEQ_VATTN && (DP == 32 || DP == 64)) vpre = a.hd == DP / 16 && a.H == 16;
-    if (GT_SEQ_PPRE && !vpre && (wave >> 1) < a.H) {
-      ppre = seq_attn_p_load(ws + (int64_t)l * a.wstride + a.w0.P + (size_t)(b * a.H + (wave >> 1)) * 1024, wave & 1, lane);
-      have_ppre = true;
-    }
-    if constexpr (PAD && SPLIT && GT_SEQ_VATTN && (DP == 32 || DP == 64)) {
+    if constexpr (PAD && SPLIT && (DP == 32 || DP == 64)) {
       if (a.hd == DP / 16 && a.H == 16)
         prow = seq_attn_bwd_small_load(ws + (int64_t)l * a.wstride + a.w0.P + (size_t)(b * a.H) * 1024,
                                        reinterpret_cast<const uint32_t*>(ws + a.amask + (int64_t)l * a.amask_stride) + b * a.H * 32, tid);
@@ -2180,9 +2099,7 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     load_rows(sZ, SX, ws + a.dctx + ((a.phase - 1) & 1) * hand + r0 * d, d, 0, 32);                         // dctx of the whole sequence
     load_rows(sQ, SQ, ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * d, 3 * d, 0, 32);                   // its saved q / k / v
     load_rows(sDZ, SX, ws + (int64_t)l * a.tstride + a.t0.dzB + r0 * d, d, rb, NROW);                        // dz1 of layer l, own rows
-#if GT_SEQ_PFB_LN
     chain_prefetch(l);
-#endif
     GT_BARRIER();
     GT_STAMP(400 + 4 * a.phase);
     attn_inproj(l);
