@@ -110,8 +110,9 @@ size_t gt_workspace_bytes(const gt_config* cfg);
  * protocol.  A no-op for configs without such a region.  No counterpart in the reference (torch owns its activations there). */
 int gt_workspace_init(const gt_config* cfg, float* ws, gt_stream_t stream);
 /* Test/debug: locate a named saved activation inside the workspace (offset & count in floats).
- * names: "x0","a0","qkv","P","ctx","xhat1","rstd1","x1","hact","xhat2","rstd2","x2","memory",
- * "enc_xhat","dlogits" ... ; layer = global layer index (decoder layers follow the encoder's). */
+ * names: every public region of ws_layout (groove_hip.hip) by the name it is recorded under; "<name>16" for its bf16 shadow where it has one;
+ * "w16" / "w16t" (weight shadows of one encoder layer); "xchg_err".  layer = global layer index (decoder layers follow the
+ * encoder's), ignored for the regions a workspace has once. */
 int gt_ws_find(const gt_config* cfg, const char* name, int layer, int64_t* offset, int64_t* count);
 
 /* Replaces GrooveTransformer(Encoder).forward(src[, tgt]) (ref:train.py:195-215 via train_loop;

@@ -94,6 +94,78 @@ def test_workspace_lookup(lib):
         lib.ws_find(c, "kvx", 0)          # encoder layers have no cross-attention buffers
     with pytest.raises(_lib.GrooveLibError):
         lib.ws_find(c, "nope", 0)
+    try:
+        for level, cfg, answers in [
+                (2, _lib.make_config(3, 16, 128, 4, 512, 2), "seq_xchg"),                      # pair-exchange region
+                (2, _lib.make_config(2, 16, 32, 16, 64, 2), "amask"),
+                (2, c, "dmem"),                                                                # decoder regions
+                (1, _lib.make_config(128, 16, 256, 4, 512, 2, precision=1), "hact16"),         # operand shadows beside the fp32 tensors
+                (2, _lib.make_config(128, 16, 256, 4, 512, 2, precision=1), "hact16"),         # ... and the bf16-only tensors
+                (2, _lib.make_config(128, 16, 512, 8, 512, 2, precision=2), "qkv16")]:         # in-place qkv16 / dctx16
+            lib.cdll.gt_set_operand_shadows(level)
+            lib.ws_find(cfg, answers, 0)
+            _check_workspace_table(lib, cfg)
+            lib.cdll.gt_set_operand_shadows(0)
+            with pytest.raises(_lib.GrooveLibError):
+                lib.ws_find(cfg, "ctx16", 0)
+    finally:
+        lib.cdll.gt_set_operand_shadows(-1)
+
+
+WS_ONCE = "x0 a0 enc_xhat enc_rstd memory y0 b0 dec_final dlogits dmem dctx seq_xchg rowx amask pack_f pack_b".split()
+WS_PER_LAYER = ("qkv P ctx xhat1 rstd1 x1 qx kvx Px ctxx xhatx rstdx x2 hact xhat2 rstd2 xout "
+                "dzA dzAm dzB dzBm dzC dzCm dhid dqkv dqkvx").split()
+
+
+def _check_workspace_table(lib, cfg):
+    """every answer of gt_ws_find for one configuration: inside the workspace, aligned, and overlapping only where the layout says so"""
+    total = lib.workspace_floats(cfg)
+    nl = cfg.n_enc_layers + cfg.n_dec_layers
+    p2 = lib.cdll.gt_precision_in_force(ctypes.byref(cfg)) == 2
+
+    def find(name, layer):
+        try:
+            return lib.ws_find(cfg, name, layer)
+        except _lib.GrooveLibError:
+            return None
+
+    keys = [(n, 0) for n in WS_ONCE] + [(n, l) for n in WS_PER_LAYER for l in range(nl)]
+    fp32 = {k: find(*k) for k in keys}
+    fp32 = {k: v for k, v in fp32.items() if v is not None}
+    assert {"x0", "qkv", "hact", "dlogits", "dzA", "dqkv"} <= {k[0] for k in fp32}
+    for k, (off, cnt) in fp32.items():
+        assert 0 <= off and cnt > 0 and off + cnt <= total and off % 64 == 0, k
+    spans = sorted((off, off + cnt, k) for k, (off, cnt) in fp32.items())
+    for a, b in zip(spans, spans[1:]):
+        assert a[1] <= b[0], (a, b)
+    err = find("xchg_err", 0)
+    xchg = [fp32[(n, 0)] for n in ("seq_xchg", "rowx") if (n, 0) in fp32]
+    assert len(xchg) <= 1 and (err is None) == (not xchg)
+    if err:
+        assert err == (xchg[0][0], 2) and xchg[0][1] >= 2
+    n16 = 0
+    for k, (off, cnt) in fp32.items():
+        s = find(k[0] + "16", k[1])
+        if s is None:
+            continue
+        n16 += 1
+        assert s[1] == (cnt + 1) // 2 and 0 <= s[0] and s[0] + s[1] <= total, k
+        if p2 and k[0] in ("qkv", "dctx"):
+            assert s[0] == off, k                      # precision 2: the bf16 tensor lies at the head of its fp32 region
+        else:
+            assert all(s[0] + s[1] <= a or b <= s[0] for a, b, _ in spans), k
+    shadows = lib.cdll.gt_operand_shadow_level(ctypes.byref(cfg)) > 0
+    for l in range(nl):
+        for a, b in (("dzA16", "dzAm16"), ("dzB16", "dzBm16")):
+            assert find(a, l) == find(b, l)
+            assert (find(a, l) is not None) == (shadows and l < cfg.n_enc_layers), (a, l)
+    assert (n16 > 0) == shadows and (find("ctx16", 0) is not None) == shadows and (find("dzA16", 0) is not None) == shadows
+    assert (find("qkv16", 0) is not None) == p2 and (find("dctx16", 0) is not None) == p2
+    assert find("kvx", 0) is None and find("nope", 0) is None
+    if cfg.n_dec_layers == 0:
+        assert find("y0", 0) is None
+    else:
+        assert find("y0", 0) is not None and find("kvx", cfg.n_enc_layers) is not None
 
 
 def test_missing_library_fails_loudly(tmp_path):

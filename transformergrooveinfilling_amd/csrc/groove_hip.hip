@@ -7,6 +7,7 @@
 // (SURVEY.md 3.2-3.4): encoder layer torch:nn/modules/transformer.py:951-956,961-982; decoder layer
 // :1143-1153; MHA torch:nn/functional.py:5820-5850,6504-6642; module tree / parameter names from the
 // reference's demo checkpoint (ref:demo/transformer_run_171tyqit_Epoch_1.Model).
+#include <assert.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -181,7 +182,16 @@ struct LayerW {
   int64_t qx, kvx, Px, ctxx, xhatx, rstdx, x2;      // decoder cross-attention block
   int64_t hact, xhat2, rstd2, xout;                 // FFN block (xhat2/rstd2 = the layer's LAST norm)
 };
+// One entry per region ws_layout() hands out: the single description of the workspace that gt_ws_find, sh_act and only16 answer from.
+struct WRegion {
+  const char* name;         // what gt_ws_find answers to (nullptr: private)
+  int layer;                // global layer index (-1: one per workspace)
+  int64_t off, n;           // in floats
+  int64_t sh = -1;          // offset of its bf16 shadow (precision = 1, bf16_shadows()), for the activations whose producers write one
+  bool only = false;        // level 2: stored in bf16 alone (the fp32 region stays allocated, unwritten)
+};
 struct WLayout {
+  std::vector<WRegion> regions;
   int64_t x0, a0, enc_xhat, enc_rstd, memory, y0, b0, dec_xhat, dec_rstd, dec_final;
   std::vector<LayerW> layers;                        // encoder layers then decoder layers
   int64_t hvo_tmp, dlogits, loss_part, dctx, dmem, da0_dec, ln_part, ln_part_stride, total, stamps = 0;
@@ -190,10 +200,7 @@ struct WLayout {
   int64_t seq_xchg = -1, seq_xchg_n = 0;               // pair-exchange region of their four-workgroups-per-sequence (QUAD) forward
   int64_t rowx = -1, rowx_n = 0;                       // row exchange of the LayerNorm-fused 64x64-tile Linears (gt_gemm64.h; d_model 256 / 512)
   int64_t seq_amask = -1, seq_amask_stride = 0;        // dropout keep bits of P, one word per (layer, sequence, head, query): their head_dim-2 attention
-  // bf16 shadows (precision = 1, bf16_shadows()): fp32 tensor offset -> offset (in floats) of its bf16 copy, for the activations whose
-  // producers write one; w16 / w16t: the encoder layers' four matrices and their transposes, [in_w | out_w | w1 | w2] per layer
-  std::vector<std::pair<int64_t, int64_t>> sh;
-  std::vector<int64_t> sh_only;                        // level 2: fp32 offsets of the tensors stored in bf16 alone
+  // bf16 shadows (precision = 1, bf16_shadows()) of the encoder layers' four matrices and their transposes, [in_w | out_w | w1 | w2] per layer
   int64_t w16 = -1, w16t = -1, w16_stride = 0;
   int64_t kbits = -1, kbits_stride = 0;                // keep bits of the FFN activation, [layer][M / 32][F / 32][64] 16-bit words (gt_gemm32.h; round 6)
   int64_t wT = -1, wT_stride = 0;                      // precision = 1 without shadows: fp32 transposes of the encoder layers' matrices (dgrads as NT)
@@ -265,85 +272,94 @@ extern "C" int gt_precision_in_force(const gt_config* cfg) {
 static WLayout ws_layout(const gt_config& c) {
   WLayout W;
   int64_t cur = 0;
-  auto add = [&](int64_t n) { int64_t o = cur; cur += (n + 63) / 64 * 64; return o; };
-  const int64_t M = (int64_t)c.batch * 32, d = c.d_model, F = c.dim_ff, BH = (int64_t)c.batch * c.n_heads;
-  W.x0 = add(M * d); W.a0 = add(M * d);
   const int nl = c.n_enc_layers + c.n_dec_layers;
+  W.regions.reserve(40 + 34 * (size_t)nl);
+  auto add = [&](const char* name, int layer, int64_t n) { int64_t o = cur; cur += (n + 63) / 64 * 64; W.regions.push_back(WRegion{name, layer, o, n}); return o; };
+#define WS(s, f, layer, n) s.f = add(#f, layer, n)          // a public region: gt_ws_find answers to the field's name
+  const int64_t M = (int64_t)c.batch * 32, d = c.d_model, F = c.dim_ff, BH = (int64_t)c.batch * c.n_heads;
+  WS(W, x0, -1, M * d); WS(W, a0, -1, M * d);
   W.layers.resize(nl);
   for (int l = 0; l < nl; ++l) {
     LayerW& w = W.layers[l];
-    w.qkv = add(M * 3 * d); w.P = add(BH * 1024); w.ctx = add(M * d);
-    w.xhat1 = add(M * d); w.rstd1 = add(M); w.x1 = add(M * d);
+    WS(w, qkv, l, M * 3 * d); WS(w, P, l, BH * 1024); WS(w, ctx, l, M * d);
+    WS(w, xhat1, l, M * d); WS(w, rstd1, l, M); WS(w, x1, l, M * d);
     if (l >= c.n_enc_layers) {
-      w.qx = add(M * d); w.kvx = add(M * 2 * d); w.Px = add(BH * 1024); w.ctxx = add(M * d);
-      w.xhatx = add(M * d); w.rstdx = add(M); w.x2 = add(M * d);
+      WS(w, qx, l, M * d); WS(w, kvx, l, M * 2 * d); WS(w, Px, l, BH * 1024); WS(w, ctxx, l, M * d);
+      WS(w, xhatx, l, M * d); WS(w, rstdx, l, M); WS(w, x2, l, M * d);
     } else {
       w.qx = w.kvx = w.Px = w.ctxx = w.xhatx = w.rstdx = w.x2 = -1;
     }
-    w.hact = add(M * F); w.xhat2 = add(M * d); w.rstd2 = add(M); w.xout = add(M * d);
+    WS(w, hact, l, M * F); WS(w, xhat2, l, M * d); WS(w, rstd2, l, M); WS(w, xout, l, M * d);
   }
-  W.enc_xhat = add(M * d); W.enc_rstd = add(M); W.memory = add(M * d);
+  WS(W, enc_xhat, -1, M * d); WS(W, enc_rstd, -1, M); WS(W, memory, -1, M * d);
   if (c.n_dec_layers > 0) {
-    W.y0 = add(M * d); W.b0 = add(M * d); W.dec_xhat = add(M * d); W.dec_rstd = add(M); W.dec_final = add(M * d);
-    W.dmem = add(M * d); W.hvo_tmp = add(M * GT_TGT);
+    WS(W, y0, -1, M * d); WS(W, b0, -1, M * d); W.dec_xhat = add(nullptr, -1, M * d); W.dec_rstd = add(nullptr, -1, M); WS(W, dec_final, -1, M * d);
+    WS(W, dmem, -1, M * d); W.hvo_tmp = add(nullptr, -1, M * GT_TGT);
   } else {
     W.y0 = W.b0 = W.dec_xhat = W.dec_rstd = W.dec_final = W.dmem = W.hvo_tmp = -1;
   }
-  W.dlogits = add(M * GT_TGT);
-  W.loss_part = add(std::max<int64_t>(((M * GT_VOICES + 255) / 256) * 4, 8 * (int64_t)c.batch));   // loss_kernel's / the fused loss's workgroups x 4
+  WS(W, dlogits, -1, M * GT_TGT);
+  W.loss_part = add(nullptr, -1, std::max<int64_t>(((M * GT_VOICES + 255) / 256) * 4, 8 * (int64_t)c.batch));   // loss_kernel's / the fused loss's workgroups x 4
   // dgamma/dbeta partials: one [row_tiles][2][d] block per LayerNorm instance (2 per encoder layer, 3 per decoder
   // layer, the final norms)
   W.ln_part_stride = ((M + 7) / 8) * 2 * d;
-  W.ln_part = add(W.ln_part_stride * (2 * c.n_enc_layers + 3 * c.n_dec_layers + 2));
-  W.dctx = add(M * d);
-  W.da0_dec = c.n_dec_layers > 0 ? add(M * d) : -1;
+  W.ln_part = add(nullptr, -1, W.ln_part_stride * (2 * c.n_enc_layers + 3 * c.n_dec_layers + 2));
+  WS(W, dctx, -1, M * d);
+  W.da0_dec = c.n_dec_layers > 0 ? add(nullptr, -1, M * d) : -1;
   // Backward temporaries: one set per layer (the weight gradients read them at the end of backward)
   W.set.resize(nl);
-  for (size_t k = 0; k < W.set.size(); ++k) {
+  for (int k = 0; k < nl; ++k) {
     WLayout::TmpSet& t = W.set[k];
-    t.dzA = add(M * d); t.dzAm = add(M * d); t.dzB = add(M * d); t.dzBm = add(M * d);
-    t.dhid = add(M * F); t.dqkv = add(M * 3 * d);
-    if (c.n_dec_layers > 0) { t.dzC = add(M * d); t.dzCm = add(M * d); t.dqkvx = add(M * 3 * d); }
+    WS(t, dzA, k, M * d); WS(t, dzAm, k, M * d); WS(t, dzB, k, M * d); WS(t, dzBm, k, M * d);
+    WS(t, dhid, k, M * F); WS(t, dqkv, k, M * 3 * d);
+    if (c.n_dec_layers > 0) { WS(t, dzC, k, M * d); WS(t, dzCm, k, M * d); WS(t, dqkvx, k, M * 3 * d); }
     else { t.dzC = t.dzCm = t.dqkvx = -1; }
   }
   if (seq_supported(c)) {
     W.pack_stride = (int64_t)4 * d * d + (int64_t)2 * d * F;
-    W.pack_f = add(W.pack_stride * c.n_enc_layers); W.pack_b = add(W.pack_stride * c.n_enc_layers);
-    W.seq_dctx = add(2 * M * d);
-    if (d == 128) { W.seq_xchg_n = 2 * gt_seq_xchg_floats(c.batch); W.seq_xchg = add(W.seq_xchg_n); }    // (two regions: the forward's, and backward phase 0's when fused behind it)
-    if ((d == 32 || d == 64) && c.n_heads == 16) { W.seq_amask_stride = BH * 32; W.seq_amask = add(W.seq_amask_stride * c.n_enc_layers); }   // (behind everything else: no other offset moves)
+    WS(W, pack_f, -1, W.pack_stride * c.n_enc_layers); WS(W, pack_b, -1, W.pack_stride * c.n_enc_layers);
+    W.seq_dctx = add(nullptr, -1, 2 * M * d);
+    if (d == 128) { W.seq_xchg_n = 2 * gt_seq_xchg_floats(c.batch); WS(W, seq_xchg, -1, W.seq_xchg_n); }    // (two regions: the forward's, and backward phase 0's when fused behind it)
+    if ((d == 32 || d == 64) && c.n_heads == 16) { W.seq_amask_stride = BH * 32; W.seq_amask = add("amask", -1, W.seq_amask_stride * c.n_enc_layers); }   // (behind everything else: no other offset moves)
   }
-  if (!seq_supported(c) && (d == 256 || d == 512) && M % 64 == 0) { W.rowx_n = gt_rowx_floats(M, (int)d); W.rowx = add(W.rowx_n); }
+  if (!seq_supported(c) && (d == 256 || d == 512) && M % 64 == 0) { W.rowx_n = gt_rowx_floats(M, (int)d); WS(W, rowx, -1, W.rowx_n); }
   if (bf16_shadows(c)) {
-    auto sh = [&](int64_t off, int64_t n) { W.sh.emplace_back(off, add((n + 1) / 2)); };
+    // the bf16 shadow of the region at fp32 offset `off` (half its floats; `with`: the shadow it shares); gt_ws_find names it "<name>16"
+    auto sh = [&](int64_t off, bool only, int64_t with = -1) {
+      size_t i = 0;
+      while (i < W.regions.size() && (W.regions[i].off != off || W.regions[i].n <= 0)) ++i;
+      assert(i < W.regions.size() && "shadow of an offset ws_layout did not hand out");
+      const int64_t s = with >= 0 ? with : add(nullptr, -1, (W.regions[i].n + 1) / 2);
+      W.regions[i].sh = s; W.regions[i].only = only;
+      return s;
+    };
     const bool only = bf16_shadow_level() >= 2;
-    sh(W.x0, M * d);        // (round 5: the input layer's output -- layer 0's in-proj and its weight gradient then run with both operands in bf16 like every other layer's)
+    sh(W.x0, false);        // (round 5: the input layer's output -- layer 0's in-proj and its weight gradient then run with both operands in bf16 like every other layer's)
     for (int l = 0; l < c.n_enc_layers; ++l) {
       const LayerW& w = W.layers[l];
-      sh(w.ctx, M * d); sh(w.x1, M * d); sh(w.hact, M * F);
-      if (only) { W.sh_only.push_back(w.ctx); W.sh_only.push_back(w.hact); }
-      if (l + 1 < c.n_enc_layers) sh(w.xout, M * d);          // (the top layer's output comes from the two-norm pass, and feeds no big GEMM)
+      sh(w.ctx, only); sh(w.x1, false); sh(w.hact, only);
+      if (l + 1 < c.n_enc_layers) sh(w.xout, false);          // (the top layer's output comes from the two-norm pass, and feeds no big GEMM)
     }
-    for (size_t k = 0; k < W.set.size() && (int)k < c.n_enc_layers; ++k) {        // (one set per layer: the encoder layers' are the first L)
+    for (int k = 0; k < c.n_enc_layers; ++k) {        // (one set per layer: the encoder layers' are the first L)
       const WLayout::TmpSet& t = W.set[k];
       // dz / dzm share a shadow: the consumer takes the masked copy when there is dropout, else dz itself (tmp_set)
-      const int64_t a = add((M * d + 1) / 2), b = add((M * d + 1) / 2);
-      W.sh.emplace_back(t.dzA, a); W.sh.emplace_back(t.dzAm, a); W.sh.emplace_back(t.dzB, b); W.sh.emplace_back(t.dzBm, b);
-      sh(t.dhid, M * F); sh(t.dqkv, M * 3 * d);
       // (dzAm / dzBm exist as tensors of their own only with dropout; without it the operand is dz itself, which stays fp32)
-      if (only) { W.sh_only.push_back(t.dhid); W.sh_only.push_back(t.dqkv); W.sh_only.push_back(t.dzAm); W.sh_only.push_back(t.dzBm); }
+      const int64_t a = sh(t.dzA, false), b = sh(t.dzB, false);
+      sh(t.dzAm, only, a); sh(t.dzBm, only, b);
+      sh(t.dhid, only); sh(t.dqkv, only);
     }
     W.w16_stride = ((int64_t)4 * d * d + (int64_t)2 * d * F + 1) / 2;          // floats per layer
-    W.w16 = add(W.w16_stride * c.n_enc_layers); W.w16t = add(W.w16_stride * c.n_enc_layers);
+    W.w16 = add(nullptr, -1, W.w16_stride * c.n_enc_layers); W.w16t = add(nullptr, -1, W.w16_stride * c.n_enc_layers);
   } else if (bf16_wt(c)) {
     W.wT_stride = (int64_t)4 * d * d + (int64_t)2 * d * F;
-    W.wT = add(W.wT_stride * c.n_enc_layers);
+    W.wT = add(nullptr, -1, W.wT_stride * c.n_enc_layers);
   }
   // (behind everything else: no other offset moves.  One bit per element of hact: M F / 32 floats per layer)
-  if (!seq_supported(c) && F % 32 == 0) { W.kbits_stride = (M * F / 32 + 63) / 64 * 64; W.kbits = add(W.kbits_stride * nl); }
+  if (!seq_supported(c) && F % 32 == 0) { W.kbits_stride = (M * F / 32 + 63) / 64 * 64; W.kbits = add(nullptr, -1, W.kbits_stride * nl); }
 #ifdef GT_SEQ_STAMPS
-  W.stamps = add(2048 + 2 * 4 * 512);
+  WS(W, stamps, -1, 2048 + 2 * 4 * 512);
 #endif
+#undef WS
   W.total = cur;
   return W;
 }
@@ -369,66 +385,45 @@ extern "C" int gt_operand_shadow_level(const gt_config* cfg) {
   if (check_cfg(cfg)) return -1;
   return bf16_shadows(*cfg) ? bf16_shadow_level() : 0;
 }
+// The error word of whichever in-launch exchange region this shape has (offset in floats, -1: none).  rowx and seq_xchg are mutually
+// exclusive (rowx requires !seq_supported), so the precedence does not matter.
+static int64_t xchg_err_off(const WLayout& W) { return W.rowx >= 0 ? W.rowx : W.seq_xchg; }
+static unsigned* xchg_err(const WLayout& W, const float* ws) {
+  const int64_t eo = xchg_err_off(W);
+  return eo >= 0 ? reinterpret_cast<unsigned*>(const_cast<float*>(ws) + eo) : nullptr;
+}
+// Answers from the table of ws_layout: every public region by its name (per-layer ones at `layer`), "<name>16" = its bf16 shadow (offset in
+// floats, count = the floats it occupies: two bf16 per float).  Not regions of their own: "w16" / "w16t" (the weight shadows of encoder
+// layer `layer`), "xchg_err", and precision 2's "qkv16" / "dctx16" (bf16 tensors in the first half of the fp32 tensor's region).
 extern "C" int gt_ws_find(const gt_config* cfg, const char* name, int layer, int64_t* offset, int64_t* count) {
   if (check_cfg(cfg)) return -1;
   const gt_config& c = *cfg;
-  WLayout W = ws_layout(c);
-  const int64_t M = (int64_t)c.batch * 32, d = c.d_model, F = c.dim_ff, BH = (int64_t)c.batch * c.n_heads;
+  const WLayout W = ws_layout(c);
   std::string n(name);
-  int64_t off = -1, cnt = 0;
-  auto set = [&](int64_t o, int64_t k) { off = o; cnt = k; };
-  // "<tensor>16": the bf16 shadow of a tensor that has one (precision = 1, bf16_shadows()): offset in floats, count = floats it occupies
-  // (two bf16 per float); "w16" / "w16t": the weight shadows of encoder layer `layer`
   if (n == "w16" || n == "w16t") {
     if (W.w16 < 0 || layer < 0 || layer >= c.n_enc_layers) return gt_fail("gt_ws_find: no weight shadows for this configuration / layer");
     *offset = (n == "w16" ? W.w16 : W.w16t) + W.w16_stride * layer; *count = W.w16_stride;
     return 0;
   }
-  if ((n == "qkv16" || n == "dctx16") && p2(c)) {       // precision = 2: bf16 tensors in the first half of the fp32 tensor's buffer
-    if (n == "qkv16") { if (layer < 0 || layer >= c.n_enc_layers) return gt_fail("gt_ws_find: qkv16: layer %d is not an encoder layer", layer); *offset = W.layers[layer].qkv; *count = (M * 3 * d + 1) / 2; }
-    else { *offset = W.dctx; *count = (M * d + 1) / 2; }
-    return 0;
-  }
   const bool want16 = n.size() > 2 && n.compare(n.size() - 2, 2, "16") == 0;
   if (want16) n.resize(n.size() - 2);
-  if (n == "x0") set(W.x0, M * d); else if (n == "a0") set(W.a0, M * d);
-  else if (n == "enc_xhat") set(W.enc_xhat, M * d); else if (n == "enc_rstd") set(W.enc_rstd, M);
-  else if (n == "memory") set(W.memory, M * d); else if (n == "y0") set(W.y0, M * d); else if (n == "b0") set(W.b0, M * d);
-  else if (n == "dec_final") set(W.dec_final, M * d); else if (n == "dlogits") set(W.dlogits, M * GT_TGT);
-  else if (n == "dmem") set(W.dmem, M * d); else if (n == "dctx") set(W.dctx, M * d);
-  else if (n == "seq_xchg") set(W.seq_xchg, W.seq_xchg_n);
-  else if (n == "rowx") set(W.rowx, W.rowx_n);
-  else if (n == "xchg_err") { if (W.seq_xchg >= 0) set(W.seq_xchg, 2); else if (W.rowx >= 0) set(W.rowx, 2); }      // the error word of whichever in-launch exchange this shape has
-  else if (n == "amask" && W.seq_amask >= 0) set(W.seq_amask, W.seq_amask_stride * c.n_enc_layers);
-  else if (n == "pack_f" && W.pack_f >= 0) set(W.pack_f, W.pack_stride * c.n_enc_layers);
-  else if (n == "pack_b" && W.pack_b >= 0) set(W.pack_b, W.pack_stride * c.n_enc_layers);
-#ifdef GT_SEQ_STAMPS
-  else if (n == "stamps") set(W.stamps, 2048 + 2 * 4 * 512);
-#endif
-  else if (n == "dzA" || n == "dzAm" || n == "dzB" || n == "dzBm" || n == "dzC" || n == "dzCm" || n == "dhid" || n == "dqkv" || n == "dqkvx") {
-    // backward temporaries of one layer (kept per layer while the weight gradients are deferred to the end of backward)
-    if (layer < 0 || layer >= (int)W.layers.size()) return gt_fail("gt_ws_find: layer %d out of range", layer);
-    const WLayout::TmpSet& t = W.set[layer];
-    if (n == "dzA") set(t.dzA, M * d); else if (n == "dzAm") set(t.dzAm, M * d); else if (n == "dzB") set(t.dzB, M * d);
-    else if (n == "dzBm") set(t.dzBm, M * d); else if (n == "dzC") set(t.dzC, M * d); else if (n == "dzCm") set(t.dzCm, M * d);
-    else if (n == "dhid") set(t.dhid, M * F); else if (n == "dqkv") set(t.dqkv, M * 3 * d); else set(t.dqkvx, M * 3 * d);
-  } else {
-    if (layer < 0 || layer >= (int)W.layers.size()) return gt_fail("gt_ws_find: layer %d out of range", layer);
-    const LayerW& w = W.layers[layer];
-    if (n == "qkv") set(w.qkv, M * 3 * d); else if (n == "P") set(w.P, BH * 1024); else if (n == "ctx") set(w.ctx, M * d);
-    else if (n == "xhat1") set(w.xhat1, M * d); else if (n == "rstd1") set(w.rstd1, M); else if (n == "x1") set(w.x1, M * d);
-    else if (n == "qx") set(w.qx, M * d); else if (n == "kvx") set(w.kvx, M * 2 * d); else if (n == "Px") set(w.Px, BH * 1024);
-    else if (n == "ctxx") set(w.ctxx, M * d); else if (n == "xhatx") set(w.xhatx, M * d); else if (n == "x2") set(w.x2, M * d);
-    else if (n == "rstdx") set(w.rstdx, M);
-    else if (n == "hact") set(w.hact, M * F); else if (n == "xhat2") set(w.xhat2, M * d); else if (n == "rstd2") set(w.rstd2, M);
-    else if (n == "xout") set(w.xout, M * d);
+  const bool inplace16 = want16 && (n == "qkv" || n == "dctx") && p2(c);
+  if (inplace16 && n == "qkv" && (layer < 0 || layer >= c.n_enc_layers)) return gt_fail("gt_ws_find: qkv16: layer %d is not an encoder layer", layer);
+  int64_t off = -1, cnt = 0, sh = -1;
+  bool other_layer = false;
+  if (n == "xchg_err") { off = xchg_err_off(W); cnt = 2; }
+  else for (const WRegion& r : W.regions) {
+    if (r.name == nullptr || n != r.name) continue;
+    if (r.layer < 0 || r.layer == layer) { off = r.off; cnt = r.n; sh = r.sh; break; }
+    other_layer = true;
   }
+  if (off < 0 && other_layer && (layer < 0 || layer >= (int)W.layers.size())) return gt_fail("gt_ws_find: layer %d out of range", layer);
   if (off < 0) return gt_fail("gt_ws_find: unknown or absent buffer '%s'", name);
-  if (want16) {
-    for (const auto& e : W.sh) if (e.first == off) { *offset = e.second; *count = (cnt + 1) / 2; return 0; }
-    return gt_fail("gt_ws_find: '%s' has no bf16 shadow in this configuration", name);
+  if (want16 && !inplace16) {
+    if (sh < 0) return gt_fail("gt_ws_find: '%s' has no bf16 shadow in this configuration", name);
+    off = sh;
   }
-  *offset = off; *count = cnt;
+  *offset = off; *count = want16 ? (cnt + 1) / 2 : cnt;
   return 0;
 }
 
@@ -457,50 +452,46 @@ static float* ln_job(const Ctx& x, int64_t gamma_off, int nwg) {
   j.part = part; j.dgamma = x.grd + gamma_off; j.dbeta = x.grd + gamma_off + (x.d + 63) / 64 * 64; j.nwg = nwg;
   return part;
 }
-// bf16 shadow of a workspace tensor (nullptr: it has none) / of an encoder-layer weight matrix (transposed: the copy that turns a
-// dgrad into the NT form)
-static uint16_t* sh_act(const Ctx& x, const float* p) {
-  if (x.W.sh.empty() || p == nullptr) return nullptr;
+// the table entry of a workspace tensor that has a bf16 shadow (nullptr: it has none)
+static const WRegion* shadowed(const Ctx& x, const float* p) {
+  if (x.W.w16 < 0 || p == nullptr) return nullptr;            // (operand shadows and weight shadows come together: bf16_shadows())
   const int64_t off = p - x.ws;
-  for (const auto& e : x.W.sh) if (e.first == off) return reinterpret_cast<uint16_t*>(x.ws + e.second);
+  for (const WRegion& r : x.W.regions) if (r.sh >= 0 && r.off == off) return &r;
   return nullptr;
 }
-// fp32 transposed copy of an encoder-layer weight matrix (precision = 1 without shadows), or nullptr
-static const float* wT_of(const Ctx& x, const float* W) {
-  if (x.W.wT < 0) return nullptr;
-  const int64_t off = W - x.prm, d = x.d, F = x.F;
-  for (int l = 0; l < x.c.n_enc_layers; ++l) {
-    const LayerP& p = x.P.enc[l];
-    const float* base = x.ws + x.W.wT + x.W.wT_stride * l;
-    if (off == p.sa.in_w) return base;
-    if (off == p.sa.out_w) return base + 3 * d * d;
-    if (off == p.w1) return base + 4 * d * d;
-    if (off == p.w2) return base + 4 * d * d + d * F;
-  }
-  return nullptr;
+static uint16_t* sh_act(const Ctx& x, const float* p) {
+  const WRegion* r = shadowed(x, p);
+  return r ? reinterpret_cast<uint16_t*>(x.ws + r->sh) : nullptr;
 }
 // level 2: is this workspace tensor stored in bf16 alone (its fp32 region is not written)?
 static bool only16(const Ctx& x, const float* p) {
-  if (x.W.sh_only.empty() || p == nullptr) return false;
-  const int64_t off = p - x.ws;
-  for (const int64_t o : x.W.sh_only) if (o == off) return true;
-  return false;
+  const WRegion* r = shadowed(x, p);
+  return r && r->only;
 }
 // a consumer of a bf16-only tensor that could not take the bf16-source kernel would read an unwritten fp32 region: refuse loudly
 static thread_local const char* g_store_error = nullptr;
 static void need16(bool ok, const char* what) { if (!ok && g_store_error == nullptr) g_store_error = what; }
-static const uint16_t* sh_w(const Ctx& x, const float* W, bool transposed) {
-  if (x.W.w16 < 0) return nullptr;
+// where an encoder-layer weight matrix lies in a copy that keeps [in_w | out_w | w1 | w2] per layer, `stride` elements apart (-1: not one of them)
+static int64_t enc_w_slot(const Ctx& x, const float* W, int64_t stride) {
   const int64_t off = W - x.prm, d = x.d, F = x.F;
   for (int l = 0; l < x.c.n_enc_layers; ++l) {
     const LayerP& p = x.P.enc[l];
-    const uint16_t* base = reinterpret_cast<const uint16_t*>(x.ws + (transposed ? x.W.w16t : x.W.w16) + x.W.w16_stride * l);
-    if (off == p.sa.in_w) return base;
-    if (off == p.sa.out_w) return base + 3 * d * d;
-    if (off == p.w1) return base + 4 * d * d;
-    if (off == p.w2) return base + 4 * d * d + d * F;
+    if (off == p.sa.in_w) return stride * l;
+    if (off == p.sa.out_w) return stride * l + 3 * d * d;
+    if (off == p.w1) return stride * l + 4 * d * d;
+    if (off == p.w2) return stride * l + 4 * d * d + d * F;
   }
-  return nullptr;
+  return -1;
+}
+// fp32 transposed copy of an encoder-layer weight matrix (precision = 1 without shadows), or nullptr
+static const float* wT_of(const Ctx& x, const float* W) {
+  const int64_t slot = x.W.wT >= 0 ? enc_w_slot(x, W, x.W.wT_stride) : -1;
+  return slot >= 0 ? x.ws + x.W.wT + slot : nullptr;
+}
+// bf16 shadow of an encoder-layer weight matrix (transposed: the copy that turns a dgrad into the NT form), or nullptr
+static const uint16_t* sh_w(const Ctx& x, const float* W, bool transposed) {
+  const int64_t slot = x.W.w16 >= 0 ? enc_w_slot(x, W, 2 * x.W.w16_stride) : -1;
+  return slot >= 0 ? reinterpret_cast<const uint16_t*>(x.ws + (transposed ? x.W.w16t : x.W.w16)) + slot : nullptr;
 }
 struct Tmp { float *dzA, *dzAm, *dzB, *dzBm, *dzC, *dzCm, *dhid, *dqkv, *dqkvx; };
 static Tmp tmp_set(const Ctx& x, int gl) {
@@ -532,7 +523,6 @@ static GemmArgs mk_gemm(const float* A, int lda, const float* B, int ldb, float*
   g.bf16 = g_bf16;
   return g;
 }
-static bool p2(const gt_config& c);
 // y = x W^T + b  (forward "NT");  out16 (precision = 2): y stored in bf16 ALONE at out16 (row stride ldout), `out` not written
 static void linear_fwd(const Ctx& x, const float* in, int ldin, const float* W, const float* b, float* out, int ldout,
                        int N, int K, uint16_t* out16 = nullptr) {
@@ -1219,27 +1209,27 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
 
 static int encoder_fwd(const Ctx& x, const float* pe, const float* src) {
   float* ws = x.ws;
-  if (x.W.wT >= 0) {       // fp32 transposes of the encoder layers' weights: this step's dgrads run as NT products
+  // this step's copies of the encoder layers' weights: `sstride` elements of the copy per layer
+  const int tiles = (4 * x.d * x.d + 2 * x.d * x.F) / 1024;
+  const dim3 wgrid((unsigned)(tiles * x.c.n_enc_layers));
+  auto wcopy_args = [&](int64_t sstride) {
     const LayerP& p0 = x.P.enc[0];
     WShadowArgs a;
     a.prm = x.prm; a.w16 = nullptr; a.w16t = nullptr;
     a.in_w = p0.sa.in_w; a.out_w = p0.sa.out_w; a.w1 = p0.w1; a.w2 = p0.w2;
-    a.pstride = x.c.n_enc_layers > 1 ? x.P.enc[1].sa.in_w - p0.sa.in_w : 0; a.sstride = x.W.wT_stride;
+    a.pstride = x.c.n_enc_layers > 1 ? x.P.enc[1].sa.in_w - p0.sa.in_w : 0; a.sstride = sstride;
     a.d = x.d; a.F = x.F; a.L = x.c.n_enc_layers;
-    const int tiles = (4 * x.d * x.d + 2 * x.d * x.F) / 1024;
+    return a;
+  };
+  if (x.W.wT >= 0) {       // fp32 transposes: this step's dgrads run as NT products
     gt_prof_tag("weight_shadow", 0.0, 8.0 * x.c.n_enc_layers * tiles * 1024.0);
-    gt_launch(weight_transpose_kernel, dim3((unsigned)(tiles * x.c.n_enc_layers)), dim3(256), x.s, a, ws + x.W.wT);
+    gt_launch(weight_transpose_kernel, wgrid, dim3(256), x.s, wcopy_args(x.W.wT_stride), ws + x.W.wT);
   }
-  if (x.W.w16 >= 0) {      // bf16 shadows of the encoder layers' weights (and their transposes) for this step's Linears and dgrads
-    const LayerP& p0 = x.P.enc[0];
-    WShadowArgs a;
-    a.prm = x.prm; a.w16 = reinterpret_cast<uint16_t*>(ws + x.W.w16); a.w16t = reinterpret_cast<uint16_t*>(ws + x.W.w16t);
-    a.in_w = p0.sa.in_w; a.out_w = p0.sa.out_w; a.w1 = p0.w1; a.w2 = p0.w2;
-    a.pstride = x.c.n_enc_layers > 1 ? x.P.enc[1].sa.in_w - p0.sa.in_w : 0; a.sstride = 2 * x.W.w16_stride;
-    a.d = x.d; a.F = x.F; a.L = x.c.n_enc_layers;
-    const int tiles = (4 * x.d * x.d + 2 * x.d * x.F) / 1024;
+  if (x.W.w16 >= 0) {      // bf16 shadows (and their transposes) for this step's Linears and dgrads
+    WShadowArgs a = wcopy_args(2 * x.W.w16_stride);
+    a.w16 = reinterpret_cast<uint16_t*>(ws + x.W.w16); a.w16t = reinterpret_cast<uint16_t*>(ws + x.W.w16t);
     gt_prof_tag("weight_shadow", 0.0, 8.0 * x.c.n_enc_layers * tiles * 1024.0);
-    gt_launch(weight_shadow_kernel, dim3((unsigned)(tiles * x.c.n_enc_layers)), dim3(256), x.s, a);
+    gt_launch(weight_shadow_kernel, wgrid, dim3(256), x.s, a);
   }
   input_layer_fwd(x, src, x.c.src_dim, x.P.in_w, x.P.in_b, pe, ws + x.W.a0, ws + x.W.x0, GT_SITE_PE_ENC);
   const float* cur = ws + x.W.x0;
@@ -1438,7 +1428,6 @@ static void input_layer_bwd(const Ctx& x, const LayerP& first, const Tmp& t, con
 // "everything from tensor X to the end" is final early: X = the decoder input layer of an encoder-decoder model, else
 // encoder layer L/2.  split_layer: first encoder layer of the upper bucket (enc-dec: L, i.e. no encoder layer).
 struct GradSplit { int nb; int split_layer; int64_t off[2], cnt[2]; };
-static bool seq_ride(const gt_config& c);
 static GradSplit grad_split(const gt_config& c, const PLayout& P) {
   GradSplit g;
   g.nb = 1; g.split_layer = 0; g.off[0] = 0; g.cnt[0] = P.total; g.off[1] = g.cnt[1] = 0;
@@ -1487,7 +1476,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
   x.wb = &wbatch;
   LnJobs lnjobs;
   lnjobs.n = 0; lnjobs.N = d; lnjobs.bump = nullptr;
-  { const int64_t eo = x.W.rowx >= 0 ? x.W.rowx : x.W.seq_xchg; lnjobs.err = eo >= 0 ? reinterpret_cast<unsigned*>(ws + eo) : nullptr; }
+  lnjobs.err = xchg_err(x.W, ws);
   x.ln = &lnjobs;
   const int top = L + Ld - 1;                       // global index of the last layer
   const GradSplit split = grad_split(*cfg, P);
@@ -1767,9 +1756,7 @@ extern "C" int gt_optimizer_step_ws(const gt_config* cfg, int algo, float* param
   if (check_cfg(cfg)) return -1;
   PLayout P = param_layout(*cfg);
   if (!use_seq(*cfg) || !zero_grads || !ws) {
-    const WLayout W0 = ws ? ws_layout(*cfg) : WLayout();
-    const int64_t eo = W0.rowx >= 0 ? W0.rowx : W0.seq_xchg;                                                  // (the error word of whichever exchange region the shape has)
-    unsigned* err = (ws && eo >= 0) ? reinterpret_cast<unsigned*>(ws + eo) : nullptr;
+    unsigned* err = ws ? xchg_err(ws_layout(*cfg), ws) : nullptr;
     return optimizer_step_impl(algo, params, grads, m, v, P.total, state, zero_grads, stream, 0, err, 1);
   }
   if (!params || !grads || !state) return gt_fail("gt_optimizer_step: params / grads / state must not be NULL");
@@ -1780,7 +1767,7 @@ extern "C" int gt_optimizer_step_ws(const gt_config* cfg, int algo, float* param
   const SeqArgs a = mk_seq(x, nullptr, nullptr, nullptr);
   gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
   gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 0, (hipStream_t)stream);
-  gt_launch(step_inc_kernel, dim3(1), dim3(64), (hipStream_t)stream, state, x.W.seq_xchg >= 0 ? reinterpret_cast<unsigned*>(ws + x.W.seq_xchg) : (unsigned*)nullptr,
+  gt_launch(step_inc_kernel, dim3(1), dim3(64), (hipStream_t)stream, state, xchg_err(x.W, ws),
             (const float*)(grads + P.total - 1));
   return launch_status("gt_optimizer_step_ws");
 }
@@ -1848,9 +1835,7 @@ extern "C" int gt_train_step(const gt_config* cfg, int algo, float* params, floa
       gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 1, (hipStream_t)stream);
       return launch_status("gt_train_step");
     }
-    const int64_t eo = W.rowx >= 0 ? W.rowx : W.seq_xchg;
-    if (optimizer_step_impl(algo, params, grads, m, v, P.total, state, 1, stream, 1,
-                            eo >= 0 ? reinterpret_cast<unsigned*>(ws + eo) : nullptr, 1)) return -1;
+    if (optimizer_step_impl(algo, params, grads, m, v, P.total, state, 1, stream, 1, xchg_err(W, ws), 1)) return -1;
   }
   return 0;
 }
@@ -1863,11 +1848,10 @@ __global__ __launch_bounds__(64) void dp_guard_kernel(float* guard, const unsign
 extern "C" int gt_dp_guard(const gt_config* cfg, float* grads, const float* ws, gt_stream_t stream) {
   if (check_cfg(cfg)) return -1;
   if (!grads || !ws) return gt_fail("gt_dp_guard: grads / ws must not be NULL");
-  const WLayout W = ws_layout(*cfg);
-  const int64_t eo = W.rowx >= 0 ? W.rowx : W.seq_xchg;
-  if (eo < 0) return 0;
+  const unsigned* err = xchg_err(ws_layout(*cfg), ws);
+  if (!err) return 0;
   const PLayout P = param_layout(*cfg);
-  gt_launch(dp_guard_kernel, dim3(1), dim3(64), (hipStream_t)stream, grads + P.total - 1, reinterpret_cast<const unsigned*>(ws + eo));
+  gt_launch(dp_guard_kernel, dim3(1), dim3(64), (hipStream_t)stream, grads + P.total - 1, err);
   return launch_status("gt_dp_guard");
 }
 
