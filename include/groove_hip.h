@@ -261,6 +261,31 @@ int gt_dp_guard(const gt_config* cfg, float* grads, const float* ws, gt_stream_t
 int64_t gt_clip_grad_norm_scratch_floats(const gt_config* cfg);
 int gt_clip_grad_norm(const gt_config* cfg, float* grads, const gt_step_state* state, float max_norm,
                       float* out, float* scratch, gt_stream_t stream);
+/* The optimizer knobs beyond the defaults -- torch.optim.SGD(momentum, nesterov, weight_decay; dampening 0), torch.optim.Adam(weight_decay)
+ * and torch.optim.AdamW(weight_decay) -- as ONE launch enqueued just BEFORE the update (gt_optimizer_step / gt_optimizer_step_ws; with
+ * gt_train_step: skip_update = 1, [gt_clip_grad_norm,] this call, the update).  It rewrites the gradient buffer (AdamW: the parameter buffer)
+ * over [0, n_floats - 1) so that the unchanged update applies the optimizer torch would; the guard element n_floats - 1 is never read as
+ * data and never written.  hp is HOST memory, read when the call is enqueued (a captured graph keeps the values); lr and grad_scale are
+ * read on the device from *state.  With gs = grad_scale, per element in fp32:
+ *   algo 0:                g = grads * gs; [g += weight_decay * params;] [b = momentum * mbuf + g, mbuf = b, g = nesterov ? g + momentum * b : b;]
+ *                          grads = g / gs  (exact for gs a power of two).  A zeroed mbuf reproduces torch's first step (buf = grad).
+ *   algo 1, decoupled 0:   grads = (grads * gs + weight_decay * params) / gs          (Adam's L2 weight_decay)
+ *   algo 1, decoupled 1:   params *= 1 - lr * weight_decay, gradients untouched       (AdamW; the Adam update reads the decayed parameter)
+ * Rejected before any launch: momentum with algo 1, decoupled with algo 0, nesterov without momentum, a negative weight_decay or momentum,
+ * momentum with mbuf == NULL.  weight_decay == 0 and momentum == 0: returns 0 and launches nothing.
+ * The buffers are the WHOLE flat buffers of the configuration (mbuf: n_floats floats, zeroed once; NULL without momentum).  Their alignment
+ * gaps stay zero.  ws != NULL: the fail-safe predicate of gt_optimizer_step_ws -- with the "xchg_err" word set or a non-zero guard element
+ * the pass writes NOTHING (no momentum advances, no parameter decays; the update that follows skips too).  ws == NULL: plain, like
+ * gt_optimizer_step.  Pass ws to both calls or to neither.  Never touches state->step / opt_step.  No atomics: bitwise reproducible,
+ * identical on every data-parallel rank.  No host sync; capturable. */
+typedef struct gt_opt_hparams {
+  float weight_decay;     /* >= 0 */
+  float momentum;         /* >= 0; algo 0 only */
+  int32_t nesterov;       /* needs momentum > 0 */
+  int32_t decoupled;      /* algo 1 only: 1 = AdamW, 0 = L2 (added to the gradient) */
+} gt_opt_hparams;
+int gt_optimizer_prepare(const gt_config* cfg, int algo, float* params, float* grads, float* mbuf, const float* ws,
+                         const gt_step_state* state, const gt_opt_hparams* hp, gt_stream_t stream);
 /* LayerNorm inside the producing Linear / dgrad (csrc/gt_gemm64.h, round 5): at d_model 256 / 512, where the 64 x 64-tile kernels apply and
  * the whole grid is resident at once (a GPU's share of a data-parallel batch: 2048 tokens), the N / 64 workgroups of a row block exchange
  * their row partials inside the launch (tagged 8-byte granules, agent-scope stores / polling loads; "rowx" workspace region, zeroed once

@@ -48,7 +48,7 @@ def build_parser():
     p.add_argument("--config", default=None, help="yaml config file; if given the hyper-parameter flags are ignored")
     p.add_argument("--experiment", default=None)
     p.add_argument("--encoder_only", default=1, type=int)
-    p.add_argument("--optimizer_algorithm", default="sgd", type=str)
+    p.add_argument("--optimizer_algorithm", default="sgd", type=str, help="sgd | adam (ref:train.py:40-42) | adamw")
     p.add_argument("--d_model", default=64, type=int)
     p.add_argument("--n_heads", default=16, type=int)
     p.add_argument("--dropout", default=0.2, type=float)
@@ -79,6 +79,11 @@ def build_parser():
     p.add_argument("--max_grad_norm", default=None, type=float,
                    help="clip the gradients to this global 2-norm every step (torch.nn.utils.clip_grad_norm_; inf: only log the norm as "
                         "train/grad_norm).  Also the YAML key max_grad_norm; the reference does not clip (default: off)")
+    p.add_argument("--momentum", default=0.0, type=float, help="SGD momentum (torch.optim.SGD, dampening 0).  Also the YAML key momentum; the reference trains without (default 0)")
+    p.add_argument("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum > 0).  Also the YAML key nesterov")
+    p.add_argument("--weight_decay", default=None, type=float,
+                   help="weight decay: L2 for sgd / adam (added to the gradient), decoupled for adamw.  Also the YAML key weight_decay; "
+                        "default: torch's (0; 1e-2 for adamw)")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible weight gradients (gt_set_deterministic: no token split in the weight-gradient kernels; +9-30 %% step time)")
     return p
@@ -103,12 +108,21 @@ def load_hyperparameters(args):
     # gradient clipping: the YAML key, else --max_grad_norm (the reference's YAMLs lack the key: off, as there)
     mgn = hp.get("max_grad_norm", args.max_grad_norm)
     hp["max_grad_norm"] = None if mgn is None else float(mgn)
+    # the optimizer's extras, the same way: YAML key, else the flag (the reference's YAMLs lack the keys: plain SGD / Adam, as there)
+    hp["momentum"] = float(hp.get("momentum", args.momentum) or 0.0)
+    hp["nesterov"] = bool(hp.get("nesterov", args.nesterov))
+    wd = hp.get("weight_decay", args.weight_decay)
+    hp["weight_decay"] = None if wd is None else float(wd)
     return hp
 
 
 def model_params(hp, device):
     """params dict of ref:train.py:115-143."""
     enc_only = bool(hp["encoder_only"])
+    # (the optimizer's extras only where set: a reference YAML gives exactly the reference's three training keys)
+    extras = {k: hp[k] for k in ("momentum", "nesterov") if hp.get(k)}
+    if hp.get("weight_decay") is not None:     # (an explicit 0 counts: adamw's default is torch's 1e-2)
+        extras["weight_decay"] = hp["weight_decay"]
     return {"model": {"experiment": hp["experiment"], "encoder_only": hp["encoder_only"], "optimizer": hp["optimizer_algorithm"],
                       "d_model": hp["d_model"], "n_heads": hp["n_heads"], "dim_feedforward": hp["dim_feedforward"],
                       "dropout": hp["dropout"], "num_encoder_layers": hp["num_encoder_decoder_layers"],
@@ -116,7 +130,7 @@ def model_params(hp, device):
                       "embedding_size_src": 27 if hp["experiment"] == "InfillingClosedHH_Symbolic" else 16,
                       "embedding_size_tgt": 27, "device": device},
             "training": {"learning_rate": hp["learning_rate"], "batch_size": hp["batch_size"],
-                         "hit_loss_penalty": hp["hit_loss_penalty"]},
+                         "hit_loss_penalty": hp["hit_loss_penalty"], **extras},
             "load_model": hp["load_model"]}
 
 

@@ -35,6 +35,13 @@ class GtStepState(ctypes.Structure):
 
 STEP_STATE_BYTES = ctypes.sizeof(GtStepState)   # 48
 
+
+class GtOptHparams(ctypes.Structure):
+    """gt_opt_hparams: host memory, read when gt_optimizer_prepare is enqueued"""
+    _fields_ = [("weight_decay", ctypes.c_float), ("momentum", ctypes.c_float), ("nesterov", ctypes.c_int32),
+                ("decoupled", ctypes.c_int32)]
+
+
 _vp, _cfgp = ctypes.c_void_p, ctypes.POINTER(GtConfig)
 _SIGS = {
     "gt_last_error": (ctypes.c_char_p, []),
@@ -78,6 +85,8 @@ _SIGS = {
     "gt_clip_grad_norm_scratch_floats": (ctypes.c_int64, [_cfgp]),
     # cfg, grads, state, max_norm, out, scratch, stream
     "gt_clip_grad_norm": (ctypes.c_int, [_cfgp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
+    # cfg, algo, params, grads, mbuf, ws, state, hp, stream
+    "gt_optimizer_prepare": (ctypes.c_int, [_cfgp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(GtOptHparams), _vp]),
     "gt_set_ln_exchange": (ctypes.c_int, [ctypes.c_int]),
     "gt_debug_occupy_cus": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp]),
     "gt_set_operand_shadows": (ctypes.c_int, [ctypes.c_int]),

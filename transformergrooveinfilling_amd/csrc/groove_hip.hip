@@ -87,7 +87,7 @@ extern "C" int gt_profile_report(char* buf, size_t buf_len, int max_rows) {
 #endif
   return n;
 }
-extern "C" int gt_version(void) { return 3; }
+extern "C" int gt_version(void) { return 4; }
 
 static int check_cfg(const gt_config* c) {
   if (!c) return gt_fail("gt_config is NULL");
@@ -1875,6 +1875,33 @@ extern "C" int gt_clip_grad_norm(const gt_config* cfg, float* grads, const gt_st
   gt_prof_tag("clip_scale", 1.0 * (n - 1), 8.0 * (n - 1));
   gt_launch(grad_scale_kernel, dim3((unsigned)nwg), dim3(256), s, grads, n, (const float*)out);
   return launch_status("gt_clip_grad_norm");
+}
+
+// ------------------------------------------------------------------------------------ optimizer extras: the pass before the update
+// SGD momentum / Nesterov / weight decay, Adam's L2 weight decay and AdamW as ONE launch (gt_misc.h opt_prepare_kernel) that rewrites the
+// gradient buffer (AdamW: the parameter buffer) in front of the unchanged update.  The hyper-parameters are read from the host struct here
+// and baked into the launch, as gt_clip_grad_norm's max_norm is; lr and grad_scale are read on the device.  ws != NULL: the predicate of
+// gt_optimizer_step_ws (error word, guard element); ws == NULL: plain, like gt_optimizer_step.  Never touches step / opt_step.
+extern "C" int gt_optimizer_prepare(const gt_config* cfg, int algo, float* params, float* grads, float* mbuf, const float* ws,
+                                    const gt_step_state* state, const gt_opt_hparams* hp, gt_stream_t stream) {
+  if (check_cfg(cfg)) return -1;
+  if (!params || !grads || !state || !hp) return gt_fail("gt_optimizer_prepare: params / grads / state / hp must not be NULL");
+  if (algo != 0 && algo != 1) return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
+  if (!(hp->weight_decay >= 0.f) || !(hp->momentum >= 0.f))
+    return gt_fail("gt_optimizer_prepare: weight_decay %g / momentum %g must be >= 0", (double)hp->weight_decay, (double)hp->momentum);
+  if (algo == 1 && hp->momentum != 0.f) return gt_fail("gt_optimizer_prepare: momentum belongs to sgd (algo 0), not to adam");
+  if (algo == 0 && hp->decoupled) return gt_fail("gt_optimizer_prepare: decoupled weight decay (AdamW) belongs to adam (algo 1), not to sgd");
+  if (hp->nesterov && hp->momentum == 0.f) return gt_fail("gt_optimizer_prepare: nesterov needs a momentum > 0");
+  if (hp->momentum != 0.f && !mbuf) return gt_fail("gt_optimizer_prepare: momentum needs mbuf");
+  if (hp->weight_decay == 0.f && hp->momentum == 0.f) return 0;      // nothing to do: no launch
+  const int64_t n = param_layout(*cfg).total, nwg = gt_prep_wgs(n);
+  if (nwg <= 0) return 0;
+  const OptPrep h{hp->weight_decay, hp->momentum, hp->nesterov ? 1 : 0, algo == 0 ? 0 : (hp->decoupled ? 2 : 1)};
+  const unsigned* err = ws ? xchg_err(ws_layout(*cfg), ws) : nullptr;
+  const double bytes = h.mode == 2 ? 8.0 : 8.0 + (h.wd != 0.f ? 4.0 : 0.0) + (h.mom != 0.f ? 8.0 : 0.0);
+  gt_prof_tag("opt_prepare", (h.mode == 2 ? 1.0 : 6.0) * (n - 1), bytes * (n - 1));
+  gt_launch(opt_prepare_kernel, dim3((unsigned)nwg), dim3(256), (hipStream_t)stream, params, grads, mbuf, n, state, h, err, ws ? 1 : 0);
+  return launch_status("gt_optimizer_prepare");
 }
 
 // ------------------------------------------------------------------------------------ test aid: hold CUs

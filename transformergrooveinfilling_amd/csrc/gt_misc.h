@@ -671,6 +671,87 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(float* __restrict__ g, 
   }
 }
 
+// ---- optimizer extras as a pass BEFORE the update: SGD momentum / Nesterov / weight decay, Adam's L2 weight decay, AdamW ---------------
+// One launch over [0, n - 1) of the flat buffers (the guard element n - 1 is never read as data and never written), which rewrites the
+// gradient buffer -- AdamW: the parameter buffer -- so that the unchanged sgd_kernel / adam_kernel / seq_update_pack_kernel apply the
+// optimizer torch would.  With gs = grad_scale, per element in fp32:
+//   mode 0 (torch.optim.SGD, dampening 0): g = grads * gs [+ wd * p];  momentum: b = mom * mbuf + g, mbuf = b, g = nesterov ? g + mom * b : b;
+//          grads = g / gs  (the update subtracts lr * gs * grads; exact for gs a power of two).  A zero mbuf gives torch's first step.
+//   mode 1 (torch.optim.Adam's L2 weight_decay): grads = (grads * gs + wd * p) / gs
+//   mode 2 (AdamW): p *= 1 - lr * wd, gradients untouched (the Adam update that follows reads the decayed parameter).
+// Fail-safe, as sgd_kernel's: with the error word set (err; nullptr: the caller has none) or, for a caller that holds the workspace (guard),
+// a non-zero guard element, NOTHING is written -- no momentum advances, no parameter decays; the update that follows skips as well.
+// CONTRACT: the alignment gaps between tensors stay zero in all three buffers.  The parameter buffer's gaps are zero (allocated zeroed;
+// every update adds k * 0 there), the gradient's are (backward writes tensors only), mbuf starts zeroed: wd * 0, mom * 0 + 0 and 0 * f keep
+// them so.  Workgroup w owns the fixed chunk [w * GT_PREP_CHUNK, (w + 1) * GT_PREP_CHUNK); no atomics, no cross-workgroup state: bitwise
+// reproducible and the same on every data-parallel rank.  All loads of a chunk are issued before its arithmetic (up to 12 float4 a thread).
+#define GT_PREP_CHUNK 4096             // floats per workgroup: 256 threads x 4 float4 (x up to three buffers in flight)
+static inline int64_t gt_prep_wgs(int64_t n) { return (n - 1 + GT_PREP_CHUNK - 1) / GT_PREP_CHUNK; }
+
+struct OptPrep { float wd, mom; int nesterov, mode; };
+
+__device__ __forceinline__ float opt_prep_elem(const OptPrep h, const float gs, float g, const float p, float& b) {
+  g *= gs;
+  if (h.wd != 0.f) g += h.wd * p;
+  if (h.mom != 0.f) {
+    b = h.mom * b + g;
+    g = h.nesterov ? g + h.mom * b : b;
+  }
+  return g / gs;
+}
+
+__global__ __launch_bounds__(256) void opt_prepare_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ mb, int64_t n,
+                                                          const gt_step_state* st, const OptPrep h, const unsigned* err, int guard) {
+  if ((err != nullptr && *err != 0u) || (guard && g[n - 1] != 0.f)) return;
+  const int64_t nu = n - 1;
+  const int64_t i0 = (int64_t)blockIdx.x * GT_PREP_CHUNK + threadIdx.x * 4;
+  constexpr int K = GT_PREP_CHUNK / 1024;
+  const bool full = (int64_t)(blockIdx.x + 1) * GT_PREP_CHUNK <= nu;
+  if (h.mode == 2) {                                       // AdamW: decoupled decay of the parameters
+    const float f = 1.0f - st->lr * h.wd;
+    if (full) {
+      float4 pv[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) pv[k] = *reinterpret_cast<const float4*>(p + i0 + k * 1024);
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        *reinterpret_cast<float4*>(p + i0 + k * 1024) = make_float4(pv[k].x * f, pv[k].y * f, pv[k].z * f, pv[k].w * f);
+      return;
+    }
+    for (int k = 0; k < K; ++k)
+      for (int64_t j = i0 + k * 1024; j < i0 + k * 1024 + 4 && j < nu; ++j) p[j] *= f;
+    return;
+  }
+  const float gs = st->grad_scale;
+  const bool use_p = h.wd != 0.f, use_b = h.mom != 0.f;
+  if (full) {
+    float4 gv[K], pv[K], bv[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      gv[k] = *reinterpret_cast<const float4*>(g + i0 + k * 1024);
+      pv[k] = use_p ? *reinterpret_cast<const float4*>(p + i0 + k * 1024) : make_float4(0.f, 0.f, 0.f, 0.f);
+      bv[k] = use_b ? *reinterpret_cast<const float4*>(mb + i0 + k * 1024) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float4 o;
+      o.x = opt_prep_elem(h, gs, gv[k].x, pv[k].x, bv[k].x);
+      o.y = opt_prep_elem(h, gs, gv[k].y, pv[k].y, bv[k].y);
+      o.z = opt_prep_elem(h, gs, gv[k].z, pv[k].z, bv[k].z);
+      o.w = opt_prep_elem(h, gs, gv[k].w, pv[k].w, bv[k].w);
+      *reinterpret_cast<float4*>(g + i0 + k * 1024) = o;
+      if (use_b) *reinterpret_cast<float4*>(mb + i0 + k * 1024) = bv[k];
+    }
+    return;
+  }
+  for (int k = 0; k < K; ++k)                              // the last chunk: stops in front of the guard element
+    for (int64_t j = i0 + k * 1024; j < i0 + k * 1024 + 4 && j < nu; ++j) {
+      float b = use_b ? mb[j] : 0.f;
+      g[j] = opt_prep_elem(h, gs, g[j], use_p ? p[j] : 0.f, b);
+      if (use_b) mb[j] = b;
+    }
+}
+
 // teacher forcing: tgt_in[b,t] = y[b,t-1], row 0 = zeros
 __global__ __launch_bounds__(256) void shift_right_kernel(const float* __restrict__ y, float* __restrict__ tgt, int n) {
   const int e = blockIdx.x * 256 + threadIdx.x;

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, layout
 
-ALGO = {"sgd": 0, "adam": 1}
+ALGO = {"sgd": 0, "adam": 1, "adamw": 1}      # "adamw": adam with DECOUPLED weight decay (StepEngine.decoupled)
 OVERLAP_MIN_BYTES = 16 << 20
 EAGER_MAX_LAUNCHES = 24                # use_graph="auto": steps of at most this many launches are enqueued directly, not replayed
 PREDICT_CHUNK = 512                    # floor of the sequences per gt_predict call
@@ -90,7 +90,7 @@ class StepEngine:
     def __init__(self, d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_layers=0,
                  dropout=0.0, embedding_size_src=16, batch_size=None, optimizer="sgd", learning_rate=0.05,
                  hit_loss_penalty=1.0, seed=0, device="cuda", world_size=1, use_graph="auto", lib=None, precision="fp32",
-                 max_grad_norm=None):
+                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False):
         self.device = torch.device(device)
         # The only way onto host memory is an EXPLICITLY passed library object (tests hand in the host-emulator build of
         # the same kernel sources to cover the multi-rank step sequence over gloo); nothing in the package does that.
@@ -122,6 +122,12 @@ class StepEngine:
         # step is the fused one, unchanged.  Settable at any time; the norm and the coefficient of a clipped step land in stats[6] / stats[7]
         self.max_grad_norm = max_grad_norm
         self._clip_scratch = None      # gt_clip_grad_norm's scratch (zeroed once; every call leaves it zero)
+        # the optimizer's knobs beyond the defaults: torch.optim.SGD(momentum, nesterov, weight_decay; dampening 0), torch.optim.Adam(weight_decay)
+        # (L2: added to the gradient) and, with optimizer="adamw", torch.optim.AdamW's decoupled decay.  All off (the default): the step is
+        # the fused one, unchanged.  Settable at any time, like max_grad_norm; see _opt_extras
+        self.weight_decay, self.momentum, self.nesterov = weight_decay, momentum, nesterov
+        self.decoupled = optimizer.lower() == "adamw"
+        self.mbuf = None               # SGD's momentum buffers, flat like the gradients (zeros when momentum is first non-zero: torch's first step)
         self.names = layout.param_names(d_model, dim_feedforward, embedding_size_src, num_encoder_layers, num_decoder_layers)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.params = torch.zeros(self.total, **f32)
@@ -289,14 +295,44 @@ class StepEngine:
                       ctypes.c_float(self.penalty), _ptr(s.hvo), _ptr(s.stats), _ptr(s.tgt), _ptr(s.ws),
                       _ptr(self.state), int(flags), self.stream)
 
+    # ---- the optimizer's extras (momentum / Nesterov / weight decay / AdamW): one launch in front of the update ------------------------------
+    # gt_optimizer_prepare rewrites the gradient buffer (AdamW: the parameter buffer) so that the unchanged update kernels apply the optimizer
+    # torch would.  It sits at the head of enqueue_update, so every split sequence gets it: the data-parallel recipes (after the last
+    # all-reduce and the clip), _watched_step, the module API's opt.step().  The single-process fused step takes the split sequence while
+    # any extra is on (_split_step).
+    def _opt_extras(self):
+        """(weight_decay, momentum, nesterov, decoupled) of the pass, validated, or None while everything is off (no launch, the fused step)"""
+        wd, mom, nest = float(self.weight_decay), float(self.momentum), bool(self.nesterov)
+        if not wd >= 0.0 or not mom >= 0.0:
+            raise ValueError("weight_decay and momentum must be >= 0, got %r / %r" % (self.weight_decay, self.momentum))
+        if mom != 0.0 and self.algo != 0:
+            raise ValueError("momentum belongs to the sgd optimizer (adam has its own moments), got momentum=%r" % (self.momentum,))
+        if nest and mom == 0.0:
+            raise ValueError("nesterov needs a momentum > 0 (torch.optim.SGD: 'Nesterov momentum requires a momentum and zero dampening')")
+        if self.decoupled and self.algo != 1:
+            raise ValueError("decoupled weight decay (optimizer='adamw') belongs to the adam update")
+        if wd == 0.0 and mom == 0.0:
+            return None
+        if mom != 0.0 and self.mbuf is None:
+            self.mbuf = torch.zeros_like(self.params)
+        return (wd, mom, nest, bool(self.decoupled))
+
+    def _enqueue_prepare(self, cfg, ws, hp):
+        self.lib.call("gt_optimizer_prepare", ctypes.byref(cfg), self.algo, _ptr(self.params), _ptr(self.grads), _ptr(self.mbuf), _ptr(ws),
+                      _ptr(self.state), ctypes.byref(_lib.GtOptHparams(hp[0], hp[1], int(hp[2]), int(hp[3]))), self.stream)
+
     def enqueue_update(self, zero_grads=True, slot=None):
-        """Fused update over the flat buffers.  zero_grads=True also clears the consumed gradients (fused step path);
-        the torch.optim-style front keeps them until zero_grad() like torch does.  slot: the step's slot -- its workspace then
-        receives the next step's weight copies (gt_optimizer_step_ws)."""
+        """Fused update over the flat buffers, behind the optimizer's extras (_opt_extras) when any is on.  zero_grads=True also clears
+        the consumed gradients (fused step path); the torch.optim-style front keeps them until zero_grad() like torch does -- what it keeps
+        is then the gradient as the extras left it.  slot: the step's slot -- its workspace then receives the next step's weight copies
+        (gt_optimizer_step_ws)."""
         self._pepoch += 1
         if slot is None:
             slot = self._bwd_slot          # module API (loss.backward(); opt.step()): the slot backward() ran on
+        hp = self._opt_extras()
         if slot is not None and slot.B in self._slots and self._slots[slot.B] is slot:
+            if hp is not None:             # (with the workspace, like the update: the pass refuses whatever the update refuses)
+                self._enqueue_prepare(slot.cfg, slot.ws, hp)
             # with the configuration and its workspace at hand the update honours the exchange region's error word and the data-parallel
             # guard element (gt_optimizer_step_ws: a timed-out exchange never reaches the parameters, Adam's t does not advance)
             if zero_grads and self.fold_pack:
@@ -304,11 +340,14 @@ class StepEngine:
             self.lib.call("gt_optimizer_step_ws", ctypes.byref(slot.cfg), self.algo, _ptr(self.params), _ptr(self.grads), _ptr(self.m),
                           _ptr(self.v), _ptr(slot.ws), _ptr(self.state), int(zero_grads), self.stream)
             return
+        if hp is not None:
+            self._enqueue_prepare(self._probe_cfg, None, hp)
         self.lib.call("gt_optimizer_step", self.algo, _ptr(self.params), _ptr(self.grads), _ptr(self.m), _ptr(self.v),
                       ctypes.c_int64(self.total), _ptr(self.state), int(zero_grads), self.stream)
 
     # ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) -------------------------------------------------
-    # A clipped step is the split sequence the data-parallel step already uses: forward + loss + backward (skip_update = 1), the two
+    # A clipped step (like one with the optimizer's extras on: _split_step) is the split sequence the data-parallel step already uses:
+    # forward + loss + backward (skip_update = 1), the two
     # launches of gt_clip_grad_norm (norm into stats[6], coefficient into stats[7]; the loss kernels zero both, the 8-float stats copy
     # carries them), then the update.  Single process it is one captured graph per max_norm.  The exchanges' fail-safe stays with the
     # update: clipping never touches the guard element, and gt_optimizer_step_ws still refuses a step whose error word is set.
@@ -330,18 +369,34 @@ class StepEngine:
     def _clip_step(self, s, max_norm):
         self._enqueue_clip(s.cfg, ctypes.c_void_p(s.stats.data_ptr() + 6 * 4), max_norm)     # -> stats[6] norm, stats[7] coefficient
 
-    def _clipped_step(self, s, max_norm):
+    def _split_step(self, s, max_norm):
+        """The single-process step as the split sequence: backward, [clip,] [the optimizer's extras +] update (max_norm None: no clip)"""
         self._enqueue_step(s, 1)
-        self._clip_step(s, max_norm)
+        if max_norm is not None:
+            self._clip_step(s, max_norm)
         self.enqueue_update(slot=s)
 
-    def _graph_for_clip(self, s):
-        """graph_for for the clipped step: use_graph="auto" counts the split step's launches (the fused step's + 1: update and step_inc
-        apart) plus the two of the clip"""
+    def _graph_for_split(self, s, clip=True, extras=False):
+        """graph_for for the split step: use_graph="auto" counts its launches (the fused step's + 1: update and step_inc apart) plus the
+        two of the clip and the one of the optimizer's extras"""
         if self.use_graph == "auto":
             n = self.lib.cdll.gt_step_launches(ctypes.byref(s.cfg))
-            return not (0 < n and n + 3 <= EAGER_MAX_LAUNCHES)
+            return not (0 < n and n + 1 + 2 * bool(clip) + bool(extras) <= EAGER_MAX_LAUNCHES)
         return bool(self.use_graph)
+
+    _graph_for_clip = _graph_for_split         # (the clipped step without extras)
+
+    def _split_recipe(self, s, name, tail=()):
+        """(graph key, decision, max_norm) of the split step in force, or None while neither clipping nor an extra is on.  The key
+        carries everything baked into the launches: max_norm and the hyper-parameter tuple."""
+        if self.max_grad_norm is None and not (self.weight_decay or self.momentum or self.nesterov):
+            return None                            # (the default, on every step of the fused path: decided without more ado)
+        hp = self._opt_extras()
+        if self.max_grad_norm is None and hp is None:
+            return None
+        mn = None if self.max_grad_norm is None else self._clip_norm(self.max_grad_norm)
+        key = (name + ("_clip" if mn is not None else "_prep"), self.algo, self.penalty) + (() if mn is None else (mn,)) + (hp or ()) + tail
+        return key, self._graph_for_split(s, mn is not None, hp is not None), mn
 
     def clip_grad_norm_(self, max_norm):
         """torch.nn.utils.clip_grad_norm_(parameters, max_norm) over the flat gradient buffer (module API: between loss.backward() and
@@ -375,7 +430,7 @@ class StepEngine:
             side = torch.cuda.Stream(self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             snap = (self.params.clone(), self.state.clone(), None if self.m is None else (self.m.clone(), self.v.clone()),
-                    self.grads.clone())
+                    self.grads.clone(), None if self.mbuf is None else self.mbuf.clone())
             self._capturing = True                # (no GT_STEP_PACKS_CURRENT in a recorded recipe: a replay would pass it blindly)
 
             def restore():
@@ -384,6 +439,8 @@ class StepEngine:
                 self.params.copy_(snap[0]); self.state.copy_(snap[1])
                 if snap[2] is not None:
                     self.m.copy_(snap[2][0]); self.v.copy_(snap[2][1])
+                if snap[4] is not None:
+                    self.mbuf.copy_(snap[4])
                 self.grads.copy_(snap[3])         # zeros for a whole-step graph (gt_train_step's precondition), else what the first half left
             try:
                 try:
@@ -463,7 +520,8 @@ class StepEngine:
         if modes is not None:
             cand = [c for c in cand if c in modes]
         name = lambda c: ("buckets" if c[0] else "plain") + ("_graph" if c[1] else "_eager")
-        snap = (self.params.clone(), self.state.clone(), None if self.m is None else (self.m.clone(), self.v.clone()))
+        snap = (self.params.clone(), self.state.clone(), None if self.m is None else (self.m.clone(), self.v.clone()),
+                None if self.mbuf is None else self.mbuf.clone())
         sync = (lambda: None) if self.on_host else (lambda: torch.cuda.synchronize(self.device))
         table, errors = {}, {}
         for c in cand:
@@ -501,6 +559,8 @@ class StepEngine:
             self.params.copy_(snap[0]); self.state.copy_(snap[1]); self.grads.zero_()
             if snap[2] is not None:
                 self.m.copy_(snap[2][0]); self.v.copy_(snap[2][1])
+            if snap[3] is not None:
+                self.mbuf.copy_(snap[3])
             self._pepoch += 1                      # (the parameters were rewritten: every slot's weight copies are stale)
             for t_ in self._slots.values():        # (graphs of this candidate go: the next one -- and the run -- record their own)
                 t_.graphs.clear(); t_.keep.clear()
@@ -533,15 +593,16 @@ class StepEngine:
             s.x.copy_(x, non_blocking=True)
         if y is not None:
             s.y.copy_(y, non_blocking=True)
-        if self.world_size == 1 and not self.force_dp and on_grads is not None:
+        single = self.world_size == 1 and not self.force_dp
+        split = self._split_recipe(s, "fused") if single and on_grads is None else None
+        if single and on_grads is not None:
             self._watched_step(s, on_grads)
-        elif self.world_size == 1 and not self.force_dp and self.max_grad_norm is not None:
-            mn = self._clip_norm(self.max_grad_norm)
-            use = self._graph_for_clip(s)
+        elif split is not None:
+            key, use, mn = split
             if use:
                 self._note_fused_step(s)          # (the replay updates the parameters and writes the next step's weight copies)
-            self._replay(s, ("fused_clip", self.algo, self.penalty, mn), lambda: self._clipped_step(s, mn), graph=use)
-        elif self.world_size == 1 and not self.force_dp:
+            self._replay(s, key, lambda: self._split_step(s, mn), graph=use)
+        elif single:
             if self.graph_for(s):
                 self._note_fused_step(s)          # (a replay updates the parameters without running _enqueue_step)
             self._replay(s, ("fused", self.algo, self.penalty), lambda: self._enqueue_step(s, 0))
@@ -559,6 +620,7 @@ class StepEngine:
             self._ar_issued = 0
             guard = self._guard_fn(s)
             mn = None if self.max_grad_norm is None else self._clip_norm(self.max_grad_norm)     # clipping: after the last all-reduce, before the update
+            hp = self._opt_extras()               # the optimizer's extras: at the head of enqueue_update, so after the clip (validated here, before any launch)
             if self.dp_graph and on_grads is None and not self.on_host:
                 # ONE enqueue per step: forward + backward, the all-reduce(s) and the update captured in one hipGraph -- the collectives are
                 # nodes of the graph (RCCL enqueues on its own stream: fork / join edges), nothing returns to Python between the halves
@@ -578,7 +640,7 @@ class StepEngine:
                     if mn is not None:
                         self._clip_step(s, mn)
                     self.enqueue_update(slot=s)
-                key = ("dp_whole", self.algo, self.penalty, len(buckets)) + (() if mn is None else (mn,))
+                key = ("dp_whole", self.algo, self.penalty, len(buckets)) + (() if mn is None else (mn,)) + (hp or ())
                 self._dp_whole(s, key, whole)
                 self.poll_exchange(s)
                 return s.stats
@@ -625,13 +687,12 @@ class StepEngine:
             gather()
             return self.train_step(B=s.B, on_grads=on_grads)
         if self.world_size == 1 and not self.force_dp:
-            if self.max_grad_norm is not None:
-                mn = self._clip_norm(self.max_grad_norm)
-                gkey = ("fused_idx_clip", self.algo, self.penalty, mn) + key
-                use = self._graph_for_clip(s)
+            split = self._split_recipe(s, "fused_idx", key)
+            if split is not None:
+                gkey, use, mn = split
                 if use:
                     self._note_fused_step(s)
-                self._replay(s, gkey, lambda: (gather(), self._clipped_step(s, mn)), graph=use)
+                self._replay(s, gkey, lambda: (gather(), self._split_step(s, mn)), graph=use)
             else:
                 gkey = ("fused_idx", self.algo, self.penalty) + key
                 if self.graph_for(s):

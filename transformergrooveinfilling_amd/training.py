@@ -28,50 +28,101 @@ def _wandb_active():
 # ------------------------------------------------------------------------------------------------ optimizers
 class _FusedMixin:
     """torch.optim-compatible front of the fused flat update (one kernel over all tensors).  Keeps torch's
-    state_dict format: SGD -> per-param {'momentum_buffer': None} (ckpt); Adam -> step/exp_avg/exp_avg_sq."""
+    state_dict format: SGD -> per-param {'momentum_buffer': None | tensor} (ckpt); Adam / AdamW -> step/exp_avg/exp_avg_sq.
 
-    def _bind(self, engine, algo):
+    Hyper-parameters: param_groups[0] is the source of truth (one group: the flat buffers have one set).  lr, momentum, nesterov and
+    weight_decay are pushed to the engine by every step() and at the head of train_loop's fast path, so editing param_groups between
+    steps takes effect.  dampening != 0, amsgrad and maximize have no kernel and raise ValueError.
+
+    ONE deviation from torch: momentum, Nesterov and weight decay run as a pass over the gradient buffer in front of the update, so after
+    step() the .grad views hold the TRANSFORMED gradient (weight decay added, the momentum step) until zero_grad(); torch leaves .grad as
+    backward wrote it.  (AdamW decays the parameters and leaves the gradients alone.)"""
+
+    def _bind(self, engine, algo, decoupled=False):
         self.engine = engine
-        self._algo = algo
-        engine.algo = algo
+        self._algo, self._decoupled = algo, decoupled
+        engine.algo, engine.decoupled = algo, decoupled
         engine._fused_opt = True           # (the update kernel honours the exchange error word: engine.backward need not zero gradients)
         self._lr_on_device = None
+        self._push_lr()
 
     def zero_grad(self, set_to_none=False):
         self.engine.grads.zero_()
 
     def _push_lr(self):
-        lr = float(self.param_groups[0]["lr"])
+        """lr into the device step state (when it changed) and the other hyper-parameters of param_groups[0] into the engine"""
+        g = self.param_groups[0]
+        for k in ("dampening", "amsgrad", "maximize"):
+            if g.get(k):
+                raise ValueError("%s: %s=%r is not supported by the fused update" % (type(self).__name__, k, g[k]))
+        lr = float(g["lr"])
         if lr != self._lr_on_device:
             self.engine.set_state(lr=lr)
             self._lr_on_device = lr
+        eng = self.engine
+        eng.algo, eng.decoupled = self._algo, self._decoupled
+        eng.weight_decay, eng.momentum, eng.nesterov = float(g.get("weight_decay", 0.0)), float(g.get("momentum", 0.0)), bool(g.get("nesterov", False))
+        eng._opt_extras()                  # (validates; allocates the momentum buffers when momentum is first non-zero)
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._push_lr()
-        self.engine.algo = self._algo
         self.engine.enqueue_update(zero_grads=False)
         return loss
 
 
 class GrooveSGD(_FusedMixin, torch.optim.SGD):
-    """torch.optim.SGD(lr, momentum=0) semantics (ckpt: optimizer param_groups) on the fused kernel."""
+    """torch.optim.SGD(lr, momentum, nesterov, weight_decay) semantics with dampening 0 (ckpt: optimizer param_groups; the reference's
+    momentum=0 is the default) on the fused kernels.  state[p]["momentum_buffer"] is a view into the engine's flat momentum buffer while
+    momentum is non-zero (zeros before the first step: torch's buf = grad), else None as in the demo checkpoint.  See _FusedMixin for the one
+    deviation from torch (.grad after step())."""
 
-    def __init__(self, params, lr, engine):
-        torch.optim.SGD.__init__(self, params, lr=lr)
+    def __init__(self, params, lr, engine, momentum=0, nesterov=False, weight_decay=0, dampening=0, maximize=False):
+        if dampening != 0 or maximize:
+            raise ValueError("GrooveSGD: dampening and maximize are not supported by the fused update")
+        torch.optim.SGD.__init__(self, params, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=weight_decay)
         self._bind(engine, 0)
-        for p in self.param_groups[0]["params"]:
-            self.state[p]["momentum_buffer"] = None
+
+    def _push_lr(self):
+        _FusedMixin._push_lr(self)
+        eng = self.engine
+        ps = self.param_groups[0]["params"]
+        cur = self.state[ps[0]].get("momentum_buffer", False)       # (False: not set yet)
+        if eng.momentum == 0.0:
+            if cur is not None:
+                for p in ps:
+                    self.state[p]["momentum_buffer"] = None
+        elif cur is None or cur is False:
+            mb = eng.views(eng.mbuf)
+            by_ptr = {t.data_ptr(): n for n, t in eng.views().items()}
+            for p in ps:
+                self.state[p]["momentum_buffer"] = mb[by_ptr[p.data_ptr()]]
+
+    def load_state_dict(self, sd):
+        """lr from the checkpoint; momentum / nesterov / weight_decay stay this run's.  Stored momentum buffers are copied into the engine's
+        flat buffer; None (a momentum-free run's or a reference-written checkpoint) resumes a momentum run from zeros."""
+        self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]
+        self._push_lr()
+        for i, p in enumerate(self.param_groups[0]["params"]):
+            buf = (sd["state"].get(i) or {}).get("momentum_buffer")
+            mine = self.state[p]["momentum_buffer"]
+            if mine is not None:
+                mine.zero_() if buf is None else mine.copy_(buf)
 
 
 class GrooveAdam(_FusedMixin, torch.optim.Adam):
-    """torch.optim.Adam(lr) defaults; exp_avg / exp_avg_sq are views into the engine's flat moment buffers."""
+    """torch.optim.Adam(lr, weight_decay) (L2: the decay is added to the gradient); exp_avg / exp_avg_sq are views into the engine's flat
+    moment buffers.  See _FusedMixin for the one deviation from torch (.grad after step())."""
+    _base, _decoupled_decay = torch.optim.Adam, False
 
-    def __init__(self, params, lr, engine):
-        torch.optim.Adam.__init__(self, params, lr=lr)
-        self._bind(engine, 1)
+    def __init__(self, params, lr, engine, weight_decay=None, amsgrad=False, maximize=False):
+        if amsgrad or maximize:
+            raise ValueError("%s: amsgrad and maximize are not supported by the fused update" % type(self).__name__)
+        kw = {} if weight_decay is None else {"weight_decay": weight_decay}          # (None: torch's default -- 0 for Adam, 1e-2 for AdamW)
+        self._base.__init__(self, params, lr=lr, **kw)
         engine.ensure_adam()
+        self._bind(engine, 1, self._decoupled_decay)
         m, v = engine.views(engine.m), engine.views(engine.v)
         by_ptr = {t.data_ptr(): n for n, t in engine.views().items()}
         for p in self.param_groups[0]["params"]:
@@ -98,6 +149,11 @@ class GrooveAdam(_FusedMixin, torch.optim.Adam):
                 self.state[p]["step"] = torch.as_tensor(float(st["step"]))
                 steps = int(st["step"])
         self.engine.set_state(opt_step=steps)
+
+
+class GrooveAdamW(GrooveAdam, torch.optim.AdamW):
+    """torch.optim.AdamW(lr, weight_decay=1e-2): the parameters are decayed by 1 - lr * weight_decay in front of the Adam update."""
+    _base, _decoupled_decay = torch.optim.AdamW, True
 
 
 # ------------------------------------------------------------------------------------------------ checkpoints
@@ -161,12 +217,16 @@ def initialize_model(params):
                                   num_decoder_layers=mp["num_decoder_layers"], **common)
     lr = tp["learning_rate"]
     algo = str(mp.get("optimizer", "sgd")).lower()
-    if algo == "adam":
-        optimizer = GrooveAdam(model.parameters(), lr, model.engine)
+    # not in the reference (its YAMLs lack the keys: plain SGD / Adam, as there): training.momentum / nesterov / weight_decay, and "adamw"
+    wd, mom, nest = tp.get("weight_decay"), tp.get("momentum") or 0, bool(tp.get("nesterov") or False)
+    if algo in ("adam", "adamw"):
+        if mom or nest:
+            raise ValueError("momentum / nesterov belong to optimizer_algorithm 'sgd', got %r with %r" % (algo, {"momentum": mom, "nesterov": nest}))
+        optimizer = (GrooveAdamW if algo == "adamw" else GrooveAdam)(model.parameters(), lr, model.engine, weight_decay=wd)
     elif algo == "sgd":
-        optimizer = GrooveSGD(model.parameters(), lr, model.engine)
+        optimizer = GrooveSGD(model.parameters(), lr, model.engine, momentum=mom, nesterov=nest, weight_decay=wd or 0)
     else:
-        raise ValueError("optimizer_algorithm must be 'sgd' or 'adam' (ref:train.py:40-42), got %r" % algo)
+        raise ValueError("optimizer_algorithm must be 'sgd', 'adam' (ref:train.py:40-42) or 'adamw', got %r" % algo)
     _bind_engine(model)
     model.engine.set_state(lr=float(lr))
     model.engine.penalty = float(tp.get("hit_loss_penalty", 1.0))
