@@ -59,7 +59,7 @@ def cfg_dict(d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_
 class Runner:
     """One model instance behind the C ABI.  backend = 'emu' | 'hip'."""
 
-    def __init__(self, cfg, B, backend="emu", rng=(1234, 99, 0), lr=0.094, seq=True):
+    def __init__(self, cfg, B, backend="emu", rng=(1234, 99, 0), lr=0.094, seq=True, flags=0):
         self.cfgd, self.B, self.backend = cfg, B, backend
         self.lib = emu_lib() if backend == "emu" else _lib.get_lib()
         self.lib.cdll.gt_set_seq(int(bool(seq)))  # process-global switch: sequence-resident kernels (default where supported)
@@ -74,7 +74,7 @@ class Runner:
         self.Buf = NpBuf if backend == "emu" else CudaBuf
         self.c = _lib.make_config(B, cfg["embedding_size_src"], cfg["d_model"], cfg["n_heads"], cfg["dim_feedforward"],
                                   cfg["num_encoder_layers"], cfg.get("num_decoder_layers", 0), cfg.get("dropout", 0.0),
-                                  cfg.get("precision", 0))
+                                  cfg.get("precision", 0), flags=flags)      # flags: gt_config.flags (_lib.CFG_NO_QUAD | _lib.CFG_NO_LN_XCHG)
         self.total, self.entries = self.lib.param_layout(self.c)
         self.names = layout.param_names(cfg["d_model"], cfg["dim_feedforward"], cfg["embedding_size_src"],
                                         cfg["num_encoder_layers"], cfg.get("num_decoder_layers", 0))
@@ -206,3 +206,49 @@ def run_ranks(fn, world, *args):
         except Exception:
             if attempt:
                 raise
+
+
+# ---- GT_TRACE_DISPATCH=1 (csrc/gt_common.h; DESIGN.md "Dispatch trace"): "[dispatch] <family> key value ..." on stderr, one line per launch
+# (family "wgrad_queue": one per queued weight-gradient problem instead) -----------------------------------------------------------------
+DISPATCH_KEYS = {
+    "kernel": ("grid", "gy", "gz", "block"),
+    "gemm_cfg": ("BM", "BN", "BK", "M", "N", "K", "form", "epi", "prec", "splitk", "row", "rowx", "edge"),
+    "gemm32": ("BM", "BN", "M", "N", "K", "form", "epi", "prec", "src", "rowx"),
+    "gemm32h": ("BM", "BN", "M", "N", "K", "form", "epi", "prec", "src", "rowx"),
+    "gemm32row": ("BM", "BN", "M", "N", "K", "form", "epi", "prec", "src", "rowx"),
+    "gemm64": ("BM", "BN", "M", "N", "K", "form", "epi", "prec", "src", "rowx"),
+    "gemm64h": ("BM", "BN", "M", "N", "K", "form", "epi", "prec", "src", "rowx"),
+    "wgrad_queue": ("cls", "M", "N", "K", "k_chunk", "splitk", "prec", "tail"),
+    "wgrad_flush": ("cls", "n", "wgs", "prec"),
+    "ln_fwd": ("variant", "M", "d", "in16"),
+    "ln_bwd": ("variant", "M", "d", "rpw", "in16"),
+    "ln_param_reduce": ("jobs", "d"),
+    "attn_fwd": ("kernel", "pairs"),
+    "attn_bwd": ("kernel", "pairs"),
+    "heads": ("M", "d", "prec", "loss"),
+    "seq_pack": ("B", "d", "F", "L"),
+    "seq_fwd": ("phase", "split", "quad", "ride", "fuse_b0", "B", "d", "F", "L"),
+    "seq_bwd": ("phase", "split", "quad", "ride", "riders", "fuse_b0", "B", "d", "F", "L"),
+    "seq_tail": ("kind", "B", "d", "F", "L"),
+    "update": ("kind", "algo", "n"),
+}
+
+
+def parse_dispatch(stderr_text):
+    """[(family, {key: int | str})] of the "[dispatch]" lines in a captured stderr; every line must have exactly its family's documented keys."""
+    out = []
+    for ln in stderr_text.splitlines():
+        if not ln.startswith("[dispatch] "):
+            continue
+        tok = ln.split()[1:]
+        fam, kv = tok[0], tok[1:]
+        assert fam in DISPATCH_KEYS, ln
+        assert len(kv) % 2 == 0 and tuple(kv[0::2]) == DISPATCH_KEYS[fam], ln
+        out.append((fam, {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in zip(kv[0::2], kv[1::2])}))
+    return out
+
+
+def dispatched(trace, family, **kv):
+    """the trace's lines of `family` (a name or a tuple of names) whose keys have the given values"""
+    fams = (family,) if isinstance(family, str) else family
+    return [d for f, d in trace if f in fams and all(d.get(k) == v for k, v in kv.items())]

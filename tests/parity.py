@@ -16,6 +16,9 @@ from oracle import numpy_groove as ng
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 OUT_TOL, GRAD_TOL = 2e-5, 2e-4
+# the last check's largest error / bar ratios ("out": outputs against OUT_TOL, "grad": the worst gradient tensor against GRAD_TOL, "update":
+# check_update's ratio, "bf16_op": the worst per-operation ratio of check_ops_bf16, "bf16_e2e": the end-to-end sanity bound) -- figures for reports (profiles/dispatch_edges.txt); nothing asserts on them
+FIGURES = {}
 
 
 def shift_right(y):
@@ -52,7 +55,7 @@ def adopt_device_kinks(r, C, cfg):
     return adopted
 
 
-def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=True):
+def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=True, flags=0):
     """forward + loss + backward (+ saved activations) against the fp64 numpy oracle."""
     cfg = dict(cfg, dropout=p)
     P = ng.init_params(cfg, seed=seed, perturb=0.05)
@@ -60,11 +63,13 @@ def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=
     Ld = cfg.get("num_decoder_layers", 0)
     tgt = shift_right(y) if Ld else None
     rng = (1234, 99, 7)
-    r = Runner(cfg, B, backend, rng=rng, seq=seq)
+    r = Runner(cfg, B, backend, rng=rng, seq=seq, flags=flags)
     r.set_params(P)
     hvo = r.forward(x, tgt, train=p > 0)
     (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=rng if p > 0 else None, dtype=np.float64)
     ref = np.concatenate([h, v, o], -1)
+    FIGURES.clear()
+    FIGURES["out"] = float(np.abs(hvo - ref).max() / OUT_TOL)
     assert np.abs(hvo - ref).max() < OUT_TOL, "forward max-abs %g" % np.abs(hvo - ref).max()
     if check_ws:
         c0 = C["enc"][0]
@@ -90,6 +95,7 @@ def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=
         # everywhere -- e.g. LayerNorm gammas at d_model 2, where the normalised outputs are +-1 and the sum cancels; the
         # oracle's own fp32 run is 10 % off its fp64 run there) is compared absolutely
         err = float(np.abs(G[k] - Gr[k]).max() / max(np.abs(Gr[k]).max(), 1e-5))
+        FIGURES["grad"] = max(FIGURES.get("grad", 0.0), err / GRAD_TOL)
         assert err < GRAD_TOL, (k, err)
     return r, P, G, Gr
 
@@ -125,6 +131,7 @@ def _close(dev, ref, what, tol=BF16_OP_TOL, where=None, stored16=False, rms_tol=
     if where is not None:
         err = err * where
     scale = max(float(np.abs(ref).max()), 1e-6)
+    FIGURES["bf16_op"] = max(FIGURES.get("bf16_op", 0.0), float(err.max() / (tol * scale)))
     assert err.max() <= tol * scale, "%s: max |err| %.3g of max |ref| %.3g (ratio %.3g)" % (what, err.max(), scale, err.max() / scale)
     if rms_tol is not None:      # behind a HIDDEN bf16 rounding single elements may sit one ulp off (max bar 2^-8-ish); on average nothing may
         assert _rms(err) <= rms_tol * scale, "%s: rms err %.3g of max |ref| %.3g (ratio %.3g)" % (what, _rms(err), scale, _rms(err) / scale)
@@ -414,7 +421,7 @@ def _check_bf16_shadows(backend, cfg, B, p, P, x, y):
     return n
 
 
-def check_step_bf16(backend, cfg, B, p=0.0, penalty=0.47, seed=3, precision=1):
+def check_step_bf16(backend, cfg, B, p=0.0, penalty=0.47, seed=3, precision=1, flags=0):
     """precision = 2: the same two bars; the end-to-end sanity bound is taken against the bf16-OPERAND oracle with a wider factor (the
     storage roundings of precision 2 are additional noise of the same size: 2.5 x the bf16 effect)"""
     cfg = dict(cfg, dropout=p, precision=precision)
@@ -424,7 +431,7 @@ def check_step_bf16(backend, cfg, B, p=0.0, penalty=0.47, seed=3, precision=1):
     Ld = cfg.get("num_decoder_layers", 0)
     tgt = shift_right(y) if Ld else None
     rng = (1234, 99, 7)
-    r = Runner(cfg, B, backend, rng=rng)
+    r = Runner(cfg, B, backend, rng=rng, flags=flags)
     r.set_params(P)
     hvo = r.forward(x, tgt, train=p > 0)
     # (2) end to end, sanity bound
@@ -435,6 +442,8 @@ def check_step_bf16(backend, cfg, B, p=0.0, penalty=0.47, seed=3, precision=1):
     assert eq > 1e-5, "the bf16 rounding has no visible effect on this case: pick another"
     assert np.abs(hvo - ref).max() < BF16_OUT_MAX, "forward max-abs %g" % np.abs(hvo - ref).max()
     frac = BF16_E2E_FRAC if r.precision_in_force() < 2 else 2.5
+    FIGURES.clear()
+    FIGURES["bf16_e2e"] = _rms(hvo - ref) / (frac * eq + 1e-5)
     assert _rms(hvo - ref) <= frac * eq + 1e-5, "forward rms %g vs bf16 effect %g" % (_rms(hvo - ref), eq)
     stats, d_hvo = r.loss(y, penalty)
     rstats, _ = ng.calculate_loss((h, v, o), y.astype(np.float64), penalty)
@@ -467,7 +476,7 @@ def check_autocast_anchor(backend, cfg, B, seed=3):
     return _rms(hvo - ac), _rms(hvo - ref), eq
 
 
-def check_train_step_bf16(backend, cfg, B, p, precision=1):
+def check_train_step_bf16(backend, cfg, B, p, precision=1, flags=0):
     """gt_train_step with precision = 1 (fp32 master weights): after each of two SGD steps the per-operation checks hold on the
     step's own saved state, the update is exactly  w -= lr * g  of the device's gradients ... observed through the parameters:
     they move along the bf16-operand oracle's gradient within the end-to-end bound."""
@@ -475,7 +484,7 @@ def check_train_step_bf16(backend, cfg, B, p, precision=1):
     P = ng.init_params(cfg, seed=9, perturb=0.05)
     x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=4)
     tgt = shift_right(y) if cfg.get("num_decoder_layers", 0) else None
-    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=0.05)
+    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=0.05, flags=flags)
     r.set_params(P)
     cur = {k: v.astype(np.float64) for k, v in P.items()}
     for step in range(2):
@@ -595,7 +604,7 @@ def check_decisions_current(r, C):
     return len(todo)
 
 
-def check_train_step(backend, cfg, B, p, algo=0, seq=True):
+def check_train_step(backend, cfg, B, p, algo=0, seq=True, flags=0):
     """gt_train_step == forward+loss+backward+update with the oracle's masks, three steps; later steps use step+1.  Each step is checked
     twice: teacher-forced (the fp64 oracle's step from the device's own parameters and moments before it, per element: check_update) and
     along the free-running fp64 trajectory from the initial parameters.  Both oracle caches adopt the device's ReLU decisions at the kink."""
@@ -605,13 +614,14 @@ def check_train_step(backend, cfg, B, p, algo=0, seq=True):
     Ld = cfg.get("num_decoder_layers", 0)
     tgt = shift_right(y) if Ld else None
     lr = 0.05
-    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=lr, seq=seq)
+    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=lr, seq=seq, flags=flags)
     r.set_params(P)
     cur = {k: v.astype(np.float64) for k, v in P.items()}
     folded = r.lib.cdll.gt_step_launches(ctypes.byref(r.c)) > 0     # sequence-resident path: the update writes the next step's weight packs
     bound = kink_bound(r, cfg)
     f64 = lambda D: {k: np.asarray(v, np.float64) for k, v in D.items()}
     steps = 3
+    FIGURES.clear()
     for step in range(steps):
         before = r.unflatten(r.params.numpy())
         if algo == 1:
@@ -632,7 +642,7 @@ def check_train_step(backend, cfg, B, p, algo=0, seq=True):
         adam = None
         if algo == 1:
             adam = dict(m0=m0, v0=v0, m1=r.unflatten(r.m.numpy()), v1=r.unflatten(r.v.numpy()), t=step + 1)
-        check_update(before, got, Gt, lr, adam=adam, tag=step)
+        FIGURES["update"] = max(FIGURES.get("update", 0.0), check_update(before, got, Gt, lr, adam=adam, tag=step))
         # free-running fp64 trajectory
         (h, v, o), C = ng.forward(cur, cfg, x, tgt=tgt, rng=rng, dtype=np.float64)
         rstats, dpred = ng.calculate_loss((h, v, o), y.astype(np.float64), 0.38)

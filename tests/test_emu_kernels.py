@@ -373,3 +373,120 @@ def test_small_models_on_the_one_kernel_per_op_path(cfg, B, p):
     if cfg is ENC:
         parity.check_train_step("emu", cfg, 2, 0.2, seq=False)
         parity.check_bucketed_backward("emu", cfg, 2, 0.25, 2, exact=True, seq=False)
+
+
+# ---- host dispatch rules seen through GT_TRACE_DISPATCH (csrc/gt_common.h; DESIGN.md "Dispatch trace") --------------------------------------
+# The GPU counterparts at real sizes: tests/test_dispatch_edges_gpu.py.
+def test_dispatch_trace_shape(capfd):
+    """Every "[dispatch]" line has its family's documented keys (harness.DISPATCH_KEYS; parse_dispatch asserts it) and there is one line per
+    launch: on the sequence-resident path a whole train step has gt_step_launches of them, the next one (weight packs current) one less."""
+    import ctypes
+    import os
+    import numpy as np
+    from harness import Runner, dispatched, parse_dispatch
+    from oracle import numpy_groove as ng
+    os.environ["GT_TRACE_DISPATCH"] = "1"
+    try:
+        cfg = cfg_dict(128, 4, 64, 2, dropout=0.1)
+        r = Runner(cfg, 2, "emu")
+        r.set_params(ng.init_params(cfg, seed=9, perturb=0.05))
+        x, y = ng.synthetic_batch(2, 16, seed=4)
+        n = r.lib.cdll.gt_step_launches(ctypes.byref(r.c))
+        assert n > 0
+        capfd.readouterr()
+        r.train_step(x, y, 0.38)
+        first = parse_dispatch(capfd.readouterr().err)
+        r.train_step(x, y, 0.38, skip_update=4)
+        second = parse_dispatch(capfd.readouterr().err)
+        # the one-kernel-per-op path, encoder-decoder, one train step and a greedy decode: every family of that path
+        parity.check_train_step("emu", cfg_dict(32, 2, 16, 1, 1), 2, 0.2)
+        parity.check_predict("emu", cfg_dict(32, 2, 16, 1, 1), 2, True)
+        rest = parse_dispatch(capfd.readouterr().err)
+    finally:
+        del os.environ["GT_TRACE_DISPATCH"]
+    assert len(first) == n and [f for f, _ in first][0] == "seq_pack" and first[-1] == ("update", dict(kind="folded_pack", algo=0, n=r.total)), first
+    assert len(second) == n - 1 and not dispatched(second, "seq_pack")
+    fams = {f for f, _ in rest}
+    assert {"gemm_cfg", "wgrad_queue", "wgrad_flush", "attn_fwd", "attn_bwd", "ln_param_reduce", "update", "kernel"} <= fams, fams
+    # queued problems are not launches; each flush carries what was queued for its class since the last one
+    assert sum(d["n"] for d in dispatched(rest, "wgrad_flush")) == len(dispatched(rest, "wgrad_queue"))
+    assert dispatched(rest, "update", kind="plain", algo=0) and not dispatched(rest, ("seq_fwd", "seq_bwd"))
+    np.testing.assert_equal(capfd.readouterr().err.count("[dispatch]"), 0)          # off again: nothing is printed
+
+
+def test_config_flag_no_ln_xchg_overrules_forced_exchange(capfd):
+    """gt_config.flags (what StepEngine sets after an exchange time-out) against the process-wide switch: NO_LN_XCHG wins over a forced
+    gt_set_ln_exchange(1) -- checked against the oracle, the trace proving that the norms ran as row passes"""
+    import os
+    import harness
+    from harness import dispatched, parse_dispatch
+    from transformergrooveinfilling_amd import _lib
+    lib = harness.emu_lib()
+    gemms = ("gemm_cfg", "gemm32", "gemm32h", "gemm32row", "gemm64", "gemm64h")
+    os.environ["GT_TRACE_DISPATCH"] = "1"
+    lib.cdll.gt_set_ln_exchange(1)
+    try:
+        capfd.readouterr()
+        parity.check_step("emu", cfg_dict(256, 4, 128, 1), 2, 0.1)
+        forced = parse_dispatch(capfd.readouterr().err)
+        parity.check_step("emu", cfg_dict(256, 4, 128, 1), 2, 0.1, flags=_lib.CFG_NO_LN_XCHG)
+        flagged = parse_dispatch(capfd.readouterr().err)
+    finally:
+        del os.environ["GT_TRACE_DISPATCH"]
+        lib.cdll.gt_set_ln_exchange(-1)
+    assert dispatched(forced, gemms, rowx=1)                        # (the control: the forced exchange does take this shape)
+    assert not dispatched(flagged, gemms, rowx=1) and dispatched(flagged, "ln_fwd") and dispatched(flagged, "ln_bwd")
+
+
+def test_config_flag_no_quad(capfd):
+    """NO_QUAD gives the schedule of gt_set_seq_quad(0): two workgroups per sequence in the forward, backward phase 0 as a launch of its own --
+    the step and three train steps against the oracle through the flag and through the switch"""
+    import os
+    import harness
+    from harness import dispatched, parse_dispatch
+    from transformergrooveinfilling_amd import _lib
+    from oracle import numpy_groove as ng
+    lib = harness.emu_lib()
+    cfg = cfg_dict(128, 4, 64, 1)
+    os.environ["GT_TRACE_DISPATCH"] = "1"
+    try:
+        capfd.readouterr()
+        r = harness.Runner(dict(cfg, dropout=0.1), 2, "emu")                   # (the control: one train step on the library's own choice)
+        r.set_params(ng.init_params(cfg, seed=9, perturb=0.05))
+        r.train_step(*ng.synthetic_batch(2, 16, seed=4), 0.38)
+        default = parse_dispatch(capfd.readouterr().err)
+        noquad = {}
+        for how, kw in (("flags", dict(flags=_lib.CFG_NO_QUAD)), ("switch", dict(seq="split-noquad"))):
+            parity.check_step("emu", cfg, 2, 0.1, **kw)
+            parity.check_train_step("emu", cfg, 2, 0.1, **kw)
+            noquad[how] = parse_dispatch(capfd.readouterr().err)
+    finally:
+        del os.environ["GT_TRACE_DISPATCH"]
+        lib.cdll.gt_set_seq_quad(-1)
+        lib.cdll.gt_set_seq_split(-1)
+    assert dispatched(default, "seq_fwd", quad=1) and dispatched(default, "seq_fwd", fuse_b0=1)      # (the control)
+    for how, tr in noquad.items():
+        assert dispatched(tr, "seq_fwd") and not dispatched(tr, "seq_fwd", quad=1) and not dispatched(tr, "seq_fwd", fuse_b0=1), how
+        assert dispatched(tr, "seq_bwd", phase=0) and not dispatched(tr, "seq_bwd", quad=1), how
+
+
+def test_generic_large_tiles_with_edges_variant():
+    """The generic kernel's 64x64 and 128x128 configurations take a problem from GT_T64_MIN / GT_T128_MIN = 512 tiles -- beyond the emulator --
+    and a partial last row tile exists only where 32 B is no multiple of the tile.  A variant library with both thresholds at 2 tiles, in
+    a subprocess: M = 96 (a partial 64-row and a partial 128-row tile), dim_feedforward 100 (partial column tiles and a partial k slab),
+    fp32 and bf16 operands, on the one-kernel-per-op path."""
+    import os
+    import subprocess
+    from harness import ROOT, dispatched, parse_dispatch
+    so = os.path.join(ROOT, "tests", "emu", "libgroove_emu_edge.so")
+    subprocess.check_call([os.path.join(ROOT, "tests", "emu", "build_emu.sh"), "-DGT_T64_MIN=2", "-DGT_T128_MIN=2"], env=dict(os.environ, GT_EMU_OUT=so),
+                          stdout=subprocess.DEVNULL)
+    out = _emu_subprocess("parity.check_step('emu', cfg_dict(64, 4, 100, 1), 3, 0.2, seq=False)\n"
+                          "parity.check_step_bf16('emu', cfg_dict(64, 4, 100, 1), 3, 0.2)\n",
+                          dict(GT_EMU_LIB_PATH=so, GT_TRACE_DISPATCH="1"))
+    assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-3000:]
+    tr = parse_dispatch(out.stderr)
+    for prec in (0, 1):
+        assert dispatched(tr, "gemm_cfg", BM=64, BN=64, M=96, N=100, K=64, form="NT", epi=3, prec=prec, edge=1), prec      # FFN1
+        assert dispatched(tr, "gemm_cfg", BM=128, BN=128, M=96, N=192, K=64, epi=0, prec=prec, edge=1), prec              # QKV
+    assert dispatched(tr, "gemm_cfg", BM=64, BN=64, M=96, N=100, form="NN", epi=5, prec=0, edge=1)                        # FFN2 dgrad

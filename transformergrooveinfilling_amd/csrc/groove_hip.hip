@@ -35,6 +35,7 @@ extern "C" const char* gt_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------ launch timing
 GtProfile g_prof;
+thread_local bool g_dispatch_named = false;     // GT_TRACE_DISPATCH (gt_common.h)
 #ifndef GT_EMU
 struct ProfRec { const char* label; double flops, bytes; hipEvent_t a, b; };
 static std::vector<ProfRec> g_recs;
@@ -725,6 +726,7 @@ static void ln_bwd(const Ctx& x, const float* dy, const float* res, const float*
   if (part != nullptr && (x.d == 256 || x.d == 512) && al16(dy) && al16(xhat) && al16(dz) && (!res || al16(res)) && (!x.drop || al16(dzm))) {
     uint16_t* dzm16 = sh_act(x, x.drop ? dzm : dz);
     float* dzm32 = (x.drop && !only16(x, dzm)) ? dzm : (float*)nullptr;          // (level 2: the masked copy lives in bf16 alone)
+    gt_dispatch("ln_bwd variant v4 M %d d %d rpw %d in16 %d", x.M, x.d, rpw, dy16 != nullptr);
     if (x.d == 512) gt_launch(ln_bwd_v4_kernel<2>, dim3(nblk), dim3(256), x.s, dy, res, xhat, rstd, x.prm + gamma_off, dz,
                               dzm32, mk_drop(x, site), part, x.M, rpw, dzm16, dy16);
     else gt_launch(ln_bwd_v4_kernel<1>, dim3(nblk), dim3(256), x.s, dy, res, xhat, rstd, x.prm + gamma_off, dz,
@@ -732,6 +734,7 @@ static void ln_bwd(const Ctx& x, const float* dy, const float* res, const float*
     return;
   }
   need16(dy16 == nullptr, "LayerNorm backward of a bf16-only gradient (precision 2)");
+  gt_dispatch("ln_bwd variant generic M %d d %d rpw %d in16 0", x.M, x.d, rpw);
   gt_launch(ln_bwd_kernel, dim3(nblk), dim3(256), x.s, dy, res, xhat, rstd,
             x.prm + gamma_off, dz, (x.drop && !only16(x, dzm)) ? dzm : (float*)nullptr, mk_drop(x, site), x.grd + gamma_off,
             x.grd + gamma_off + (x.d + 63) / 64 * 64, part, x.M, x.d, rpw, sh_act(x, x.drop ? dzm : dz));
@@ -750,6 +753,7 @@ static void ln_bwd2(const Ctx& x, const float* dy, const float* xhat_o, const fl
     return;
   }
   gt_prof_tag("ln_bwd", 0, 20.0 * x.M * x.d);
+  gt_dispatch("ln_bwd variant two_norms M %d d %d rpw %d in16 0", x.M, x.d, rpw);
   gt_launch(ln_bwd2_kernel, dim3(nblk), dim3(256), x.s, dy, xhat_o, rstd_o, (const float*)(x.prm + gamma_o), part_o, xhat_i, rstd_i,
             (const float*)(x.prm + gamma_i), part_i, dz, (x.drop && !only16(x, dzm)) ? dzm : (float*)nullptr, mk_drop(x, site), x.M, x.d, rpw,
             sh_act(x, x.drop ? dzm : dz));
@@ -790,12 +794,14 @@ static int linear_res_ln(const Ctx& x, const float* in, int K, int64_t w_off, in
       gemm_launch<false, false, EPI_STORE>(g, x.s);
       if (second) {
         gt_prof_tag("ln_fwd", 0, 22.0 * x.M * x.d);
+        gt_dispatch("ln_fwd variant two_norms M %d d %d in16 1", x.M, x.d);
         gt_launch(ln_fwd2_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
                   x.prm + gamma_off + bo, out, xhat, rstd, (const float*)(x.prm + second->gamma_off),
                   (const float*)(x.prm + second->gamma_off + bo), second->y, second->xhat, second->rstd, x.M, x.d, (const uint16_t*)t16);
         return 0;
       }
       gt_prof_tag("ln_fwd", 0, 14.0 * x.M * x.d);
+      gt_dispatch("ln_fwd variant one_norm M %d d %d in16 1", x.M, x.d);
       gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
                 x.prm + gamma_off + bo, out, xhat, rstd, x.M, x.d, x.d, x.d, x.d, t16, (const uint16_t*)t16);
       return 0;
@@ -804,12 +810,14 @@ static int linear_res_ln(const Ctx& x, const float* in, int K, int64_t w_off, in
     gemm_launch<false, false, EPI_STORE>(g, x.s);
     if (second) {
       gt_prof_tag("ln_fwd", 0, 24.0 * x.M * x.d);
+      gt_dispatch("ln_fwd variant two_norms M %d d %d in16 0", x.M, x.d);
       gt_launch(ln_fwd2_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
                 x.prm + gamma_off + bo, out, xhat, rstd, (const float*)(x.prm + second->gamma_off),
                 (const float*)(x.prm + second->gamma_off + bo), second->y, second->xhat, second->rstd, x.M, x.d, (const uint16_t*)nullptr);
       return 0;
     }
     gt_prof_tag("ln_fwd", 0, 16.0 * x.M * x.d);
+    gt_dispatch("ln_fwd variant one_norm M %d d %d in16 0", x.M, x.d);
     gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
               x.prm + gamma_off + bo, out, xhat, rstd, x.M, x.d, x.d, x.d, x.d, sh_act(x, out), (const uint16_t*)nullptr);
     return 0;
@@ -821,6 +829,7 @@ static int linear_res_ln(const Ctx& x, const float* in, int K, int64_t w_off, in
   if (gemm_launch_row<false, false, EPI_RES_LN>(g, x.s)) return -1;
   if (second) {                                     // fused row tile for the first norm: the second one is its own pass
     gt_prof_tag("ln_fwd", 0, 12.0 * x.M * x.d);
+    gt_dispatch("ln_fwd variant one_norm M %d d %d in16 0", x.M, x.d);
     gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, (const float*)nullptr, no_drop(),
               x.prm + second->gamma_off, x.prm + second->gamma_off + bo, second->y, second->xhat, second->rstd, x.M, x.d, x.d, x.d, x.d, (uint16_t*)nullptr, (const uint16_t*)nullptr);
   }
@@ -859,10 +868,13 @@ static void attention_fwd(const Ctx& x, const float* q, int ldq, const float* k,
     a.q16 = reinterpret_cast<const uint16_t*>(q); a.k16 = a.q16 + (k - q); a.v16 = a.q16 + (v - q);
     a.q = a.k = a.v = nullptr;
     need16(((ldq | ldkv) & 3) == 0 && (attn_mfma_hd(x) == 64 || attn_mfma_hd(x) == 128), "attention over bf16-stored q / k / v (precision 2)");
+    gt_dispatch("attn_fwd kernel lds%d-bf16 pairs %u", attn_mfma_hd(x), grid.x);
     if (attn_mfma_hd(x) == 128) gt_launch(attn_fwd_lds_kernel<128, true>, grid, dim3(128), x.s, a);
     else gt_launch(attn_fwd_lds_kernel<64, true>, grid, dim3(128), x.s, a);
     return;
   }
+  if (attn_mfma_hd(x) == 0) gt_dispatch("attn_fwd kernel generic pairs %u", grid.x);
+  else gt_dispatch("attn_fwd kernel mfma%d%s pairs %u", attn_mfma_hd(x) < 0 ? 16 : attn_mfma_hd(x), attn_mfma_hd(x) < 0 ? "-padded" : "", grid.x);
   switch (attn_mfma_hd(x)) {
     case 16:  gt_launch(attn_fwd_mfma_kernel<16, false>, grid, dim3(128), x.s, a); break;
     case 32:  gt_launch(attn_fwd_mfma_kernel<32, false>, grid, dim3(128), x.s, a); break;
@@ -893,6 +905,7 @@ static void attention_bwd(const Ctx& x, const float* q, int ldq, const float* k,
     a.q16 = reinterpret_cast<const uint16_t*>(q); a.k16 = a.q16 + (k - q); a.v16 = a.q16 + (v - q); a.dctx16 = reinterpret_cast<const uint16_t*>(dctx);
     a.q = a.k = a.v = nullptr; a.dctx = nullptr;
     need16(((ldq | ldkv | lddq | lddkv | x.d) & 3) == 0 && (attn_mfma_hd(x) == 64 || attn_mfma_hd(x) == 128), "attention backward over bf16-stored operands (precision 2)");
+    gt_dispatch("attn_bwd kernel lds%dx%d-bf16 pairs %u", attn_mfma_hd(x), (attn_mfma_hd(x) == 128 || (int)grid.x < GT_ATTN_CS_MAX_PAIRS) ? 4 : 1, grid.x);
     if (attn_mfma_hd(x) == 128) gt_launch(attn_bwd_lds_kernel<128, 4, true>, grid, dim3(512), x.s, a);
     else if ((int)grid.x < GT_ATTN_CS_MAX_PAIRS) gt_launch(attn_bwd_lds_kernel<64, 4, true>, grid, dim3(512), x.s, a);
     else gt_launch(attn_bwd_lds_kernel<64, 1, true>, grid, dim3(128), x.s, a);
@@ -900,14 +913,18 @@ static void attention_bwd(const Ctx& x, const float* q, int ldq, const float* k,
   }
   const bool lds_ok = ((ldq | ldkv | lddq | lddkv | x.d) & 3) == 0 && al16(q) && al16(k) && al16(v) && al16(dctx) && al16(dq) && al16(dk) && al16(dv);
   if (attn_mfma_hd(x) == 64 && (int)grid.x >= lds_min && lds_ok) {
+    gt_dispatch("attn_bwd kernel lds64x1 pairs %u", grid.x);
     gt_launch(attn_bwd_lds_kernel<64>, grid, dim3(128), x.s, a);
     return;
   }
   if (attn_col_split(x, (int)grid.x) && lds_ok) {     // few pairs, wide heads: LDS-staged operands, four wave pairs per pair
+    gt_dispatch("attn_bwd kernel lds%dx4 pairs %u", attn_mfma_hd(x), grid.x);
     if (attn_mfma_hd(x) == 128) gt_launch(attn_bwd_lds_kernel<128, 4>, grid, dim3(512), x.s, a);
     else gt_launch(attn_bwd_lds_kernel<64, 4>, grid, dim3(512), x.s, a);
     return;
   }
+  if (attn_mfma_hd(x) == 0) gt_dispatch("attn_bwd kernel generic pairs %u", grid.x);
+  else gt_dispatch("attn_bwd kernel mfma%d%s pairs %u", attn_mfma_hd(x) < 0 ? 16 : attn_mfma_hd(x), attn_mfma_hd(x) < 0 ? "-padded" : "", grid.x);
   switch (attn_mfma_hd(x)) {
     case 16:  gt_launch(attn_bwd_mfma_kernel<16, false>, grid, dim3(128), x.s, a); break;
     case 32:  gt_launch(attn_bwd_mfma_kernel<32, false>, grid, dim3(128), x.s, a); break;
@@ -1174,6 +1191,7 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
   if (!g_seq_packs_current) {   // fragment-ordered copies of this step's weights, for the forward and the backward kernel
     const int64_t frags = 2 * (int64_t)x.c.n_enc_layers * x.W.pack_stride / 256;
     gt_prof_tag("seq_pack", 0.0, 12.0 * x.c.n_enc_layers * x.W.pack_stride);
+    gt_dispatch("seq_pack B %d d %d F %d L %d", x.c.batch, x.d, x.F, x.c.n_enc_layers);
     gt_seq_launch_pack(a, (unsigned)((frags + 3) / 4), x.s);
   }
   const int hc = x.hd < 16 ? 0 : x.hd;             // head-dim class (one instantiation each: the attention bodies' registers differ 4x)
@@ -1192,6 +1210,8 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
       SeqArgs ap = a;
       ap.phase = p;
       if (p > (a.quad_pro ? -1 : 0)) gt_prof_tag("seq_fwd", 0.0, 0.0);          // (flops and bytes of the whole forward are on the first phase's tag)
+      gt_dispatch("seq_fwd phase %d split 1 quad %d ride %d fuse_b0 %d B %d d %d F %d L %d", p, quad, seq_ride(x.c), fuse_b0 && p == x.c.n_enc_layers - 1,
+                  x.c.batch, x.d, x.F, x.c.n_enc_layers);
       if (fuse_b0 && p == x.c.n_enc_layers - 1) {
         ap.fuse_b0 = 1;
         gt_seq_launch_fb(ap, 4 * x.c.batch, x.s);
@@ -1203,6 +1223,7 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
     return 0;
   }
   const dim3 grid(x.c.batch);
+  gt_dispatch("seq_fwd phase 0 split 0 quad 0 ride 0 fuse_b0 0 B %d d %d F %d L %d", x.c.batch, x.d, x.F, x.c.n_enc_layers);
   gt_seq_launch_fwd(a, x.d, hc, false, x.c.batch, x.s);
   return 0;
 }
@@ -1335,6 +1356,7 @@ static void output_layer_fwd(const Ctx& x, float* hvo_out) {
     static const bool trace = [] { const char* e = getenv("GT_TRACE_HEADS"); return e && e[0] == '1'; }();     // (tests: which launches took the kernel)
     if (trace) fprintf(stderr, "[heads] M %d d %d precision %d loss %d\n", x.M, x.d, x.c.precision, hl.y != nullptr);
     gt_prof_tag("gemm_fwd_heads", 2.0 * x.M * GT_TGT * x.d, 4.0 * ((double)x.M * x.d + (double)GT_TGT * x.d + (double)x.M * GT_TGT));
+    gt_dispatch("heads M %d d %d prec %d loss %d", x.M, x.d, x.c.precision, hl.y != nullptr);
     if (x.c.precision) gt_launch(heads_fwd_kernel<1>, dim3(x.M / 16), dim3(256), x.s, fin, (const float*)(x.prm + x.P.out_w), (const float*)(x.prm + x.P.out_b), hvo_out, x.M, x.d, hl);
     else               gt_launch(heads_fwd_kernel<0>, dim3(x.M / 16), dim3(256), x.s, fin, (const float*)(x.prm + x.P.out_w), (const float*)(x.prm + x.P.out_b), hvo_out, x.M, x.d, hl);
     return;
@@ -1490,6 +1512,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     if (lnjobs.n > 0) {                             // LayerNorm dgamma/dbeta: one launch, fixed order
       lnjobs.bump = bump_state;
       gt_prof_tag("ln_param_reduce", 0, 4.0 * lnjobs.n * W.ln_part_stride);
+      gt_dispatch("ln_param_reduce jobs %d d %d", lnjobs.n, d);
       gt_launch(ln_param_reduce_kernel, dim3((2 * d + 63) / 64, lnjobs.n), dim3(1024), x.s, lnjobs);
     }
     return launch_status("gt_backward");
@@ -1542,6 +1565,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
           SeqArgs ap = a;
           ap.phase = p;
           if (p > p_lo && !(b0_done && p == 1)) gt_prof_tag("seq_bwd", 0.0, 0.0);
+          gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d", p, p == 0 && quad0, p == 0 ? 0 : R, b0_done, cfg->batch, d, x.F, L);
           // phase 0 has no riders: four workgroups per sequence there (column partners, gt_seq.h QUAD) while they fit the chip
           if (p == 0 && quad0) gt_seq_launch_bwd(ap, d, hc, true, 2 * a.nseq, x.s, true);
           else gt_seq_launch_bwd(ap, d, hc, true, a.nseq + (p == 0 ? 0 : R), x.s);
@@ -1549,6 +1573,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
         if (phase == 1) {      // bucket 0 reaches to the END of the buffer: the output layer's gradient now, by a launch of its own
           a.phase = 0; a.tail_phase = 0; a.tail_ksplit = 2; a.bump = nullptr;
           gt_prof_tag("seq_tail", 2.0 * M * 27.0 * d, 4.0 * M * (27.0 + d));
+          gt_dispatch("seq_tail kind out_early B %d d %d F %d L %d", cfg->batch, d, x.F, L);
           gt_seq_launch_tail(a, (unsigned)(gt_seq_wg_tiles(GT_TGT, d) * 2), x.s);
           return launch_status("gt_backward");
         }
@@ -1561,6 +1586,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
         const int nrest = a.ride_last_k < M ? per_layer + (L > 1 ? win : 0) : 0;
         gt_prof_tag("seq_tail", 2.0 * M * (3.0 * d * d + (a.out_early ? 0.0 : 27.0 * d) + (double)d * cfg->src_dim) + 2.0 * (M - a.ride_last_k) * nrest * 2048.0,
                     4.0 * M * (4.0 * d + cfg->src_dim));
+        gt_dispatch("seq_tail kind tail B %d d %d F %d L %d", cfg->batch, d, x.F, L);
         gt_seq_launch_tail(a, (unsigned)(nrest + tiles * ks), x.s);
         return launch_status("gt_backward");
       }
@@ -1570,9 +1596,11 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
           SeqArgs ap = a;
           ap.phase = p;
           if (p > 0) gt_prof_tag("seq_bwd", 0.0, 0.0);
+          gt_dispatch("seq_bwd phase %d split 1 quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d", p, cfg->batch, d, x.F, L);
           gt_seq_launch_bwd(ap, d, hc, true, 2 * cfg->batch, x.s);
         }
       } else {
+        gt_dispatch("seq_bwd phase 0 split 0 quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d", cfg->batch, d, x.F, L);
         gt_seq_launch_bwd(a, d, hc, false, cfg->batch, x.s);
       }
     }
@@ -1732,10 +1760,12 @@ static int optimizer_step_impl(int algo, float* params, float* grads, float* m, 
   const unsigned blocks = (unsigned)((n + 1023) / 1024);
   if (algo == 0) {
     gt_prof_tag("optimizer", 0, 12.0 * n);
+    gt_dispatch("update kind plain algo 0 n %lld", (long long)n);
     gt_launch(sgd_kernel, dim3(blocks), dim3(256), s, params, grads, n, (const gt_step_state*)state, zero_grads, (const unsigned*)err, guard);
   } else if (algo == 1) {
     if (!m || !v) return gt_fail("gt_optimizer_step: adam needs m and v");
     gt_prof_tag("optimizer", 0, 28.0 * n);
+    gt_dispatch("update kind plain algo 1 n %lld", (long long)n);
     gt_launch(adam_kernel, dim3(blocks), dim3(256), s, params, grads, m, v, n, (const gt_step_state*)state, zero_grads, step_advanced, (const unsigned*)err, guard);
   } else {
     return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
@@ -1766,6 +1796,7 @@ extern "C" int gt_optimizer_step_ws(const gt_config* cfg, int algo, float* param
   if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
   const SeqArgs a = mk_seq(x, nullptr, nullptr, nullptr);
   gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
+  gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)P.total);
   gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 0, (hipStream_t)stream);
   gt_launch(step_inc_kernel, dim3(1), dim3(64), (hipStream_t)stream, state, xchg_err(x.W, ws),
             (const float*)(grads + P.total - 1));
@@ -1832,6 +1863,7 @@ extern "C" int gt_train_step(const gt_config* cfg, int algo, float* params, floa
       if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
       const SeqArgs a = mk_seq(x, pe, xin, hvo_out);
       gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
+      gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)P.total);
       gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 1, (hipStream_t)stream);
       return launch_status("gt_train_step");
     }

@@ -1,8 +1,11 @@
 // Common device/host helpers for libgroove_hip.so (gfx950 / CDNA4 only).
 // GT_EMU is defined only by tests/emu/build_emu.sh (host fiber emulator, test infrastructure).
 #pragma once
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #ifdef GT_EMU
 #include "hip_emu.h"
@@ -92,8 +95,31 @@ static inline void gt_prof_tag(const char* label, double flops, double bytes) {
   if (g_prof.on) { g_prof.label = label; g_prof.flops = flops; g_prof.bytes = bytes; }
 }
 
+// ---- host-side dispatch trace (GT_TRACE_DISPATCH=1; DESIGN.md "Dispatch trace") ----
+// One line per kernel launch on stderr, "[dispatch] <family> key value ...": which kernel, tile class and schedule the host rules picked.
+// The environment is read per launch (a test switches it on for some calls of its process; host side, ~0.1 us).  A launch site that knows
+// more than the grid describes its launch with gt_dispatch() just before it; gt_launch() prints a "kernel" line for every launch nobody
+// described, so the number of lines without the "wgrad_queue" family (queued problems, gt_dispatch_note) IS the number of launches.
+extern thread_local bool g_dispatch_named;                   // the next launch has its line already
+static inline bool gt_dispatch_on() { const char* e = getenv("GT_TRACE_DISPATCH"); return e && e[0] == '1'; }
+__attribute__((format(printf, 2, 3))) static inline void gt_dispatch_line(bool names_launch, const char* fmt, ...) {
+  char line[320];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(line, sizeof(line), fmt, ap);
+  va_end(ap);
+  fprintf(stderr, "[dispatch] %s\n", line);
+  if (names_launch) g_dispatch_named = true;
+}
+#define gt_dispatch(...) do { if (gt_dispatch_on()) gt_dispatch_line(true, __VA_ARGS__); } while (0)         /* describes the launch that follows */
+#define gt_dispatch_note(...) do { if (gt_dispatch_on()) gt_dispatch_line(false, __VA_ARGS__); } while (0)   /* a line that is not a launch */
+
 template <typename... KArgs, typename... Args>
 static inline void gt_launch(void (*kern)(KArgs...), dim3 grid, dim3 block, hipStream_t s, Args... args) {
+  if (gt_dispatch_on()) {
+    if (!g_dispatch_named) fprintf(stderr, "[dispatch] kernel grid %u gy %u gz %u block %u\n", (unsigned)grid.x, (unsigned)grid.y, (unsigned)grid.z, (unsigned)block.x);
+    g_dispatch_named = false;
+  }
 #ifdef GT_EMU
   (void)s;
   emu::launch(grid, block, 0, [=]() { kern(args...); });

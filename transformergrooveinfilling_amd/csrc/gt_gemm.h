@@ -784,6 +784,13 @@ static inline const char* gemm_label() {
        : EPI == EPI_MASK_NZ ? "gemm_dgrad_ffn2" : EPI == EPI_ADD_RELUMASK_DROP ? "gemm_dgrad_input"
        : BKM ? "gemm_dgrad" : "gemm_fwd_bias";
 }
+// operand forms as the dispatch trace names them: A [M][K] x B [N][K] (NT), B [K][N] (NN), A [K][M] (TN: the weight gradients)
+static inline const char* gemm_form(bool akm, bool bkm) { return akm ? "TN" : bkm ? "NN" : "NT"; }
+// the interior-only ring-tile kernels (gt_gemm32.h, gt_gemm64.h): src = where the operands are staged from (fp32 tensors / their bf16 shadows)
+static inline void gemm_ring_dispatch(const char* family, int bm, int bn, const GemmArgs& g, bool bkm, int epi, const char* src) {
+  gt_dispatch("%s BM %d BN %d M %d N %d K %d form %s epi %d prec %d src %s rowx %d", family, bm, bn, g.M, g.N, g.K, gemm_form(false, bkm), epi, g.bf16, src,
+              g.rowx != nullptr);
+}
 template <int WM, int WN, int TM, int TN, int BK, bool AKM, bool BKM, int EPI, int PREC = 0>
 static inline void gemm_launch_cfg(const GemmArgs& g, int splitk, hipStream_t s) {
   typedef GemmCfg<WM, WN, TM, TN, BK, AKM, BKM, EPI, PREC> Cfg;
@@ -791,6 +798,8 @@ static inline void gemm_launch_cfg(const GemmArgs& g, int splitk, hipStream_t s)
   gt_prof_tag((g.as_dgrad && EPI == EPI_STORE) ? "gemm_dgrad" : gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K,
               4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
   dim3 grid((g.N + Cfg::BN - 1) / Cfg::BN, (g.M + Cfg::BM - 1) / Cfg::BM, splitk);
+  gt_dispatch("gemm_cfg BM %d BN %d BK %d M %d N %d K %d form %s epi %d prec %d splitk %d row %d rowx %d edge %d", Cfg::BM, Cfg::BN, BK, g.M, g.N, g.K,
+              gemm_form(AKM, BKM), EPI, PREC, splitk, Cfg::ROW ? 1 : 0, g.rowx != nullptr, (g.M % Cfg::BM || g.N % Cfg::BN || g.K % BK) ? 1 : 0);
   gt_launch(gemm_kernel<WM, WN, TM, TN, BK, AKM, BKM, EPI, PREC>, grid, dim3(Cfg::NT), s, g);
 }
 
@@ -871,6 +880,7 @@ static inline void wgrad_flush_one(WgradBatch& wb, int k, hipStream_t s) {
   GemmGroup& G = wb.grp[k];
   if (G.n == 0) return;
   gt_prof_tag("gemm_wgrad", wb.flops[k], wb.bytes[k]);
+  gt_dispatch("wgrad_flush cls %d n %d wgs %d prec %d", k, G.n, G.start[G.n], wb.bf16);
   if (k == 4 && GT_WGRAD32T) gt_launch(wgrad32t_group_kernel, dim3(G.start[G.n]), dim3(256), s, G);
   else if (k == 4) gt_launch(wgrad32_group_kernel<1, true, true>, dim3(G.start[G.n]), dim3(256), s, G);
   else if (k == 5) gt_launch(wgrad32_group_kernel<1, true, false>, dim3(G.start[G.n]), dim3(256), s, G);
@@ -918,6 +928,8 @@ static inline void wgrad_queue(WgradBatch& wb, GemmArgs g, hipStream_t s) {
   G.gx[i] = (g.N + tile - 1) / tile;
   G.gy[i] = (g.M + tile - 1) / tile;
   G.start[i + 1] = G.start[i] + G.gx[i] * G.gy[i] * splitk;
+  // (M, N: the gradient's rows and columns; K: the tokens it contracts over)
+  gt_dispatch_note("wgrad_queue cls %d M %d N %d K %d k_chunk %d splitk %d prec %d tail %d", cls, g.M, g.N, g.K, g.k_chunk, splitk, g.bf16, g.K % g.k_chunk ? 1 : 0);
   wb.flops[cls] += 2.0 * g.M * g.N * g.K;
   wb.bytes[cls] += 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
 }

@@ -482,6 +482,7 @@ static inline bool gemm32h_ok(const GemmArgs& g, int epi) {
 template <bool BKM, int EPI>
 static inline void gemm32h_launch(const GemmArgs& g, hipStream_t s) {
   gt_prof_tag(gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K, 2.0 * ((double)g.M * g.K + (double)g.N * g.K) + 4.0 * (double)g.M * g.N);
+  gemm_ring_dispatch("gemm32h", 128, 128, g, false, EPI, "bf16");
   gt_launch(gemm32h_kernel<EPI>, dim3(g.N / 128, g.M / 128), dim3(256), s, g);
 }
 
@@ -593,6 +594,7 @@ template <bool BKM, int EPI>
 static inline void gemm32row_launch(const GemmArgs& g, hipStream_t s) {
   gt_prof_tag(gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + 3.0 * g.M * g.N));
   // 64-row tiles once they fill the chip (one workgroup per CU at d_model 512: 132 KB of LDS); 32-row tiles below that at 256
+  gemm_ring_dispatch("gemm32row", (g.N == 512 || g.M / 64 >= GT_ROW32_BM64_MIN_WG) ? 64 : 32, g.N, g, BKM, EPI, "fp32");
   if (g.N == 512) gt_launch(gemm32row_kernel<512, 2, BKM, EPI>, dim3(g.M / 64), dim3(512), s, g);
   else if (g.M / 64 >= GT_ROW32_BM64_MIN_WG) gt_launch(gemm32row_kernel<256, 2, BKM, EPI>, dim3(g.M / 64), dim3(512), s, g);
   else gt_launch(gemm32row_kernel<256, 1, BKM, EPI>, dim3(g.M / 32), dim3(512), s, g);
@@ -612,6 +614,7 @@ template <bool BKM, int EPI>
 static inline void gemm32_launch(const GemmArgs& g, hipStream_t s) {
   gt_prof_tag((g.as_dgrad && EPI == EPI_STORE) ? "gemm_dgrad" : gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K,
               4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
+  gemm_ring_dispatch("gemm32", 128, 128, g, BKM, EPI, "fp32");
   if (g.bf16) gt_launch(gemm32_kernel<BKM, EPI, 1>, dim3(g.N / 128, g.M / 128), dim3(256), s, g);
   else        gt_launch(gemm32_kernel<BKM, EPI, 0>, dim3(g.N / 128, g.M / 128), dim3(256), s, g);
 }

@@ -917,6 +917,7 @@ static inline void gemm64_launch(const GemmArgs& g, hipStream_t s) {
   gemm64_trace("fp32-source", g, BKM, EPI);
   gt_prof_tag((g.as_dgrad && EPI == EPI_STORE) ? "gemm_dgrad" : gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K,
               4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
+  gemm_ring_dispatch("gemm64", 64, 64, g, BKM, EPI, "fp32");
   if (g.bf16) gt_launch(gemm64_kernel<BKM, EPI, 1>, dim3(g.N / 64, g.M / 64), dim3(256), s, g);
   else        gt_launch(gemm64_kernel<BKM, EPI, 0>, dim3(g.N / 64, g.M / 64), dim3(256), s, g);
 }
@@ -1013,5 +1014,6 @@ template <bool BKM, int EPI>
 static inline void gemm64h_launch(const GemmArgs& g, hipStream_t s) {
   gemm64_trace("bf16-source", g, BKM, EPI);
   gt_prof_tag(gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K, 2.0 * ((double)g.M * g.K + (double)g.N * g.K) + 4.0 * (double)g.M * g.N);
+  gemm_ring_dispatch("gemm64h", 64, 64, g, false, EPI, "bf16");
   gt_launch(gemm64h_kernel<EPI>, dim3(g.N / 64, g.M / 64), dim3(256), s, g);
 }
