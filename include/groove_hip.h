@@ -200,6 +200,37 @@ int gt_predict_pd(const gt_config* cfg, const float* params, const float* pe, co
 int gt_predict_pd_at(const gt_config* cfg, const float* params, const float* pe, const float* x, float* hvo_out, uint32_t seed,
                      int64_t first_seq, float* tgt_scratch, float* ws, gt_stream_t stream);
 
+/* The generation controls of this model family's front ends beyond one threshold (no counterpart in ref:evaluator.py:173, which passes
+ * only use_thres / thres / use_pd): a threshold per voice, a cap on the hits a voice may place in the 32-step pattern, a temperature on
+ * the hit logits.  vs is HOST memory, read when the call is enqueued (a captured graph keeps the values).
+ * Decision per hit element (row m, voice c), in fp32: p = sigmoid(logit / temperature) -- a division, so temperature 1 gives exactly
+ * the probability of gt_predict -- is written to prob_out[m * 9 + c]; mode 0: h = p > thres[c]; mode 1: h = (p > u) && (p > thres[c])
+ * with u the uniform of gt_predict_pd_at (same hash, same index first_seq * 32 * 27 + m * 27 + c: thres = 0 is pure sampling, and the
+ * samples do not depend on how a set is cut into calls; seed is unused in mode 0).  Velocity and offset pass through as in gt_predict.
+ * The encoder-decoder's greedy decode takes this decision at each step, writes that step's rows of prob_out and feeds the decided hits
+ * back (velocity and offset unmasked, as in gt_predict).
+ * Then ONE pass (gt_voice_select: the same pass over any (n_seq * 32, 27) HVO buffer and (n_seq * 32, 9) probabilities): per (sequence,
+ * voice), of the steps with a hit at most max_count[voice] stay -- the most probable ones, and of two equal probabilities the EARLIER
+ * step: step t stays iff fewer than max_count other hit steps t' have p[t'] > p[t], or p[t'] == p[t] with t' < t.  Dropped hits become 0.
+ * mask_vo: velocity and offset of every (step, voice) whose final hit is 0 become 0; without it those columns are never written.
+ * Encoder-decoder: the cap prunes the FINISHED pattern -- the hits fed back during the decode are the uncapped ones.
+ * With every cap at 32 and mask_vo 0 the pass is not launched.  No atomics: bitwise reproducible.  No host sync, no allocation; capturable.
+ * Rejected before any launch: vs or prob_out NULL, a threshold outside [0,1] or NaN, a cap outside 0..32, a temperature <= 0 or not
+ * finite, a mode other than 0 / 1 (gt_voice_select checks the whole struct too), first_seq < 0, an encoder-decoder call without
+ * tgt_scratch.  prob_out: (M,9) device floats. */
+typedef struct gt_voice_sampling {
+  float   thres[GT_VOICES];      /* each in [0,1] */
+  int32_t max_count[GT_VOICES];  /* 0..32 hits of this voice per sequence; 32 = no cap */
+  float   temperature;           /* > 0, finite; p = sigmoid(logit / temperature) */
+  int32_t mode;                  /* 0 = threshold, 1 = sampled */
+  int32_t mask_vo;               /* 1: velocity and offset of a (step, voice) without a hit are written as 0 */
+} gt_voice_sampling;
+int gt_predict_voices(const gt_config* cfg, const float* params, const float* pe, const float* x,
+                      float* hvo_out, const gt_voice_sampling* vs, uint32_t seed, int64_t first_seq,
+                      float* prob_out, float* tgt_scratch, float* ws, gt_stream_t stream);
+int gt_voice_select(float* hvo, const float* prob, const gt_voice_sampling* vs, int64_t n_seq,
+                    gt_stream_t stream);
+
 /* Replaces, for the device side, what the reference's evaluator computes from model.predict's output per epoch
  * (ref:evaluator.py:522-525: get_hits_accuracies / get_velocity_errors / get_micro_timing_errors over the 9 voices of
  * ROLAND_REDUCED_MAPPING): hvo_pred / hvo_gt are (n_rows,27) HVO tensors (n_rows = sequences * 32).  out30:

@@ -42,6 +42,12 @@ class GtOptHparams(ctypes.Structure):
                 ("decoupled", ctypes.c_int32)]
 
 
+class GtVoiceSampling(ctypes.Structure):
+    """gt_voice_sampling: host memory, read when gt_predict_voices / gt_voice_select is enqueued"""
+    _fields_ = [("thres", ctypes.c_float * GT_VOICES), ("max_count", ctypes.c_int32 * GT_VOICES), ("temperature", ctypes.c_float),
+                ("mode", ctypes.c_int32), ("mask_vo", ctypes.c_int32)]
+
+
 _vp, _cfgp = ctypes.c_void_p, ctypes.POINTER(GtConfig)
 _SIGS = {
     "gt_last_error": (ctypes.c_char_p, []),
@@ -68,6 +74,11 @@ _SIGS = {
     # cfg, params, pe, x, hvo_out, seed, tgt_scratch, ws, stream
     "gt_predict_pd": (ctypes.c_int, [_cfgp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp]),
     "gt_predict_pd_at": (ctypes.c_int, [_cfgp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int64, _vp, _vp, _vp]),
+    # cfg, params, pe, x, hvo_out, vs, seed, first_seq, prob_out, tgt_scratch, ws, stream
+    "gt_predict_voices": (ctypes.c_int, [_cfgp, _vp, _vp, _vp, _vp, ctypes.POINTER(GtVoiceSampling), ctypes.c_uint32, ctypes.c_int64, _vp,
+                                         _vp, _vp, _vp]),
+    # hvo, prob, vs, n_seq, stream
+    "gt_voice_select": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(GtVoiceSampling), ctypes.c_int64, _vp]),
     "gt_voice_metrics_scratch_floats": (ctypes.c_int64, [ctypes.c_int64]),
     # hvo_pred, hvo_gt, n_rows, out30, scratch, stream
     "gt_voice_metrics": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
@@ -173,6 +184,17 @@ def get_lib():
 
 # 0 fp32 | 1 bf16 GEMM operands | 2 ... and bf16 storage of the Linear outputs ("autocast": what torch.autocast(bfloat16) keeps in bf16)
 PRECISION = {"fp32": 0, "f32": 0, "float32": 0, 0: 0, None: 0, "bf16": 1, "bfloat16": 1, 1: 1, "bf16_storage": 2, "bf16s": 2, "autocast": 2, 2: 2}
+
+
+def make_voice_sampling(thres=0.5, max_count=32, temperature=1.0, mode=0, mask_vo=False):
+    """gt_voice_sampling from scalars (broadcast over the 9 voices) or sequences of 9"""
+    def nine(v, conv):
+        v = [conv(v)] * GT_VOICES if not hasattr(v, "__len__") else [conv(a) for a in v]
+        if len(v) != GT_VOICES:
+            raise ValueError("expected %d per-voice values, got %d" % (GT_VOICES, len(v)))
+        return v
+    return GtVoiceSampling((ctypes.c_float * GT_VOICES)(*nine(thres, float)), (ctypes.c_int32 * GT_VOICES)(*nine(max_count, int)),
+                           float(temperature), int(mode), int(bool(mask_vo)))
 
 
 def make_config(batch, src_dim, d_model, n_heads, dim_ff, n_enc_layers, n_dec_layers=0, dropout=0.0, precision=0, flags=0):

@@ -1981,8 +1981,10 @@ extern "C" int gt_gather_batch(const float* xs, const float* ys, const int64_t* 
 }
 
 // ------------------------------------------------------------------------------------ predict
+// vs != nullptr (gt_predict_voices): the per-voice head kernel decides and writes prob_out; thres / use_thres are then unused
 static int predict_impl(const gt_config* cfg, const float* params, const float* pe, const float* xin, float* hvo_out, float thres,
-                        int use_thres, uint32_t seed, float* tgt_scratch, float* ws, gt_stream_t stream, uint32_t idx0 = 0u);
+                        int use_thres, uint32_t seed, float* tgt_scratch, float* ws, gt_stream_t stream, uint32_t idx0 = 0u,
+                        const gt_voice_sampling* vs = nullptr, float* prob_out = nullptr);
 extern "C" int gt_predict(const gt_config* cfg, const float* params, const float* pe, const float* xin, float* hvo_out, float thres,
                           int use_thres, float* tgt_scratch, float* ws, gt_stream_t stream) {
   return predict_impl(cfg, params, pe, xin, hvo_out, thres, use_thres != 0, 0u, tgt_scratch, ws, stream);
@@ -2001,17 +2003,28 @@ extern "C" int gt_predict_pd_at(const gt_config* cfg, const float* params, const
   return predict_impl(cfg, params, pe, xin, hvo_out, 0.5f, 2, seed, tgt_scratch, ws, stream, (uint32_t)((uint64_t)first_seq * 32u * GT_TGT));
 }
 static int predict_impl(const gt_config* cfg, const float* params, const float* pe, const float* xin, float* hvo_out, float thres,
-                        int use_thres, uint32_t seed, float* tgt_scratch, float* ws, gt_stream_t stream, uint32_t idx0) {
+                        int use_thres, uint32_t seed, float* tgt_scratch, float* ws, gt_stream_t stream, uint32_t idx0,
+                        const gt_voice_sampling* vs, float* prob_out) {
   Ctx x;
   if (make_ctx(x, cfg, params, nullptr, ws, nullptr, 0, stream)) return -1;
   if (!pe || !xin || !hvo_out) return gt_fail("gt_predict: pe / x / hvo_out must not be NULL");
   const int M = x.M, B = cfg->batch;
+  VoiceHeadArgs va{};
+  if (vs) {
+    for (int c = 0; c < GT_VOICES; ++c) va.thres[c] = vs->thres[c];
+    va.temperature = vs->temperature;
+    va.mode = vs->mode;
+  }
   if (encoder_fwd(x, pe, xin)) return -1;
   if (cfg->n_dec_layers == 0) {
     output_layer_fwd(x, hvo_out);
-    gt_launch(predict_head_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)hvo_out, hvo_out, (float*)nullptr,
-              thres, use_thres, -1, B, seed, idx0);
-    return launch_status("gt_predict");
+    if (vs)
+      gt_launch(predict_voices_head_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)hvo_out, hvo_out, (float*)nullptr,
+                prob_out, va, -1, B, seed, idx0);
+    else
+      gt_launch(predict_head_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)hvo_out, hvo_out, (float*)nullptr,
+                thres, use_thres, -1, B, seed, idx0);
+    return launch_status(vs ? "gt_predict_voices" : "gt_predict");
   }
   if (!tgt_scratch) return gt_fail("gt_predict: encoder-decoder model needs tgt_scratch");
   // greedy decode: tgt row 0 = zeros, row t+1 = thresholded step t.  The encoder memory and every layer's cross-attention
@@ -2027,9 +2040,58 @@ static int predict_impl(const gt_config* cfg, const float* params, const float* 
   }
   for (int t = 0; t < 32; ++t) {
     decoder_step(x, pe, tgt_scratch, t, tmp);
-    gt_launch(predict_head_kernel, dim3((B * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)tmp, hvo_out, tgt_scratch, thres,
-              use_thres, t, B, seed, idx0);
+    if (vs)
+      gt_launch(predict_voices_head_kernel, dim3((B * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)tmp, hvo_out, tgt_scratch,
+                prob_out, va, t, B, seed, idx0);
+    else
+      gt_launch(predict_head_kernel, dim3((B * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)tmp, hvo_out, tgt_scratch, thres,
+                use_thres, t, B, seed, idx0);
   }
-  return launch_status("gt_predict");
+  return launch_status(vs ? "gt_predict_voices" : "gt_predict");
+}
+
+// ---- per-voice controls: thresholds, temperature, hit caps, velocity / offset mask (include/groove_hip.h, gt_voice_sampling) ----
+static int voice_sampling_check(const char* what, const gt_voice_sampling* vs) {
+  if (!vs) return gt_fail("%s: vs must not be NULL", what);
+  for (int c = 0; c < GT_VOICES; ++c) {
+    if (!(vs->thres[c] >= 0.f && vs->thres[c] <= 1.f)) return gt_fail("%s: thres[%d] = %g outside [0, 1]", what, c, (double)vs->thres[c]);
+    if (vs->max_count[c] < 0 || vs->max_count[c] > 32) return gt_fail("%s: max_count[%d] = %d outside 0..32", what, c, (int)vs->max_count[c]);
+  }
+  if (!(vs->temperature > 0.f) || __builtin_isinf(vs->temperature)) return gt_fail("%s: temperature %g must be > 0 and finite", what, (double)vs->temperature);
+  if (vs->mode != 0 && vs->mode != 1) return gt_fail("%s: mode %d (0 = threshold, 1 = sampled)", what, (int)vs->mode);
+  return 0;
+}
+// the cap / mask pass over n_seq sequences; launches nothing when it would change nothing
+static void voice_select_launch(float* hvo, const float* prob, const gt_voice_sampling* vs, int n_seq, hipStream_t s) {
+  VoiceSelectArgs va{};
+  bool capped = false;
+  for (int c = 0; c < GT_VOICES; ++c) {
+    va.max_count[c] = vs->max_count[c];
+    capped = capped || vs->max_count[c] < 32;
+  }
+  va.mask_vo = vs->mask_vo ? 1 : 0;
+  if (!capped && !va.mask_vo) return;
+  gt_prof_tag("voice_select", 0.0, (double)n_seq * 32 * 4.0 * (GT_TGT + GT_VOICES + (va.mask_vo ? GT_TGT : GT_VOICES)));
+  gt_launch(voice_select_kernel, dim3((unsigned)((n_seq + GT_VS_SEQ - 1) / GT_VS_SEQ)), dim3(GT_VS_THREADS), s, hvo, prob, va, n_seq);
+}
+extern "C" int gt_voice_select(float* hvo, const float* prob, const gt_voice_sampling* vs, int64_t n_seq, gt_stream_t stream) {
+  if (!hvo || !prob) return gt_fail("gt_voice_select: hvo / prob must not be NULL");
+  if (voice_sampling_check("gt_voice_select", vs)) return -1;
+  if (n_seq <= 0 || n_seq >= (1ll << 26)) return gt_fail("gt_voice_select: n_seq %lld out of range", (long long)n_seq);
+  voice_select_launch(hvo, prob, vs, (int)n_seq, (hipStream_t)stream);
+  return launch_status("gt_voice_select");
+}
+extern "C" int gt_predict_voices(const gt_config* cfg, const float* params, const float* pe, const float* xin, float* hvo_out,
+                                 const gt_voice_sampling* vs, uint32_t seed, int64_t first_seq, float* prob_out, float* tgt_scratch,
+                                 float* ws, gt_stream_t stream) {
+  if (voice_sampling_check("gt_predict_voices", vs)) return -1;
+  if (!prob_out) return gt_fail("gt_predict_voices: prob_out must not be NULL");
+  if (first_seq < 0) return gt_fail("gt_predict_voices: first_seq must be >= 0");
+  if (cfg && cfg->n_dec_layers > 0 && !tgt_scratch) return gt_fail("gt_predict_voices: encoder-decoder model needs tgt_scratch");
+  if (predict_impl(cfg, params, pe, xin, hvo_out, 0.5f, 1, seed, tgt_scratch, ws, stream, (uint32_t)((uint64_t)first_seq * 32u * GT_TGT), vs,
+                   prob_out))
+    return -1;
+  voice_select_launch(hvo_out, prob_out, vs, cfg->batch, (hipStream_t)stream);
+  return launch_status("gt_predict_voices");
 }
 

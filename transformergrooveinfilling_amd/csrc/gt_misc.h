@@ -783,6 +783,93 @@ __global__ __launch_bounds__(256) void predict_head_kernel(const float* __restri
   if (tgt != nullptr && t >= 0 && t + 1 < 32) tgt[(size_t)(m + 1) * GT_TGT + c] = a;
 }
 
+// predict with per-voice controls (gt_predict_voices): the element mapping of predict_head_kernel (t < 0: all rows, t >= 0: row t of every
+// sequence, hits fed to tgt row t+1).  p = sigmoid(logit / temperature) -- a DIVISION, so that temperature 1 leaves the logit's bits alone
+// and p is what predict_head_kernel computes -- goes to prob (M,9); h = p > thres[voice], in mode 1 also p > u (the uniform above, same
+// index).  Velocity and offset pass through.  The thresholds travel by value in the kernel arguments: a lane reads its voice's with one
+// load from the argument segment.
+struct VoiceHeadArgs { float thres[GT_VOICES]; float temperature; int mode; };
+__global__ __launch_bounds__(256) void predict_voices_head_kernel(const float* __restrict__ hvo_in, float* __restrict__ hvo_out,
+                                                                  float* __restrict__ tgt, float* __restrict__ prob, VoiceHeadArgs va, int t,
+                                                                  int B, uint32_t seed, uint32_t idx0) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  const int rows = (t < 0) ? B * 32 : B;
+  if (e >= rows * GT_TGT) return;
+  const int r = e / GT_TGT, c = e % GT_TGT;
+  const int m = (t < 0) ? r : r * 32 + t;
+  float a = hvo_in[(size_t)m * GT_TGT + c];
+  if (c < GT_VOICES) {
+    const float pr = gt_sigmoid(a / va.temperature);
+    prob[(size_t)m * GT_VOICES + c] = pr;
+    bool hit = pr > va.thres[c];
+    if (va.mode == 1)
+      hit = hit && pr > (float)(gt_fmix32(((idx0 + (uint32_t)(m * GT_TGT + c)) * 0x9E3779B1u) ^ seed) >> 8) * (1.0f / 16777216.0f);
+    a = hit ? 1.0f : 0.0f;
+  }
+  hvo_out[(size_t)m * GT_TGT + c] = a;
+  if (tgt != nullptr && t >= 0 && t + 1 < 32) tgt[(size_t)(m + 1) * GT_TGT + c] = a;
+}
+
+// ---- hit cap and velocity / offset mask (gt_voice_select; the pass behind gt_predict_voices) ---------------------------------------------
+// Per (sequence, voice): of the steps with a hit (h != 0) at most max_count[voice] stay, the most probable ones; of two equal
+// probabilities the earlier step stays.  Step t stays iff fewer than max_count other hit steps t' have p[t'] > p[t], or p[t'] == p[t] with
+// t' < t.  mask_vo: velocity and offset of every (step, voice) whose final h is 0 become 0.
+// A workgroup stages GT_VS_SEQ whole sequences -- per sequence the contiguous (32,27) HVO tile and (32,9) probability tile -- into LDS
+// with unit-stride loads, and one lane owns one (sequence, voice, step): thread = (sequence * 9 + voice) * 32 + step, so a 32-lane half
+// of a wave64 is the 32 steps of ONE voice.  The tiles keep their global row-major form in LDS: the half's own elements lie 27 (HVO) / 9
+// (probabilities) dwords apart -- odd strides, 32 distinct banks of the 32 a ds_read_b32 half sees -- and in the rank loop every lane of
+// the half reads the same address (a broadcast), so no read conflicts and the tile needs no transposing or padding.  The decisions go back
+// into the LDS tile and leave with unit-stride stores in which only the lanes of a hit column (with mask_vo: of every column) are
+// active: velocity and offset are otherwise never written.  No atomics, no state shared between workgroups: bitwise reproducible.
+#define GT_VS_SEQ 2
+#define GT_VS_THREADS (GT_VS_SEQ * GT_VOICES * 32)          // 576 = 9 waves
+struct VoiceSelectArgs { int max_count[GT_VOICES]; int mask_vo; };
+__global__ __launch_bounds__(GT_VS_THREADS) void voice_select_kernel(float* __restrict__ hvo, const float* __restrict__ prob,
+                                                                     VoiceSelectArgs va, int n_seq) {
+  __shared__ float sh[GT_VS_SEQ * 32 * GT_TGT];
+  __shared__ float sp[GT_VS_SEQ * 32 * GT_VOICES];
+  const int tid = threadIdx.x;
+  const int seq0 = blockIdx.x * GT_VS_SEQ;
+  const int ns = (n_seq - seq0 < GT_VS_SEQ) ? n_seq - seq0 : GT_VS_SEQ;      // the last workgroup may hold fewer sequences
+  float* gh = hvo + (size_t)seq0 * (32 * GT_TGT);
+  const float* gp = prob + (size_t)seq0 * (32 * GT_VOICES);
+#pragma unroll
+  for (int k = 0; k < GT_TGT / GT_VOICES; ++k) {            // 27 / 9 = 3 tile elements per lane, all in flight together
+    const int i = tid + k * GT_VS_THREADS;
+    if (i < ns * 32 * GT_TGT) sh[i] = gh[i];
+  }
+  if (tid < ns * 32 * GT_VOICES) sp[tid] = gp[tid];
+  __syncthreads();
+  const int s = tid / (GT_VOICES * 32), v = (tid / 32) % GT_VOICES, t = tid % 32;
+  const float* hv = sh + s * (32 * GT_TGT) + v;             // this voice's hit column, step stride 27
+  const float* pv = sp + s * (32 * GT_VOICES) + v;          // ... and probabilities, step stride 9
+  float h = 0.f;
+  if (s < ns) {
+    h = hv[t * GT_TGT];
+    const int cap = va.max_count[v];
+    if (h != 0.f && cap < 32) {
+      const float p = pv[t * GT_VOICES];
+      int ahead = 0;
+      for (int u = 0; u < 32; ++u) {
+        const float q = pv[u * GT_VOICES];
+        ahead += (hv[u * GT_TGT] != 0.f && (q > p || (q == p && u < t))) ? 1 : 0;
+      }
+      if (ahead >= cap) h = 0.f;
+    }
+  }
+  __syncthreads();                                          // every rank is counted: the tile may take the decisions
+  if (s < ns) sh[s * (32 * GT_TGT) + t * GT_TGT + v] = h;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < GT_TGT / GT_VOICES; ++k) {
+    const int i = tid + k * GT_VS_THREADS;
+    if (i >= ns * 32 * GT_TGT) continue;
+    const int c = i % GT_TGT;
+    if (c < GT_VOICES) gh[i] = sh[i];
+    else if (va.mask_vo) gh[i] = (sh[i - c + c % GT_VOICES] != 0.f) ? sh[i] : 0.f;
+  }
+}
+
 // ---- per-voice evaluation metrics (ref:evaluator.py:522-525 get_hits_accuracies / get_velocity_errors /
 // get_micro_timing_errors over the 9 voices of ROLAND_REDUCED_MAPPING) ---------------------------------------------------
 // pred / gt: (M,27) HVO = [hits | velocities | offsets].  Column c < 9: 1 if pred == gt (hit agreement), else the squared

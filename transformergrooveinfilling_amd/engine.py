@@ -160,6 +160,7 @@ class StepEngine:
         self._loss_slots = {}
         self._train_B = None           # batch size of the most recent train step (its slot is never evicted)
         self._predict_ws = {}          # chunk size -> (cfg, workspace, tgt scratch) of predict()
+        self._predict_prob = {}        # chunk size -> (m,32,9) probabilities of gt_predict_voices; lives as long as that chunk's workspace
         self._predict_epoch = None     # gt_layout_epoch() those were sized at
         # gt_config.flags of every configuration this engine hands to the library (per ENGINE, not per process: train.py's evaluation engines and
         # bench.py's second engine keep their own).  _flags_fallback: set for good once an in-launch exchange timed out (no QUAD, no row exchange);
@@ -790,8 +791,31 @@ class StepEngine:
             chunk *= 2
         return chunk
 
-    def predict(self, x, use_thres=True, thres=0.5, chunk=None, pd_seed=None):
-        out = self._predict(x, use_thres, thres, chunk, pd_seed)
+    def voice_sampling(self, use_thres=True, thres=0.5, pd_seed=None, voice_thresholds=None, voice_max_count=None, temperature=1.0,
+                       mask_vo=False):
+        """The gt_voice_sampling of a predict call, or None when every per-voice keyword has its default (the call then runs exactly as
+        gt_predict / gt_predict_pd_at).  voice_thresholds (9 values in [0,1]) override thres; pd_seed selects the sampled mode, whose
+        thresholds are 0 unless given.  ValueError for a wrong length or range, before the library is called."""
+        if voice_thresholds is None and voice_max_count is None and float(temperature) == 1.0 and not mask_vo:
+            return None
+        if not use_thres and pd_seed is None:
+            raise ValueError("voice_thresholds / voice_max_count / temperature / mask_vo need decided hits: use_thres=False returns probabilities")
+        th = voice_thresholds if voice_thresholds is not None else (0.0 if pd_seed is not None else thres)
+        vs = _lib.make_voice_sampling(th, 32 if voice_max_count is None else voice_max_count, temperature, 0 if pd_seed is None else 1, mask_vo)
+        if not all(0.0 <= t <= 1.0 for t in vs.thres):
+            raise ValueError("voice thresholds must lie in [0, 1]: %s" % list(vs.thres))
+        if not all(0 <= c <= 32 for c in vs.max_count):
+            raise ValueError("voice_max_count must lie in 0..32: %s" % list(vs.max_count))
+        if not (0.0 < vs.temperature < float("inf")):
+            raise ValueError("temperature must be > 0 and finite, got %r" % (temperature,))
+        return vs
+
+    def predict(self, x, use_thres=True, thres=0.5, chunk=None, pd_seed=None, voice_thresholds=None, voice_max_count=None, temperature=1.0,
+                mask_vo=False):
+        """voice_thresholds / voice_max_count / temperature / mask_vo: the per-voice controls of gt_predict_voices (include/groove_hip.h);
+        with all four at their defaults the call sequence is that of gt_predict / gt_predict_pd_at."""
+        vs = self.voice_sampling(use_thres, thres, pd_seed, voice_thresholds, voice_max_count, temperature, mask_vo)
+        out = self._predict(x, use_thres, thres, chunk, pd_seed, vs)
         # a timed-out exchange inside the call (its own workspaces): noticed when the call ends, the call repeated on the exchange-free schedule
         # (predict has no side effects; rank-local like an evaluation forward)
         bad = [(cfg, ws) for cfg, ws, _ in self._predict_ws.values()
@@ -802,12 +826,12 @@ class StepEngine:
 
             def again():
                 nonlocal out
-                out = self._predict(x, use_thres, thres, chunk, pd_seed)
+                out = self._predict(x, use_thres, thres, chunk, pd_seed, vs)
             self._local_retry(None, None, "predict", again)
         self._trim_predict_ws()
         return out
 
-    def _predict(self, x, use_thres=True, thres=0.5, chunk=None, pd_seed=None):
+    def _predict(self, x, use_thres=True, thres=0.5, chunk=None, pd_seed=None, vs=None):
         """model.predict for ANY batch size (ref:evaluator.py:173 passes the whole evaluation set at once):
         returns a (N,32,27) HVO tensor on the device ([h | v | o], one D2H for the evaluator).  The set is walked in chunks
         of `chunk` sequences (default: predict_chunk) over one cached workspace (sized for a chunk, not for N)."""
@@ -832,6 +856,14 @@ class StepEngine:
                 tgt = torch.empty(m, 32, 27, dtype=torch.float32, device=self.device) if not self.encoder_only else None
                 self._predict_ws[m] = (cfg, ws, tgt)
             cfg, ws, tgt = self._predict_ws[m]
+            if vs is not None:              # per-voice controls: the chunk's probabilities go to a buffer kept beside its workspace
+                self._predict_prob = {k: v for k, v in self._predict_prob.items() if k in self._predict_ws}
+                if m not in self._predict_prob:
+                    self._predict_prob[m] = torch.empty(m, 32, 9, dtype=torch.float32, device=self.device)
+                self.lib.call("gt_predict_voices", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(out[i:i + m]),
+                              ctypes.byref(vs), ctypes.c_uint32(int(pd_seed or 0) & 0xFFFFFFFF), ctypes.c_int64(i),
+                              _ptr(self._predict_prob[m]), _ptr(tgt), _ptr(ws), self.stream)
+                continue
             if pd_seed is not None:         # use_pd: hits sampled from the probabilities, hashed from the element's index in the WHOLE set
                 self.lib.call("gt_predict_pd_at", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(out[i:i + m]),
                               ctypes.c_uint32(int(pd_seed) & 0xFFFFFFFF), ctypes.c_int64(i), _ptr(tgt), _ptr(ws), self.stream)

@@ -162,28 +162,35 @@ class _GrooveBase(nn.Module):
         n = self.embedding_size_tgt // 3
         return hvo[..., :n], hvo[..., n:2 * n], hvo[..., 2 * n:]
 
-    def predict(self, src, use_thres=True, thres=0.5, use_pd=False, pd_seed=None):
+    def predict(self, src, use_thres=True, thres=0.5, use_pd=False, pd_seed=None, voice_thresholds=None, voice_max_count=None,
+                temperature=1.0, mask_vo=False):
         """eval-mode, no-grad inference (ref:evaluator.py:173): h thresholded to {0,1} (or probabilities).
         use_pd: hits SAMPLED from the predicted probabilities on the device (gt_predict_pd: h = 1 iff p > u, one u per (sequence, step,
         voice) from a counter hash of pd_seed -- drawn from torch's generator when not given); the encoder-decoder feeds the sampled
-        hits back through its greedy decode."""
+        hits back through its greedy decode.
+        Per-voice controls (gt_predict_voices): voice_thresholds -- 9 values in [0,1] that override thres (with use_pd: a floor under the
+        sampled hits, 0 when not given); voice_max_count -- 9 caps in 0..32 on a voice's hits per sequence, the most probable stay and of
+        equal probabilities the earlier step; temperature -- p = sigmoid(logit / temperature); mask_vo -- velocity and offset are 0
+        wherever the final hit is 0.  They need decided hits: with use_thres=False (and no use_pd) they raise ValueError."""
         self.eval()
         n = self.embedding_size_tgt // 3
+        voices = dict(voice_thresholds=voice_thresholds, voice_max_count=voice_max_count, temperature=temperature, mask_vo=mask_vo)
         if use_pd:
             if pd_seed is None:
                 pd_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
             with torch.no_grad():
-                hvo = self.engine.predict(src, pd_seed=pd_seed)
+                hvo = self.engine.predict(src, pd_seed=pd_seed, **voices)
             return hvo[..., :n], hvo[..., n:2 * n], hvo[..., 2 * n:]
         with torch.no_grad():
-            hvo = self.engine.predict(src, use_thres=use_thres, thres=thres)
+            hvo = self.engine.predict(src, use_thres=use_thres, thres=thres, **voices)
         return hvo[..., :n], hvo[..., n:2 * n], hvo[..., 2 * n:]
 
-    def predict_hvo(self, src, use_thres=True, thres=0.5):
+    def predict_hvo(self, src, use_thres=True, thres=0.5, voice_thresholds=None, voice_max_count=None, temperature=1.0, mask_vo=False):
         """Same, but returns the concatenated (N,32,27) HVO tensor (one D2H for the evaluator)."""
         self.eval()
         with torch.no_grad():
-            return self.engine.predict(src, use_thres=use_thres, thres=thres)
+            return self.engine.predict(src, use_thres=use_thres, thres=thres, voice_thresholds=voice_thresholds,
+                                       voice_max_count=voice_max_count, temperature=temperature, mask_vo=mask_vo)
 
 
 class GrooveTransformerEncoder(_GrooveBase):
