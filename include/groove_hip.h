@@ -183,6 +183,48 @@ int gt_train_step(const gt_config* cfg, int algo, float* params, float* grads, f
                   float* hvo_out, float* stats, float* tgt_scratch, float* ws, gt_step_state* state,
                   int skip_update, gt_stream_t stream);
 
+/* The loss controls beyond the one hit_loss_penalty (no counterpart in ref:train.py:55-58,176-179, whose calculate_loss has that float
+ * alone): separate penalties for the hit term and for the velocity / offset terms, torch.nn.BCEWithLogitsLoss(pos_weight) per voice, a
+ * weight per voice and per term, focal modulation of the hit term.  lo is HOST memory, read when the call is enqueued (a captured graph
+ * keeps the values).  Per element (row m, voice c), in fp32, with p = sigmoid(h), sp = log1pf(expf(-|h|)):
+ *   pen_h = (yh == 1) ? 1 : penalty_h;  pen_vo = (yh == 1) ? 1 : penalty_vo
+ *   bce0  = max(h,0) - h yh + sp + (pos_weight[c] - 1) yh (sp + max(-h,0))        (torch's formula; pos_weight 1 adds an exact zero)
+ *   f     = 1 for focal_gamma == 0 (no powf), else powf(q, focal_gamma), q = yh sigmoid(-h) + (1 - yh) p  (= 1 - p_t, no cancellation)
+ *   bce   = voice_weight[c] pen_h f bce0;  mv = voice_weight[c] pen_vo (v - yv)^2;  mo = voice_weight[c] pen_vo (o - yo)^2
+ * stats (8 floats): [3] [4] [5] the means over the M rows of the voice sums of bce / mv / mo, [0] = (tw[0] [3] + tw[1] [4]) + tw[2] [5],
+ * [1] hit accuracy, [2] [6] [7] = 0.  voice_stats (36 floats, or NULL): [0..9) [9..18) [18..27) each voice's share of [3] [4] [5],
+ * [27..36) the hit accuracy per voice.  d_out (M,27), or NULL: the gradient of stats[0] w.r.t. the activated outputs (wrt_logits = 0), or
+ * already multiplied by the head activations' derivative (wrt_logits = 1: what backward's workspace "dlogits" holds); finite for every
+ * finite input; where q == 0 the focal term and its gradient are 0.  With every option neutral and penalty_vo = penalty_h, d_out is
+ * bit for bit gt_loss's.
+ * One workgroup per sequence; no float atomics: the per-voice sums over a sequence's 32 rows, then over the workgroups in the last arriver,
+ * run in a fixed order that depends on the batch alone -- stats and voice_stats are bitwise repeatable.  scratch: gt_loss_scratch_floats
+ * floats (the ticket word, then 36 partials per sequence); zero once, left zero by every call.  Needs no workspace and no step state.
+ * Rejected before any launch: lo / hvo / y / stats / scratch NULL, any NaN or Inf in lo, a pos_weight <= 0, a negative voice_weight,
+ * term_weight or penalty, a focal_gamma outside [0, 8].  No host sync, no allocation; capturable. */
+typedef struct gt_loss_opts {
+  float penalty_h;                 /* weight of the hit term where y_h != 1 (gt_loss's hit_loss_penalty) */
+  float penalty_vo;                /* weight of the velocity and offset terms where y_h != 1 */
+  float pos_weight[GT_VOICES];     /* BCEWithLogitsLoss(pos_weight): > 0, finite */
+  float voice_weight[GT_VOICES];   /* multiplies all three terms of a voice: >= 0, finite */
+  float focal_gamma;               /* 0 = plain BCE; 0 <= gamma <= 8 */
+  float term_weight[3];            /* loss = tw[0] bce + tw[1] mse_v + tw[2] mse_o: >= 0, finite */
+} gt_loss_opts;
+int64_t gt_loss_scratch_floats(const gt_config* cfg);
+int gt_loss_ex(const gt_config* cfg, const float* hvo, const float* y, const gt_loss_opts* lo, float* stats, float* voice_stats,
+               float* d_out, int wrt_logits, float* scratch, gt_stream_t stream);
+/* gt_train_step with that loss as a launch of its own: [shift y for the decoder,] gt_forward(train = 1) WITHOUT the loss hand-off (the
+ * sequence-resident forward does not run on into backward phase 0), gt_loss_ex(wrt_logits = 1) into the workspace's "dlogits", the
+ * unchanged backward, and for skip_update 0 the unchanged update (sequence-resident path: the folded update + pack).  skip_update 0..3
+ * and GT_STEP_PACKS_CURRENT mean what they mean for gt_train_step (3 runs the rest of the backward alone: lo is not read).  The same
+ * precondition on grads, the same fail-safe of the in-launch exchanges (it lives in the update).  One launch more than gt_train_step -- two
+ * where gt_train_step's last forward launch runs on into backward phase 0; gt_step_launches itself is unchanged.  With neutral options the results agree with gt_train_step to fp32
+ * rounding (the loss sums run in another order). */
+int gt_train_step_loss(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v,
+                       const float* pe, const float* x, const float* y, const gt_loss_opts* lo, float* voice_stats,
+                       float* loss_scratch, float* hvo_out, float* stats, float* tgt_scratch, float* ws, gt_step_state* state,
+                       int skip_update, gt_stream_t stream);
+
 /* Replaces model.predict(src, use_thres=True, thres=0.5) (ref:evaluator.py:173-177): eval forward,
  * h = sigmoid(logit) > thres ? 1 : 0 (or the probability when use_thres == 0); the encoder-decoder
  * runs the 32-step greedy decode.  hvo_out (M,27) is the concatenated HVO the evaluator builds. */

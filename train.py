@@ -84,6 +84,12 @@ def build_parser():
     p.add_argument("--weight_decay", default=None, type=float,
                    help="weight decay: L2 for sgd / adam (added to the gradient), decoupled for adamw.  Also the YAML key weight_decay; "
                         "default: torch's (0; 1e-2 for adamw)")
+    # the loss's options (gt_loss_opts; the reference has hit_loss_penalty alone).  Also YAML keys of the same names; all off by default
+    p.add_argument("--pos_weight", default=None, type=str, help="BCEWithLogitsLoss(pos_weight): 1 or 9 comma-separated floats (one per voice)")
+    p.add_argument("--voice_weight", default=None, type=str, help="9 comma-separated weights, one per voice, on all three loss terms")
+    p.add_argument("--focal_gamma", default=None, type=float, help="focal modulation (1 - p_t)^gamma of the hit term, 0..8")
+    p.add_argument("--vo_penalty", default=None, type=float, help="penalty of the velocity / offset terms where there is no hit (default: hit_loss_penalty)")
+    p.add_argument("--loss_weights", default=None, type=str, help="h,v,o: weights of the hit / velocity / offset terms in the loss")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible weight gradients (gt_set_deterministic: no token split in the weight-gradient kernels; +9-30 %% step time)")
     return p
@@ -113,7 +119,30 @@ def load_hyperparameters(args):
     hp["nesterov"] = bool(hp.get("nesterov", args.nesterov))
     wd = hp.get("weight_decay", args.weight_decay)
     hp["weight_decay"] = None if wd is None else float(wd)
+    # the loss's options, the same way (a YAML may give a list or a comma-separated string; the reference's YAMLs lack the keys: the plain loss)
+    for k, counts in (("pos_weight", (1, 9)), ("voice_weight", (9,)), ("loss_weights", (3,))):
+        hp[k] = _floats(hp.get(k, getattr(args, k)), counts, k)
+    for k in ("focal_gamma", "vo_penalty"):
+        v = hp.get(k, getattr(args, k))
+        hp[k] = None if v is None else float(v)
     return hp
+
+
+def _floats(v, counts, what):
+    """None, a number, a list or a comma-separated string -> list of floats whose length is one of `counts`"""
+    if v is None:
+        return None
+    v = [float(a) for a in v.split(",")] if isinstance(v, str) else [float(a) for a in v] if hasattr(v, "__len__") else [float(v)]
+    if len(v) not in counts:
+        raise SystemExit("--%s expects %s comma-separated floats, got %d" % (what, " or ".join(str(c) for c in counts), len(v)))
+    return v
+
+
+def loss_setup(hp):
+    """(bce_fn keywords, train_loop's loss_options) of the loss flags / YAML keys: ({}, None) while none is set"""
+    opts = {k: hp[src] for k, src in (("voice_weight", "voice_weight"), ("focal_gamma", "focal_gamma"), ("vo_penalty", "vo_penalty"),
+                                      ("term_weights", "loss_weights")) if hp.get(src) is not None}
+    return ({} if hp.get("pos_weight") is None else {"pos_weight": hp["pos_weight"]}), (opts or None)
 
 
 def model_params(hp, device):
@@ -245,7 +274,9 @@ def main(argv=None):
     else:
         sampler = None
         loader = DataLoader(ds, batch_size=hp["batch_size"], shuffle=True, pin_memory=True)
-    bce, mse = torch.nn.BCEWithLogitsLoss(reduction="none"), torch.nn.MSELoss(reduction="none")
+    bce_kw, loss_options = loss_setup(hp)
+    bce_kw = {k: torch.tensor(v, device=device) for k, v in bce_kw.items()}
+    bce, mse = torch.nn.BCEWithLogitsLoss(reduction="none", **bce_kw), torch.nn.MSELoss(reduction="none")
     part, full = save_schedule(hp["epochs"], only_final=bool(args.only_final_eval) and str(args.only_final_eval) != "False")
     save_dir = args.save_dir or (wb.run.dir if wb else os.path.join(ROOT, "checkpoints"))
     os.makedirs(save_dir, exist_ok=True)
@@ -258,7 +289,7 @@ def main(argv=None):
                        # test / validation LOSS after the epoch's batches, as the reference's train_loop arguments (ref:train.py:204-212)
                        test_inputs=test[0], test_gt=test[1], validation_inputs=val[0], validation_gt=val[1],
                        save=(rank == 0 and (ep in part or ep in full)), save_dir=save_dir,
-                       run_id=(wb.run.id if wb else "local"), max_grad_norm=hp["max_grad_norm"])
+                       run_id=(wb.run.id if wb else "local"), max_grad_norm=hp["max_grad_norm"], loss_options=loss_options)
         torch.cuda.synchronize()
         if rank == 0:
             n = min(len(loader) * hp["batch_size"], len(ds) // world) * world

@@ -48,6 +48,12 @@ class GtVoiceSampling(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("mask_vo", ctypes.c_int32)]
 
 
+class GtLossOpts(ctypes.Structure):
+    """gt_loss_opts: host memory, read when gt_loss_ex / gt_train_step_loss is enqueued"""
+    _fields_ = [("penalty_h", ctypes.c_float), ("penalty_vo", ctypes.c_float), ("pos_weight", ctypes.c_float * GT_VOICES),
+                ("voice_weight", ctypes.c_float * GT_VOICES), ("focal_gamma", ctypes.c_float), ("term_weight", ctypes.c_float * 3)]
+
+
 _vp, _cfgp = ctypes.c_void_p, ctypes.POINTER(GtConfig)
 _SIGS = {
     "gt_last_error": (ctypes.c_char_p, []),
@@ -69,6 +75,12 @@ _SIGS = {
     # cfg, algo, params, grads, m, v, pe, x, y, penalty, hvo_out, stats, tgt_scratch, ws, state, skip_update, stream
     "gt_train_step": (ctypes.c_int, [_cfgp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp,
                                      _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "gt_loss_scratch_floats": (ctypes.c_int64, [_cfgp]),
+    # cfg, hvo, y, lo, stats, voice_stats, d_out, wrt_logits, scratch, stream
+    "gt_loss_ex": (ctypes.c_int, [_cfgp, _vp, _vp, ctypes.POINTER(GtLossOpts), _vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    # cfg, algo, params, grads, m, v, pe, x, y, lo, voice_stats, loss_scratch, hvo_out, stats, tgt_scratch, ws, state, skip_update, stream
+    "gt_train_step_loss": (ctypes.c_int, [_cfgp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(GtLossOpts), _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     # cfg, params, pe, x, hvo_out, thres, use_thres, tgt_scratch, ws, stream
     "gt_predict": (ctypes.c_int, [_cfgp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_int, _vp, _vp, _vp]),
     # cfg, params, pe, x, hvo_out, seed, tgt_scratch, ws, stream
@@ -195,6 +207,45 @@ def make_voice_sampling(thres=0.5, max_count=32, temperature=1.0, mode=0, mask_v
         return v
     return GtVoiceSampling((ctypes.c_float * GT_VOICES)(*nine(thres, float)), (ctypes.c_int32 * GT_VOICES)(*nine(max_count, int)),
                            float(temperature), int(mode), int(bool(mask_vo)))
+
+
+def make_loss_opts(penalty_h=1.0, penalty_vo=None, pos_weight=1.0, voice_weight=1.0, focal_gamma=0.0, term_weight=(1.0, 1.0, 1.0)):
+    """gt_loss_opts from scalars (pos_weight / voice_weight: broadcast over the 9 voices) or sequences of 9; penalty_vo None = penalty_h.
+    ValueError for a wrong length or a value the library would refuse (include/groove_hip.h), before the library is called."""
+    def many(v, n, what):
+        if torch_like(v):
+            v = v.detach().reshape(-1).tolist()
+        v = [float(v)] * n if not hasattr(v, "__len__") else [float(a) for a in v]
+        if len(v) == 1:
+            v = v * n
+        if len(v) != n:
+            raise ValueError("%s: expected 1 or %d values, got %d" % (what, n, len(v)))
+        return v
+    finite = lambda a: a == a and abs(a) != float("inf")
+    ph = float(penalty_h)
+    pvo = ph if penalty_vo is None else float(penalty_vo)
+    pw, vw, tw = many(pos_weight, GT_VOICES, "pos_weight"), many(voice_weight, GT_VOICES, "voice_weight"), many(term_weight, 3, "term_weight")
+    g = float(focal_gamma)
+    if not all(finite(a) and a >= 0.0 for a in [ph, pvo] + vw + tw):
+        raise ValueError("penalties, voice_weight and term_weight must be >= 0 and finite: %r" % (([ph, pvo], vw, tw),))
+    if not all(finite(a) and a > 0.0 for a in pw):
+        raise ValueError("pos_weight must be > 0 and finite: %r" % (pw,))
+    if not 0.0 <= g <= 8.0:
+        raise ValueError("focal_gamma must lie in [0, 8], got %r" % (focal_gamma,))
+    return GtLossOpts(ph, pvo, (ctypes.c_float * GT_VOICES)(*pw), (ctypes.c_float * GT_VOICES)(*vw), g, (ctypes.c_float * 3)(*tw))
+
+
+def torch_like(v):
+    return hasattr(v, "detach") and hasattr(v, "reshape")
+
+
+def loss_opts_tuple(lo):
+    """the hashable form of a GtLossOpts (StepEngine.loss_opts; part of a captured graph's key): its 24 floats in field order"""
+    return (lo.penalty_h, lo.penalty_vo) + tuple(lo.pos_weight) + tuple(lo.voice_weight) + (lo.focal_gamma,) + tuple(lo.term_weight)
+
+
+def loss_opts_struct(t):
+    return GtLossOpts(t[0], t[1], (ctypes.c_float * GT_VOICES)(*t[2:11]), (ctypes.c_float * GT_VOICES)(*t[11:20]), t[20], (ctypes.c_float * 3)(*t[21:24]))
 
 
 def make_config(batch, src_dim, d_model, n_heads, dim_ff, n_enc_layers, n_dec_layers=0, dropout=0.0, precision=0, flags=0):

@@ -1396,6 +1396,43 @@ extern "C" int gt_loss(const gt_config* cfg, const float* hvo, const float* y, f
   return launch_status("gt_loss");
 }
 
+// The loss with options (gt_misc.h loss_ex_kernel): one workgroup per sequence, the options baked into the launch (host struct, read here --
+// as gt_optimizer_prepare's hyper-parameters are).  scratch = the ticket word, then GT_LOSSX_PART partials per sequence.
+static int loss_opts_check(const char* what, const gt_loss_opts* lo) {
+  if (!lo) return gt_fail("%s: lo must not be NULL", what);
+  const auto bad = [](float a) { return !(a >= 0.f) || __builtin_isinf(a); };      // negative, NaN or Inf
+  if (bad(lo->penalty_h) || bad(lo->penalty_vo))
+    return gt_fail("%s: penalty_h %g / penalty_vo %g must be >= 0 and finite", what, (double)lo->penalty_h, (double)lo->penalty_vo);
+  for (int c = 0; c < GT_VOICES; ++c) {
+    if (bad(lo->pos_weight[c]) || lo->pos_weight[c] == 0.f) return gt_fail("%s: pos_weight[%d] = %g must be > 0 and finite", what, c, (double)lo->pos_weight[c]);
+    if (bad(lo->voice_weight[c])) return gt_fail("%s: voice_weight[%d] = %g must be >= 0 and finite", what, c, (double)lo->voice_weight[c]);
+  }
+  for (int q = 0; q < 3; ++q)
+    if (bad(lo->term_weight[q])) return gt_fail("%s: term_weight[%d] = %g must be >= 0 and finite", what, q, (double)lo->term_weight[q]);
+  if (!(lo->focal_gamma >= 0.f && lo->focal_gamma <= 8.f)) return gt_fail("%s: focal_gamma %g outside [0, 8]", what, (double)lo->focal_gamma);
+  return 0;
+}
+static void loss_ex_launch(const gt_config& c, const float* hvo, const float* y, const gt_loss_opts& lo, float* stats, float* voice_stats,
+                           float* d_out, bool wrt_logits, float* scratch, hipStream_t s) {
+  const int M = c.batch * 32;
+  gt_prof_tag("loss_ex", 0, 12.0 * M * GT_TGT);
+  unsigned* ticket = reinterpret_cast<unsigned*>(scratch);
+  if (wrt_logits) gt_launch(loss_ex_kernel<true>, dim3(c.batch), dim3(GT_LOSSX_THREADS), s, hvo, y, lo, stats, voice_stats, d_out, M, scratch + 1, ticket);
+  else            gt_launch(loss_ex_kernel<false>, dim3(c.batch), dim3(GT_LOSSX_THREADS), s, hvo, y, lo, stats, voice_stats, d_out, M, scratch + 1, ticket);
+}
+extern "C" int64_t gt_loss_scratch_floats(const gt_config* cfg) {
+  if (check_cfg(cfg)) return 0;
+  return (int64_t)cfg->batch * GT_LOSSX_PART + 1;
+}
+extern "C" int gt_loss_ex(const gt_config* cfg, const float* hvo, const float* y, const gt_loss_opts* lo, float* stats, float* voice_stats,
+                          float* d_out, int wrt_logits, float* scratch, gt_stream_t stream) {
+  if (check_cfg(cfg)) return -1;
+  if (!hvo || !y || !stats || !scratch) return gt_fail("gt_loss_ex: hvo / y / stats / scratch must not be NULL");
+  if (loss_opts_check("gt_loss_ex", lo)) return -1;
+  loss_ex_launch(*cfg, hvo, y, *lo, stats, voice_stats, d_out, wrt_logits != 0, scratch, (hipStream_t)stream);
+  return launch_status("gt_loss_ex");
+}
+
 // ------------------------------------------------------------------------------------ backward
 // FFN block backward.  In: dz (grad of the pre-norm sum of the layer's last norm) and its dropout-masked
 // copy dzm.  Out: dz_prev = LNbwd_prev(dhid W1 + dz) into (dzo, dzom) for the norm in front of the FFN.
@@ -1804,6 +1841,25 @@ extern "C" int gt_optimizer_step_ws(const gt_config* cfg, int algo, float* param
 }
 
 // ------------------------------------------------------------------------------------ fused train step
+// the update that ends a whole step (gt_train_step, gt_train_step_loss): the last launch of backward advanced the step counters already
+static int step_update(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe, const float* xin,
+                       float* hvo_out, float* ws, gt_step_state* state, gt_stream_t stream) {
+  PLayout P = param_layout(*cfg);
+  if (use_seq(*cfg)) {
+    // sequence-resident path: the update also writes the NEXT step's fragment-ordered weights (its caller may then pass
+    // GT_STEP_PACKS_CURRENT and the packing launch at the head of the step disappears)
+    if (algo != 0 && algo != 1) return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
+    if (algo == 1 && (!m || !v)) return gt_fail("gt_optimizer_step: adam needs m and v");
+    Ctx x;
+    if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
+    const SeqArgs a = mk_seq(x, pe, xin, hvo_out);
+    gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
+    gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)P.total);
+    gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 1, (hipStream_t)stream);
+    return launch_status("gt_train_step");
+  }
+  return optimizer_step_impl(algo, params, grads, m, v, P.total, state, 1, stream, 1, xchg_err(ws_layout(*cfg), ws), 1) ? -1 : 0;
+}
 extern "C" int gt_train_step(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe,
                              const float* xin, const float* y, float hit_loss_penalty, float* hvo_out, float* stats,
                              float* tgt_scratch, float* ws, gt_step_state* state, int skip_update, gt_stream_t stream) {
@@ -1852,23 +1908,46 @@ extern "C" int gt_train_step(const gt_config* cfg, int algo, float* params, floa
                                 skip_update == 0 ? state : nullptr, true);
   g_seq_b0_fused = false;                           // (consumed by that call; cleared here too in case it left early)
   if (brc) return -1;
-  if (!skip_update) {
-    PLayout P = param_layout(*cfg);
-    if (use_seq(*cfg)) {
-      // sequence-resident path: the update also writes the NEXT step's fragment-ordered weights (its caller may then pass
-      // GT_STEP_PACKS_CURRENT and the packing launch at the head of the step disappears)
-      if (algo != 0 && algo != 1) return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
-      if (algo == 1 && (!m || !v)) return gt_fail("gt_optimizer_step: adam needs m and v");
-      Ctx x;
-      if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
-      const SeqArgs a = mk_seq(x, pe, xin, hvo_out);
-      gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
-      gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)P.total);
-      gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 1, (hipStream_t)stream);
-      return launch_status("gt_train_step");
-    }
-    if (optimizer_step_impl(algo, params, grads, m, v, P.total, state, 1, stream, 1, xchg_err(W, ws), 1)) return -1;
+  if (!skip_update) return step_update(cfg, algo, params, grads, m, v, pe, xin, hvo_out, ws, state, stream);
+  return 0;
+}
+
+// gt_train_step with the loss as a launch of its own (include/groove_hip.h): no hand-off is set, so the forward runs exactly as gt_forward's
+// (the sequence-resident one does not go on into backward phase 0), loss_ex_kernel writes d loss / d logits into ws.dlogits, and backward
+// and update are gt_train_step's own calls with its own arguments.
+extern "C" int gt_train_step_loss(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe,
+                                  const float* xin, const float* y, const gt_loss_opts* lo, float* voice_stats, float* loss_scratch,
+                                  float* hvo_out, float* stats, float* tgt_scratch, float* ws, gt_step_state* state, int skip_update,
+                                  gt_stream_t stream) {
+  if (check_cfg(cfg)) return -1;
+  if (!y || !state) return gt_fail("gt_train_step_loss: y / state must not be NULL");
+  if (skip_update < 0 || skip_update > 7) return gt_fail("gt_train_step_loss: skip_update %d outside 0..7", skip_update);
+  const bool packs_current = (skip_update & GT_STEP_PACKS_CURRENT) != 0;
+  skip_update &= 3;
+  struct Handoffs { ~Handoffs() { g_seq_packs_current = false; g_seq_b0_fused = false; } } handoffs_guard;
+  const int M = cfg->batch * 32;
+  hipStream_t s = (hipStream_t)stream;
+  const float* tgt_in = nullptr;
+  if (cfg->n_dec_layers > 0) {
+    if (!tgt_scratch) return gt_fail("gt_train_step_loss: encoder-decoder model needs tgt_scratch");
+    tgt_in = tgt_scratch;
   }
+  g_seq_b0_fused = false;
+  if (skip_update == 3)                             // second half of a bucketed backward (tgt_scratch still holds the shifted y)
+    return backward_impl(cfg, params, grads, xin, tgt_in, hvo_out, nullptr, ws, state, 1, 1, stream, 2);
+  if (!stats || !hvo_out || !loss_scratch) return gt_fail("gt_train_step_loss: hvo_out / stats / loss_scratch must not be NULL");
+  if (!ws) return gt_fail("gt_train_step_loss: ws must not be NULL");
+  if (loss_opts_check("gt_train_step_loss", lo)) return -1;
+  if (tgt_in) gt_launch(shift_right_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), s, y, tgt_scratch, M * GT_TGT);
+  g_seq_packs_current = packs_current && use_seq(*cfg);
+  const int frc = gt_forward(cfg, params, pe, xin, tgt_in, hvo_out, ws, state, 1, stream);
+  g_seq_packs_current = false;
+  if (frc) return -1;
+  loss_ex_launch(*cfg, hvo_out, y, *lo, stats, voice_stats, ws + ws_layout(*cfg).dlogits, true, loss_scratch, s);
+  const int brc = backward_impl(cfg, params, grads, xin, tgt_in, hvo_out, nullptr, ws, state, 1, 1, stream, skip_update == 2 ? 1 : 0,
+                                skip_update == 0 ? state : nullptr, true);
+  if (brc) return -1;
+  if (!skip_update) return step_update(cfg, algo, params, grads, m, v, pe, xin, hvo_out, ws, state, stream);
   return 0;
 }
 

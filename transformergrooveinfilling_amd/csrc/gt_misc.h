@@ -518,6 +518,108 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
   dlogits[e] = g;
 }
 
+// ---- loss with options (gt_loss_ex, gt_train_step_loss; formulas: include/groove_hip.h) ----------------------------------------------
+// One workgroup per sequence: thread t < 288 owns (row t / 9, voice t % 9).  Its four quantities (bce, mse_v, mse_o, hit-accuracy
+// indicator) go to LDS, 36 threads add the 32 rows of one (quantity, voice) in row order and publish the sum (write-through), lane 0 of
+// the same wave takes the ticket behind them.  The last arriver adds the 36 columns over the workgroups -- wave w takes columns w, w + 5,
+// ..., lane l workgroups l, l + 64, ..., then the xor tree of gt_wave_sum -- clears the partials and re-arms the ticket: the order depends
+// on the grid alone, the scratch is all-zero between launches (the contract of grad_norm_kernel's).
+#define GT_LOSSX_Q 4
+#define GT_LOSSX_PART (GT_LOSSX_Q * GT_VOICES)   // partials per workgroup
+#define GT_LOSSX_THREADS 320                     // 288 elements, rounded up to whole waves
+
+// one (row, voice) element under gt_loss_opts; the option-free case is gt_loss_elem's arithmetic bit for bit in dh / dv / dO
+template <bool WRT_LOGITS>
+__device__ __forceinline__ void gt_loss_elem_ex(const float h, const float v, const float o, const float yh, const float yv, const float yo,
+                                                const gt_loss_opts& lo, const int c, const float invM, float& bce, float& mv, float& mo,
+                                                float& ok, float& dh, float& dv, float& dO) {
+  const float vw = lo.voice_weight[c], pw1 = lo.pos_weight[c] - 1.0f;
+  const float wh = vw * ((yh == 1.0f) ? 1.0f : lo.penalty_h), wvo = vw * ((yh == 1.0f) ? 1.0f : lo.penalty_vo);
+  const float sp = log1pf(expf(-fabsf(h)));
+  const float p = gt_sigmoid(h), sn = gt_sigmoid(-h);            // sn = 1 - p without the cancellation
+  const float bce0 = fmaxf(h, 0.f) - h * yh + sp + pw1 * yh * (sp + fmaxf(-h, 0.f));
+  float g = (p - yh) + pw1 * yh * (-sn);                         // d bce0 / d h
+  float f = 1.0f;
+  if (lo.focal_gamma != 0.0f) {
+    const float q = yh * sn + (1.0f - yh) * p;                   // 1 - p_t: both terms >= 0
+    float df = 0.0f;                                             // d f / d h = gamma f (dq/dh) / q, dq/dh = (1 - 2 yh) p sn
+    if (q > 0.0f) { f = powf(q, lo.focal_gamma); df = lo.focal_gamma * f * ((1.0f - 2.0f * yh) * (p * sn / q)); }
+    else f = 0.0f;
+    g = f * g + bce0 * df;
+  }
+  bce = wh * f * bce0;
+  mv = (v - yv) * (v - yv) * wvo;
+  mo = (o - yo) * (o - yo) * wvo;
+  ok = (((h > 0.f) ? 1.0f : 0.0f) == yh) ? 1.0f : 0.0f;
+  dv = 2.0f * (v - yv) * (lo.term_weight[1] * wvo) * invM; dO = 2.0f * (o - yo) * (lo.term_weight[2] * wvo) * invM;
+  if (WRT_LOGITS) { dv *= v * (1.0f - v); dO *= (0.5f - 2.0f * o * o); }
+  dh = g * (lo.term_weight[0] * wh) * invM;
+}
+
+template <bool WRT_LOGITS>
+__global__ __launch_bounds__(GT_LOSSX_THREADS) void loss_ex_kernel(const float* __restrict__ hvo, const float* __restrict__ y, const gt_loss_opts lo,
+                                                                   float* __restrict__ stats, float* __restrict__ voice_stats,
+                                                                   float* __restrict__ d_out, int M, float* __restrict__ partials,
+                                                                   unsigned* __restrict__ ticket) {
+  __shared__ float el[GT_LOSSX_Q][GT_T][GT_VOICES];
+  __shared__ float red[GT_LOSSX_PART];
+  __shared__ int is_last;
+  const int t = threadIdx.x;
+  const float invM = 1.0f / (float)M;
+  if (t < GT_T * GT_VOICES) {                                    // (grid = M / 32: every row exists)
+    const int r = t / GT_VOICES, c = t % GT_VOICES;
+    const size_t base = ((size_t)blockIdx.x * GT_T + r) * GT_TGT + c;
+    const float h = hvo[base], v = hvo[base + GT_VOICES], o = hvo[base + 2 * GT_VOICES];
+    const float yh = y[base], yv = y[base + GT_VOICES], yo = y[base + 2 * GT_VOICES];
+    float bce, mv, mo, ok, gh, gv, go;
+    gt_loss_elem_ex<WRT_LOGITS>(h, v, o, yh, yv, yo, lo, c, invM, bce, mv, mo, ok, gh, gv, go);
+    if (d_out) {
+      d_out[base] = gh;
+      d_out[base + GT_VOICES] = gv;
+      d_out[base + 2 * GT_VOICES] = go;
+    }
+    el[0][r][c] = bce; el[1][r][c] = mv; el[2][r][c] = mo; el[3][r][c] = ok;
+  }
+  __syncthreads();
+  if (t < GT_LOSSX_PART) {                                       // (quantity t / 9, voice t % 9): the 32 rows in order
+    const float* col = &el[0][0][0] + (t / GT_VOICES) * GT_T * GT_VOICES + t % GT_VOICES;
+    float s = 0.f;
+    for (int r = 0; r < GT_T; ++r) s += col[r * GT_VOICES];
+    gt_pub_store(partials + (size_t)blockIdx.x * GT_LOSSX_PART + t, s);
+  }
+  if (t == 0) {                                                  // (the 36 stores above are this wave's: drained with lane 0's own)
+    const unsigned tk = gt_pub_ticket(ticket);
+    is_last = (tk == gridDim.x - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!is_last) return;
+  {
+    const int w = t >> 6, l = t & 63;
+    for (int k = w; k < GT_LOSSX_PART; k += GT_LOSSX_THREADS / 64) {
+      float acc = 0.f;
+      for (unsigned bk = l; bk < gridDim.x; bk += 64) acc += gt_pub_load(partials + (size_t)bk * GT_LOSSX_PART + k);
+      acc = gt_wave_sum(acc);
+      if (l == 0) red[k] = acc;
+    }
+  }
+  __syncthreads();
+  for (unsigned i = t; i < gridDim.x * GT_LOSSX_PART; i += GT_LOSSX_THREADS) partials[i] = 0.f;
+  if (voice_stats != nullptr && t < GT_LOSSX_PART) voice_stats[t] = red[t] * invM;
+  if (t == 0) {
+    float s[GT_LOSSX_Q];
+    for (int q = 0; q < GT_LOSSX_Q; ++q) {
+      float a = 0.f;
+      for (int c = 0; c < GT_VOICES; ++c) a += red[q * GT_VOICES + c];
+      s[q] = a * invM;
+    }
+    stats[0] = (lo.term_weight[0] * s[0] + lo.term_weight[1] * s[1]) + lo.term_weight[2] * s[2];
+    stats[1] = s[3] * (1.0f / GT_VOICES);
+    stats[2] = 0.f;
+    stats[3] = s[0]; stats[4] = s[1]; stats[5] = s[2]; stats[6] = 0.f; stats[7] = 0.f;
+    *ticket = 0u;                                                // re-arm for the next call
+  }
+}
+
 // ---- optimizer: flat multi-tensor update (one launch for all 78+ tensors) -----------------------
 // zero_grads: the gradient is consumed and left zeroed (the next backward accumulates into it: no memset node).
 // (step / opt_step advance in step_inc_kernel: a last-workgroup ticket inside these kernels was measured SLOWER --

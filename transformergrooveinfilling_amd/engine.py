@@ -58,6 +58,8 @@ class _Slot:
         self.hvo = torch.zeros(B, 32, 27, **f32)
         self.tgt = torch.zeros(B, 32, 27, **f32)
         self.stats = torch.zeros(8, **f32)
+        self.voice_stats = None        # gt_train_step_loss's per-voice statistics and its scratch: made by the first step with loss
+        self.loss_scratch = None       # options (StepEngine._loss_ready); the scratch is zeroed once, every call leaves it zero
         self.idx = torch.zeros(B, dtype=torch.int64, device=eng.device)     # static batch indices of the indexed step
         self.graphs = {}               # step recipe -> captured hipGraph
         self.keep = {}                 # step recipe -> tensors whose raw pointers its graph holds
@@ -84,13 +86,15 @@ class _LossSlot:
         self.hvo = torch.zeros(B, 32, 27, **f32)
         self.y = torch.zeros(B, 32, 27, **f32)
         self.stats = torch.zeros(8, **f32)
+        self.voice_stats = None        # (as _Slot's)
+        self.loss_scratch = None
 
 
 class StepEngine:
     def __init__(self, d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_layers=0,
                  dropout=0.0, embedding_size_src=16, batch_size=None, optimizer="sgd", learning_rate=0.05,
                  hit_loss_penalty=1.0, seed=0, device="cuda", world_size=1, use_graph="auto", lib=None, precision="fp32",
-                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False):
+                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False, loss_opts=None):
         self.device = torch.device(device)
         # The only way onto host memory is an EXPLICITLY passed library object (tests hand in the host-emulator build of
         # the same kernel sources to cover the multi-rank step sequence over gloo); nothing in the package does that.
@@ -127,6 +131,12 @@ class StepEngine:
         # the fused one, unchanged.  Settable at any time, like max_grad_norm; see _opt_extras
         self.weight_decay, self.momentum, self.nesterov = weight_decay, momentum, nesterov
         self.decoupled = optimizer.lower() == "adamw"
+        # the loss's options beyond hit_loss_penalty (gt_loss_opts: separate hit and velocity / offset penalties, pos_weight, voice and term
+        # weights, focal modulation): None = off, the step is the fused one, unchanged; else the tuple make_loss_opts() returns -- every step
+        # then goes through gt_train_step_loss (the loss as a launch of its own) and fills the slot's voice_stats.  Settable at any time
+        self.loss_opts = loss_opts
+        self._lo_struct = (None, None)     # (tuple, its validated GtLossOpts)
+        self.last_voice_stats = None       # module API: the 36 per-voice statistics of the last calculate_loss with options
         self.mbuf = None               # SGD's momentum buffers, flat like the gradients (zeros when momentum is first non-zero: torch's first step)
         self.names = layout.param_names(d_model, dim_feedforward, embedding_size_src, num_encoder_layers, num_decoder_layers)
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -285,12 +295,56 @@ class StepEngine:
         self._pepoch += 1
         s.pack_epoch, self._pver = self._pepoch, self.params._version
 
+    # ---- the loss's options (gt_loss_opts): the loss as a launch of its own ----------------------------------------------------------------
+    def _loss_ready(self, s, opts=None):
+        """Before a call with loss options on slot s (train or loss slot), OUTSIDE any capture: the options validated, the slot's 36
+        per-voice statistics and the kernel's scratch allocated (zeroed once; every call leaves it zero).  -> the GtLossOpts"""
+        lo = self._loss_struct(opts)
+        if s.loss_scratch is None:
+            n = int(self.lib.cdll.gt_loss_scratch_floats(ctypes.byref(s.cfg)))
+            if n <= 0:
+                raise _lib.GrooveLibError("gt_loss_scratch_floats failed: %s" % self.lib.cdll.gt_last_error().decode())
+            s.voice_stats = torch.zeros(36, dtype=torch.float32, device=self.device)
+            s.loss_scratch = torch.zeros(n, dtype=torch.float32, device=self.device)
+        return lo
+
+    def make_loss_opts(self, vo_penalty=None, pos_weight=1.0, voice_weight=1.0, focal_gamma=0.0, term_weights=(1.0, 1.0, 1.0), hit_penalty=None):
+        """A value for self.loss_opts: the validated, hashable tuple of a gt_loss_opts (its 24 floats in field order).  hit_penalty /
+        vo_penalty default to the engine's hit_loss_penalty; pos_weight / voice_weight: a scalar or 9 values.  ValueError for a wrong length
+        or a value outside its range."""
+        ph = self.penalty if hit_penalty is None else hit_penalty
+        return _lib.loss_opts_tuple(_lib.make_loss_opts(ph, ph if vo_penalty is None else vo_penalty, pos_weight, voice_weight, focal_gamma,
+                                                        term_weights))
+
+    def _loss_struct(self, opts=None):
+        """the GtLossOpts of self.loss_opts (or of `opts`), validated once per value"""
+        t = self.loss_opts if opts is None else opts
+        if self._lo_struct[0] != t:
+            if not isinstance(t, tuple) or len(t) != 24:
+                raise ValueError("loss_opts must be None or the tuple StepEngine.make_loss_opts() returns, got %r" % (t,))
+            lo = _lib.make_loss_opts(t[0], t[1], t[2:11], t[11:20], t[20], t[21:24])
+            self._lo_struct = (_lib.loss_opts_tuple(lo), lo)
+            if self._lo_struct[0] != t:
+                raise ValueError("loss_opts holds values that are not fp32 numbers (use StepEngine.make_loss_opts): %r" % (t,))
+        return self._lo_struct[1]
+
+    @property
+    def _lk(self):
+        """what the loss's options add to a graph key (nothing while they are off: the keys are the fused step's own)"""
+        return () if self.loss_opts is None else (self.loss_opts,)
+
     def _enqueue_step(self, s, skip_update):
         flags = skip_update
         if skip_update != 3 and self._packs_current(s):
             flags |= 4                         # GT_STEP_PACKS_CURRENT: no packing launch at the head of the step
         if skip_update == 0:                   # whole step: its update writes the next step's copies into this slot
             self._note_fused_step(s)
+        if self.loss_opts is not None:
+            self.lib.call("gt_train_step_loss", ctypes.byref(s.cfg), self.algo, _ptr(self.params), _ptr(self.grads),
+                          _ptr(self.m), _ptr(self.v), _ptr(self.pe), _ptr(s.x), _ptr(s.y), ctypes.byref(self._loss_ready(s)),
+                          _ptr(s.voice_stats), _ptr(s.loss_scratch), _ptr(s.hvo), _ptr(s.stats), _ptr(s.tgt), _ptr(s.ws),
+                          _ptr(self.state), int(flags), self.stream)
+            return
         self.lib.call("gt_train_step", ctypes.byref(s.cfg), self.algo, _ptr(self.params), _ptr(self.grads),
                       _ptr(self.m), _ptr(self.v), _ptr(self.pe), _ptr(s.x), _ptr(s.y),
                       ctypes.c_float(self.penalty), _ptr(s.hvo), _ptr(s.stats), _ptr(s.tgt), _ptr(s.ws),
@@ -382,7 +436,7 @@ class StepEngine:
         two of the clip and the one of the optimizer's extras"""
         if self.use_graph == "auto":
             n = self.lib.cdll.gt_step_launches(ctypes.byref(s.cfg))
-            return not (0 < n and n + 1 + 2 * bool(clip) + bool(extras) <= EAGER_MAX_LAUNCHES)
+            return not (0 < n and n + 1 + 2 * bool(clip) + bool(extras) + (self.loss_opts is not None) <= EAGER_MAX_LAUNCHES)
         return bool(self.use_graph)
 
     _graph_for_clip = _graph_for_split         # (the clipped step without extras)
@@ -396,7 +450,7 @@ class StepEngine:
         if self.max_grad_norm is None and hp is None:
             return None
         mn = None if self.max_grad_norm is None else self._clip_norm(self.max_grad_norm)
-        key = (name + ("_clip" if mn is not None else "_prep"), self.algo, self.penalty) + (() if mn is None else (mn,)) + (hp or ()) + tail
+        key = (name + ("_clip" if mn is not None else "_prep"), self.algo, self.penalty) + self._lk + (() if mn is None else (mn,)) + (hp or ()) + tail
         return key, self._graph_for_split(s, mn is not None, hp is not None), mn
 
     def clip_grad_norm_(self, max_norm):
@@ -411,6 +465,9 @@ class StepEngine:
     def graph_for(self, s):
         """Does slot s replay captured graphs?  (use_graph True / False / "auto": by the step's launch count)"""
         if self.use_graph == "auto":
+            if self.loss_opts is not None:    # (the loss as a launch of its own: one more; not cached -- the options come and go)
+                n = self.lib.cdll.gt_step_launches(ctypes.byref(s.cfg))
+                return not (0 < n and n + 1 <= EAGER_MAX_LAUNCHES)
             if s.use_graph is None:
                 n = self.lib.cdll.gt_step_launches(ctypes.byref(s.cfg))
                 s.use_graph = not (0 < n <= EAGER_MAX_LAUNCHES)
@@ -590,6 +647,8 @@ class StepEngine:
         s = self.slot(x.shape[0] if x is not None else (B or self.B))
         self._train_B = s.B
         s.fwd_id += 1
+        if self.loss_opts is not None:
+            self._loss_ready(s)
         if x is not None:
             s.x.copy_(x, non_blocking=True)
         if y is not None:
@@ -606,7 +665,8 @@ class StepEngine:
         elif single:
             if self.graph_for(s):
                 self._note_fused_step(s)          # (a replay updates the parameters without running _enqueue_step)
-            self._replay(s, ("fused", self.algo, self.penalty), lambda: self._enqueue_step(s, 0))
+            key = ("fused", self.algo, self.penalty)
+            self._replay(s, key if self.loss_opts is None else key + self._lk, lambda: self._enqueue_step(s, 0))
         else:
             buckets = self.lib.grad_buckets(s.cfg) if self.overlap_allreduce else []
             two = len(buckets) == 2
@@ -641,7 +701,7 @@ class StepEngine:
                     if mn is not None:
                         self._clip_step(s, mn)
                     self.enqueue_update(slot=s)
-                key = ("dp_whole", self.algo, self.penalty, len(buckets)) + (() if mn is None else (mn,)) + (hp or ())
+                key = ("dp_whole", self.algo, self.penalty, len(buckets)) + self._lk + (() if mn is None else (mn,)) + (hp or ())
                 self._dp_whole(s, key, whole)
                 self.poll_exchange(s)
                 return s.stats
@@ -650,16 +710,16 @@ class StepEngine:
                 # all-reduce (RCCL stream) runs under graph B, the rest of backward.  The collectives stay OUTSIDE the
                 # captured graphs.  Sums over ranks; averaged by grad_scale inside the optimizer kernel.
                 (o0, c0), (o1, c1) = buckets
-                self._replay(s, ("bwd_top", self.algo, self.penalty), lambda: self._enqueue_step(s, 2))
+                self._replay(s, ("bwd_top", self.algo, self.penalty) + self._lk, lambda: self._enqueue_step(s, 2))
                 guard()
                 w0 = self._ar(self.grads[o0:o0 + c0], async_op=True)
-                if self.graph_for(s) and ("bwd_rest", self.algo, self.penalty) not in s.graphs:
+                if self.graph_for(s) and ("bwd_rest", self.algo, self.penalty) + self._lk not in s.graphs:
                     w0.wait()                     # first step only: the capture warm-up snapshots and restores the gradient buffer
-                self._replay(s, ("bwd_rest", self.algo, self.penalty), lambda: self._enqueue_step(s, 3), aux=True)
+                self._replay(s, ("bwd_rest", self.algo, self.penalty) + self._lk, lambda: self._enqueue_step(s, 3), aux=True)
                 w1 = self._ar(self.grads[o1:o1 + c1], async_op=True)
                 w0.wait(); w1.wait()
             else:
-                self._replay(s, ("fwdbwd", self.algo, self.penalty), lambda: self._enqueue_step(s, 1))
+                self._replay(s, ("fwdbwd", self.algo, self.penalty) + self._lk, lambda: self._enqueue_step(s, 1))
                 guard()
                 self._ar(self.grads)                         # RCCL sum over xGMI; averaged by grad_scale
             if on_grads is not None:
@@ -677,6 +737,8 @@ class StepEngine:
         s = self.slot(idx.shape[0])
         self._train_B = s.B
         s.fwd_id += 1
+        if self.loss_opts is not None:
+            self._loss_ready(s)
         s.idx.copy_(idx, non_blocking=True)
         key = (xs.data_ptr(), ys.data_ptr(), xs.shape[0])
 
@@ -695,7 +757,7 @@ class StepEngine:
                     self._note_fused_step(s)
                 self._replay(s, gkey, lambda: (gather(), self._split_step(s, mn)), graph=use)
             else:
-                gkey = ("fused_idx", self.algo, self.penalty) + key
+                gkey = ("fused_idx", self.algo, self.penalty) + self._lk + key
                 if self.graph_for(s):
                     self._note_fused_step(s)
                 self._replay(s, gkey, lambda: (gather(), self._enqueue_step(s, 0)))
@@ -751,10 +813,15 @@ class StepEngine:
             self._local_retry(s.ws, s.cfg, "an evaluation forward", run)
         return s.hvo
 
-    def loss(self, s, y, penalty, want_grad=True):
-        """calculate_loss on slot s's current hvo.  -> (stats, d_hvo) device tensors."""
+    def loss(self, s, y, penalty, want_grad=True, opts=None):
+        """calculate_loss on slot s's current hvo.  -> (stats, d_hvo) device tensors.  opts: a make_loss_opts() tuple -- the loss with
+        options (gt_loss_ex; `penalty` is then the tuple's own), which also fills s.voice_stats."""
         s.y.copy_(y)
         d_hvo = torch.empty_like(s.hvo) if want_grad else None
+        if opts is not None:
+            self.lib.call("gt_loss_ex", ctypes.byref(s.cfg), _ptr(s.hvo), _ptr(s.y), ctypes.byref(self._loss_ready(s, opts)), _ptr(s.stats),
+                          _ptr(s.voice_stats), _ptr(d_hvo), 0, _ptr(s.loss_scratch), self.stream)
+            return s.stats, d_hvo
         self.lib.call("gt_loss", ctypes.byref(s.cfg), _ptr(s.hvo), _ptr(s.y), ctypes.c_float(penalty), _ptr(s.stats),
                       _ptr(d_hvo), self.stream)
         return s.stats, d_hvo
@@ -1051,6 +1118,18 @@ class StepEngine:
             self._recover_exchange(s.ws, s.cfg, "a train step (some rank)")     # (ranks whose own word is clean fall back too: one schedule everywhere)
             return torch.full_like(s.stats, float("nan"))
         return t[:8] / self.world_size
+
+    def mean_voice_stats(self, s):
+        """The slot's 36 per-voice statistics of the last step with loss options (gt_loss_opts: [0..9) bce, [9..18) mse_v, [18..27) mse_o
+        shares, [27..36) hit accuracy per voice), averaged over the data-parallel ranks like mean_stats (every rank must call it)."""
+        if s.voice_stats is None:                  # (no step with options ran on this slot yet)
+            self._loss_ready(s, self.loss_opts or self.make_loss_opts())
+        if self.world_size == 1 or not self.reduce_stats:
+            return s.voice_stats
+        import torch.distributed as dist
+        t = s.voice_stats.clone()
+        dist.all_reduce(t)
+        return t / self.world_size
 
     def profile(self, steps):
         """Eager (no graph) pass of `steps` train steps with HIP events around every launch.

@@ -251,23 +251,43 @@ class _LossFn(torch.autograd.Function):
     """gt_loss: BCE(hits)*pen + MSE(vel)*pen + MSE(off)*pen, voices summed, (B,T) averaged; grad = gt_loss's d_hvo."""
 
     @staticmethod
-    def forward(ctx, hvo, y, penalty, engine):
+    def forward(ctx, hvo, y, penalty, engine, opts=None):
         s = engine.loss_slot(hvo.shape[0])
         s.hvo.copy_(hvo)
-        stats, d_hvo = engine.loss(s, y, penalty, want_grad=True)
+        stats, d_hvo = engine.loss(s, y, penalty, want_grad=True, opts=opts)
         ctx.save_for_backward(d_hvo)
         ctx.stats = stats.clone()
         return ctx.stats[0].clone()
 
     @staticmethod
     def backward(ctx, g):
-        return ctx.saved_tensors[0] * g, None, None, None
+        return ctx.saved_tensors[0] * g, None, None, None, None
 
 
-def calculate_loss(prediction, y, bce_fn, mse_fn, hit_loss_penalty):
+def _loss_opts_of(engine, bce_fn=None, hit_loss_penalty=None, voice_weight=None, focal_gamma=None, vo_penalty=None, term_weights=None):
+    """The StepEngine.loss_opts tuple for a bce_fn (its pos_weight: 1 or 9 elements) and calculate_loss's keyword options, or None when
+    none of them is set (the loss then runs exactly as before).  ValueError for a pos_weight of any other shape or a value out of range."""
+    pw = getattr(bce_fn, "pos_weight", None)
+    if pw is None and voice_weight is None and focal_gamma is None and vo_penalty is None and term_weights is None:
+        return None
+    if pw is not None:
+        pw = torch.as_tensor(pw).detach().float().cpu()
+        if pw.numel() not in (1, 9) or pw.dim() > 1:
+            raise ValueError("bce_fn.pos_weight must hold 1 or 9 elements (one per voice), got shape %s" % (tuple(pw.shape),))
+        pw = pw.reshape(-1).tolist()
+    return engine.make_loss_opts(vo_penalty=vo_penalty, pos_weight=1.0 if pw is None else pw, voice_weight=1.0 if voice_weight is None else voice_weight,
+                                 focal_gamma=0.0 if focal_gamma is None else focal_gamma,
+                                 term_weights=(1.0, 1.0, 1.0) if term_weights is None else term_weights, hit_penalty=hit_loss_penalty)
+
+
+def calculate_loss(prediction, y, bce_fn, mse_fn, hit_loss_penalty, *, voice_weight=None, focal_gamma=None, vo_penalty=None, term_weights=None):
     """loss_fn of train_loop (ref:train.py:201-203,213).  bce_fn / mse_fn must be the reference's
     BCEWithLogitsLoss / MSELoss(reduction='none') (ref:train.py:176-179): the fused kernel implements exactly
-    those.  Returns (loss tensor, hit_accuracy, hit_perplexity, bce_hits, mse_velocities, mse_offsets)."""
+    those.  Returns (loss tensor, hit_accuracy, hit_perplexity, bce_hits, mse_velocities, mse_offsets).
+    Not in the reference: bce_fn.pos_weight (1 or 9 elements) is honoured as torch does; voice_weight (9) multiplies a voice's three terms,
+    focal_gamma modulates the hit term by (1 - p_t)^gamma, vo_penalty is the penalty of the velocity / offset terms (default:
+    hit_loss_penalty), term_weights = (h, v, o) weights of the three terms in the loss (gt_loss_opts, include/groove_hip.h).  With any of
+    them the engine's `last_voice_stats` holds the 36 per-voice statistics of this call."""
     for fn, kind in ((bce_fn, torch.nn.BCEWithLogitsLoss), (mse_fn, torch.nn.MSELoss)):
         if fn is not None and (not isinstance(fn, kind) or fn.reduction != "none"):
             raise ValueError("calculate_loss expects %s(reduction='none') as in ref:train.py:176-179" % kind.__name__)
@@ -281,7 +301,10 @@ def calculate_loss(prediction, y, bce_fn, mse_fn, hit_loss_penalty):
         raise RuntimeError("no model initialised: call initialize_model() (or bind calculate_loss._engine) first")
     hvo = torch.cat([h, v, o], dim=-1).contiguous()
     y = y.to(hvo.device, torch.float32)
-    loss = _LossFn.apply(hvo, y, float(hit_loss_penalty), engine)
+    opts = _loss_opts_of(engine, bce_fn, float(hit_loss_penalty), voice_weight, focal_gamma, vo_penalty, term_weights)
+    loss = _LossFn.apply(hvo, y, float(hit_loss_penalty), engine, opts)
+    if opts is not None:
+        engine.last_voice_stats = engine.loss_slot(hvo.shape[0]).voice_stats.clone()
     st = engine.loss_slot(hvo.shape[0]).stats.tolist()       # ONE D2H of the stats struct (no 5-6 .item() syncs)
     return loss, st[1], math.exp(st[3]), st[3], st[4], st[5]
 
@@ -314,11 +337,14 @@ def shift_right(y):
     return torch.cat([torch.zeros_like(y[:, :1]), y[:, :-1]], dim=1)
 
 
-def _metrics_dict(prefix, st, clipped=False):
+def _metrics_dict(prefix, st, clipped=False, voice=None):
     d = {prefix + "loss": st[0], prefix + "hit_accuracy": st[1], prefix + "hit_perplexity": math.exp(st[3]),
          prefix + "bce_h": st[3], prefix + "mse_v": st[4], prefix + "mse_o": st[5]}
     if clipped:                                # a clipped step's gradient norm before clipping and the coefficient applied
         d[prefix + "grad_norm"], d[prefix + "clip_coef"] = st[6], st[7]
+    if voice is not None:                      # loss options on: each voice's share of bce_h and its hit accuracy (gt_loss_opts voice_stats)
+        for c in range(9):
+            d[prefix + "bce_h_voice%d" % c], d[prefix + "hit_accuracy_voice%d" % c] = voice[c], voice[27 + c]
     return d
 
 
@@ -359,14 +385,19 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 
 def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn, bce_fn, mse_fn, device,
                test_inputs=None, test_gt=None, validation_inputs=None, validation_gt=None, hit_loss_penalty=1,
-               save=False, save_dir=None, run_id=None, log_every=50, on_log=None, max_grad_norm=None):
+               save=False, save_dir=None, run_id=None, log_every=50, on_log=None, max_grad_norm=None, loss_options=None):
     """One epoch (ref:train.py:195-215).  For every (x, y, idx) batch: forward, calculate_loss, backward, update.
     When model, loss_fn and optimizer are this package's, the whole batch body is ONE captured hipGraph replay
     (gt_train_step) and metrics leave the GPU as one 8-float copy every `log_every` batches; any other
     combination takes the generic autograd path.  Returns the metrics of the last logged batch.
     max_grad_norm (not in the reference): clip the gradients to this global 2-norm between backward and update
-    (torch.nn.utils.clip_grad_norm_; inf = only measure); the logged records then carry train/grad_norm and train/clip_coef."""
+    (torch.nn.utils.clip_grad_norm_; inf = only measure); the logged records then carry train/grad_norm and train/clip_coef.
+    loss_options (not in the reference): calculate_loss's keyword options {voice_weight, focal_gamma, vo_penalty, term_weights}; with them,
+    or with a bce_fn that carries a pos_weight, every step computes the loss with options (StepEngine.loss_opts; the generic path and the
+    test / validation leg pass the same options to loss_fn) and the logged records carry train/bce_h_voice{0..8} and
+    train/hit_accuracy_voice{0..8}."""
     model = groove_transformer
+    lopts = dict(loss_options or {})
     _bind_engine(model)
     model.train()
     eng = getattr(model, "engine", None)
@@ -391,6 +422,14 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
     clip_keep = eng.max_grad_norm if fast else None
     if fast and clipped:
         eng.max_grad_norm = max_grad_norm      # the engine's clipped step (restored when the epoch ends)
+    lo_keep = eng.loss_opts if fast else None
+    lo_on = False                              # the fast path's loss runs with options
+    if fast:
+        lo = _loss_opts_of(eng, bce_fn, float(hit_loss_penalty), **lopts)
+        lo_on = lo is not None
+        if lo_on:
+            eng.loss_opts = lo                 # (restored when the epoch ends)
+    voice_of = lambda s_: eng.mean_voice_stats(s_).tolist() if lo_on else None
     last, stats = None, None
     n_batches = 0
     # a dataset resident in HBM hands over INDICES: the gather is the first launch of the step's graph
@@ -421,7 +460,7 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
                 stats = eng.train_step_indexed(dataloader.x, dataloader.y, _idx, on_grads=on_grads)
                 X = _idx                           # (only its length is used below)
                 if (batch + 1) % log_every == 0:
-                    last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped)
+                    last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped, voice_of(eng.slot(X.shape[0])))
                 if last is not None and (batch + 1) % log_every == 0:
                     rec = dict(last, epoch=epoch, batch=batch)
                     if _wandb_active():
@@ -434,11 +473,13 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
             if fast:
                 stats = eng.train_step(X, y, on_grads=on_grads)
                 if (batch + 1) % log_every == 0:
-                    last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped)
+                    last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped, voice_of(eng.slot(X.shape[0])))
             else:
                 opt.zero_grad()
                 pred = model(X) if encoder_only else model(X, shift_right(y))
-                out = loss_fn(pred, y, bce_fn, mse_fn, hit_loss_penalty)
+                if eng is not None:
+                    eng.last_voice_stats = None    # (calculate_loss leaves the per-voice statistics here when it ran with options)
+                out = loss_fn(pred, y, bce_fn, mse_fn, hit_loss_penalty, **lopts)
                 out[0].backward()
                 if world > 1:
                     if eng is not None:            # every .grad is a view of ONE flat buffer: one collective, not one per tensor
@@ -454,6 +495,10 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
                 opt.step()
                 last = {"train/loss": float(out[0]), "train/hit_accuracy": out[1], "train/hit_perplexity": out[2],
                         "train/bce_h": out[3], "train/mse_v": out[4], "train/mse_o": out[5]}
+                if eng is not None and eng.last_voice_stats is not None:
+                    vs = eng.last_voice_stats.tolist()
+                    for c in range(9):
+                        last["train/bce_h_voice%d" % c], last["train/hit_accuracy_voice%d" % c] = vs[c], vs[27 + c]
                 if clipped:
                     n32 = torch.tensor(float(norm), dtype=torch.float32)
                     coef = torch.clamp(max_grad_norm / (n32 + 1e-6), max=1.0) if max_grad_norm != float("inf") else torch.tensor(1.0)
@@ -467,8 +512,9 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
     finally:
         if fast:
             eng.max_grad_norm = clip_keep
+            eng.loss_opts = lo_keep
     if fast and stats is not None:
-        last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped)
+        last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped, voice_of(eng.slot(X.shape[0])))
     if isinstance(opt, GrooveAdam) and fast:
         for st in opt.state.values():
             st["step"] += n_batches
@@ -484,7 +530,7 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
         with torch.no_grad():
             xin, gt = xin.to(device, torch.float32), gt.to(device, torch.float32)
             pred = model(xin) if encoder_only else model(xin, shift_right(gt))
-            out = loss_fn(pred, gt, bce_fn, mse_fn, hit_loss_penalty)
+            out = loss_fn(pred, gt, bce_fn, mse_fn, hit_loss_penalty, **lopts)
         rec = {name + "loss": float(out[0]), name + "hit_accuracy": out[1], name + "hit_perplexity": out[2],
                name + "bce_h": out[3], name + "mse_v": out[4], name + "mse_o": out[5], "epoch": epoch}
         if _wandb_active():
