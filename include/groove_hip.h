@@ -289,6 +289,49 @@ int gt_voice_metrics(const float* hvo_pred, const float* hvo_gt, int64_t n_rows,
 int gt_gather_batch(const float* xs, const float* ys, const int64_t* idx, int64_t n_seq, int32_t batch, int32_t src_dim,
                     float* x, float* y, gt_stream_t stream);
 
+/* Replaces GrooveMidiDatasetInfillingSymbolic's pairing (ref:dataset.py:380-459) and the voice combinations it freezes per groove at
+ * preprocessing time (ref:utils.py:69-115) for the symbolic experiments (src_dim 27): the gather itself draws which voices to remove,
+ * afresh at every visit of a groove.  hvo_set (n_seq,32,27) FULL grooves; idx: batch int64 indices on the device, clamped like
+ * gt_gather_batch's.  x[b] = the groove with the hit / velocity / offset columns c, 9 + c, 18 + c zeroed for every removed voice c (the model's
+ * input), y[b] = the groove with those columns kept and all others zeroed (the target: the removed part; ref:evaluator.py:364-372 adds the
+ * two back together); kept values are bit copies.  removed (batch int32, or NULL): the removal bitmasks.  io is HOST memory, read when the
+ * call is enqueued (a captured graph keeps the values); state is a DEVICE pointer, required: seed_lo, seed_hi and step are read on the
+ * device, so a graph replay draws afresh once the update has advanced step.
+ * The draw for source index src (after clamping), in unsigned 32-bit wrap-around integers throughout -- no floating point:
+ *   voice c is active iff any of the 32 hit values hvo_set[src][t][c] is != 0; n_tot = active voices, n_act = active voices inside
+ *   voice_mask (the candidates, in ascending voice order); hi = min(max_remove, n_act, n_tot - 1) (the reference drops pairs whose input or
+ *   output would be empty); W_k = count_weight[k - min_remove] * C(n_act, k) for k in min_remove..hi, T = their sum.  T == 0: the sequence
+ *   is INELIGIBLE -- nothing is removed (x = the groove, y = zeros, removed = 0); hosts keep such sequences out of the index stream.
+ *   key = the dropout streams' key(site) above with site = GT_SITE_INFILL; r_j = fmix32(((uint32)(src * 16 + j) * 0x9E3779B1) ^ key).
+ *   Size: pick = ((uint64)r_0 * T) >> 32, k = the smallest size whose running sum of W exceeds pick.  Subset, by selection sampling: need = k,
+ *   left = n_act; candidate c is taken iff (((uint64)r_{1+c} * left) >> 32) < need; then left--, and need-- if taken.  Exactly k are taken.
+ * The draw depends on src, not on the batch position: two batch elements with the same src in one call get the SAME draw.
+ * Rejected before any launch: a NULL pointer other than removed, batch or n_seq <= 0, a zero voice_mask or one with bits >= 9,
+ * min_remove < 1, max_remove < min_remove, max_remove > 9, a weight outside 0..1024, all weights of the sizes min_remove..max_remove zero.
+ * One launch, no atomics; no host sync, no allocation; capturable. */
+#define GT_SITE_INFILL 2      /* free: sites 0, 1 and >= 16 are taken */
+typedef struct gt_infill_opts {
+  int32_t voice_mask;               /* bit c set: voice c may be removed (voices_params["voice_idx"]); non-zero, no bits >= 9 */
+  int32_t min_remove, max_remove;   /* 1 <= min_remove <= max_remove <= 9 */
+  int32_t count_weight[GT_VOICES];  /* count_weight[k - min_remove]: weight of EACH combination of size k (the reference's "prob");
+                                       0..1024; entries past max_remove - min_remove are ignored */
+} gt_infill_opts;
+int gt_gather_infill(const float* hvo_set, const int64_t* idx, int64_t n_seq, int32_t batch,
+                     const gt_infill_opts* io, const gt_step_state* state,
+                     float* x, float* y, int32_t* removed, gt_stream_t stream);
+/* Replaces add_removed_part_to_hvo (ref:evaluator.py:364-372): a prediction put back into the groove it was made from, so that what leaves
+ * the device is a complete pattern.  hvo_pred, hvo_in, hvo_out: (n_seq * 32, 27); hvo_out may alias hvo_pred.  removed (n_seq int32, or
+ * NULL): where voice c is outside removed[row / 32] the prediction's three values of that cell count as 0 -- the model may only fill what
+ * was removed.  Per cell (row, voice c) with the input's hit in_h:
+ *   mode 0 (the reference's arithmetic): h = in_h != 0 ? in_h : pred_h + in_h;  v = pred_v + in_v;  o = pred_o + in_o
+ *   mode 1: where in_h != 0 the input's (h, v, o) win whole; elsewhere (h, v, o) = pred.
+ * mode 1 with pred = y, in = x of gt_gather_infill and its removed gives back the source groove exactly (an HVO groove: velocity and
+ * offset are 0 wherever the hit is 0).
+ * Rejected before any launch: hvo_pred, hvo_in or hvo_out NULL, n_seq <= 0 or >= 2^26 (the grid's reach; hosts walk larger sets in
+ * chunks), a mode other than 0 or 1.  One elementwise launch. */
+int gt_infill_merge(const float* hvo_pred, const float* hvo_in, const int32_t* removed, int64_t n_seq,
+                    int32_t mode, float* hvo_out, gt_stream_t stream);
+
 /* Measurement aid (no reference counterpart): with profiling on, every kernel launch is bracketed by
  * HIP events on its own stream.  gt_profile_report synchronises and writes one text row per kernel
  * class: "label launches total_ms total_flops total_bytes".  Not graph-capturable while on. */

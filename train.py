@@ -9,7 +9,9 @@ The reference's own YAMLs (InfillingClosedHH / KicksAndSnares / Random ...) load
 Host side stays Python: data come from (a) the reference's processed dataset when its dataset modules are
 importable (`load_processed_dataset`, ref:train.py:153-155), (b) --data-npz FILE with arrays
 `inputs (N,32,S)` / `outputs (N,32,27)` (= the dataset's processed_inputs/processed_outputs tensors,
-ref:dataset.py:263-264), or (c) --synthetic N sequences from the SURVEY 8(d) generator.  W&B is optional.
+ref:dataset.py:263-264), (c) --synthetic N sequences from the SURVEY 8(d) generator, or (d), for the symbolic
+infilling experiments, --infill-npz FILE with ONE array `hvo (N,32,27)` of full grooves: the voices to remove are
+drawn on the device at every visit (--infill_voices / --infill_min / --infill_max / --infill_prob).  W&B is optional.
 Data-parallel: launch with torch.distributed.run, one process per GPU.
 """
 import argparse
@@ -90,6 +92,14 @@ def build_parser():
     p.add_argument("--focal_gamma", default=None, type=float, help="focal modulation (1 - p_t)^gamma of the hit term, 0..8")
     p.add_argument("--vo_penalty", default=None, type=float, help="penalty of the velocity / offset terms where there is no hit (default: hit_loss_penalty)")
     p.add_argument("--loss_weights", default=None, type=str, help="h,v,o: weights of the hit / velocity / offset terms in the loss")
+    # infilling pairs drawn on the device from full grooves (gt_gather_infill; the reference freezes a few voice combinations per groove at
+    # preprocessing time, ref:utils.py:69-115).  Also YAML keys of the same names (infill_npz, infill_voices, ...); symbolic experiments only
+    p.add_argument("--infill-npz", default=None, help="npz with hvo (N,32,27): full grooves; x / y pairs are drawn on the device every step")
+    p.add_argument("--infill_voices", default=None, type=str, help="comma list of the voices that may be removed (voices_params voice_idx; default 2: the closed hi-hat)")
+    p.add_argument("--infill_min", default=None, type=int, help="fewest voices removed per groove (default 1)")
+    p.add_argument("--infill_max", default=None, type=int, help="most voices removed per groove (default: infill_min)")
+    p.add_argument("--infill_prob", default=None, type=str,
+                   help="comma list of integer weights, one per size infill_min..infill_max: the weight of EACH combination of that size (default all 1)")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible weight gradients (gt_set_deterministic: no token split in the weight-gradient kernels; +9-30 %% step time)")
     return p
@@ -125,7 +135,48 @@ def load_hyperparameters(args):
     for k in ("focal_gamma", "vo_penalty"):
         v = hp.get(k, getattr(args, k))
         hp[k] = None if v is None else float(v)
+    # infilling from full grooves, the same way
+    hp["infill_npz"] = hp.get("infill_npz", args.infill_npz)
+    hp["infill"] = infill_setup(hp, args)
     return hp
+
+
+SYMBOLIC = ("InfillingClosedHH_Symbolic",)      # the experiments whose input is an HVO groove (embedding_size_src 27, ref:train.py:129-131)
+
+
+def _ints(v, what):
+    """None, a number, a list or a comma-separated string -> list of ints"""
+    if v is None:
+        return None
+    try:
+        v = [a for a in v.split(",")] if isinstance(v, str) else list(v) if hasattr(v, "__len__") else [v]
+        if any(float(a) != int(float(a)) for a in v):
+            raise ValueError(v)
+        return [int(float(a)) for a in v]
+    except ValueError:
+        raise SystemExit("--%s expects comma-separated integers, got %r" % (what, v))
+
+
+def infill_setup(hp, args):
+    """make_infill_opts keywords of the infill flags / YAML keys, or None while none is given.  SystemExit for a non-symbolic experiment:
+    only there is the input the groove itself."""
+    vals = {k: hp.get(k, getattr(args, k)) for k in ("infill_voices", "infill_min", "infill_max", "infill_prob")}
+    if hp.get("infill_npz") is None and all(v is None for v in vals.values()):
+        return None
+    if hp["experiment"] not in SYMBOLIC:
+        raise SystemExit("--infill-npz / --infill_* need a symbolic experiment (%s): the input of %r is not an HVO groove"
+                         % (", ".join(SYMBOLIC), hp["experiment"]))
+    if hp.get("infill_npz") is None:
+        raise SystemExit("--infill_voices / --infill_min / --infill_max / --infill_prob need --infill-npz FILE (full grooves)")
+    from transformergrooveinfilling_amd import _lib
+    lo = 1 if vals["infill_min"] is None else int(vals["infill_min"])
+    kw = dict(voices=_ints(vals["infill_voices"], "infill_voices") or [2], min_remove=lo,
+              max_remove=lo if vals["infill_max"] is None else int(vals["infill_max"]), prob=_ints(vals["infill_prob"], "infill_prob"))
+    try:
+        _lib.make_infill_opts(**kw)
+    except ValueError as e:
+        raise SystemExit("infill options: %s" % e)
+    return kw
 
 
 def _floats(v, counts, what):
@@ -198,10 +249,11 @@ def _flag(v):
     return bool(v) and str(v).lower() not in ("false", "0", "no", "none")
 
 
-def load_eval_sets(args, x, y, src_dim):
+def load_eval_sets(args, x, y, src_dim, pair=None):
     """{"Train_Set" | "Test_Set" | "Validation_Set": (inputs, gt)} for the sets the flags enable (ref:train.py:160-174: three
     pickled evaluators, each holding processed_inputs / processed_gt of a subset).  Sources: --eval-npz; else, with --synthetic,
-    seeded synthetic subsets; the train subset defaults to the head of the training tensors."""
+    seeded synthetic subsets; the train subset defaults to the head of the training tensors.  pair (infilling from full grooves): a set given
+    as ONE array <set>_hvo (n,32,27) is paired once through it -- a fixed state, so every epoch scores the same pairs."""
     import numpy as np
     import torch
     want = {"Train_Set": _flag(args.eval_train), "Test_Set": _flag(args.eval_test), "Validation_Set": _flag(args.eval_validation)}
@@ -214,6 +266,8 @@ def load_eval_sets(args, x, y, src_dim):
         k = key[name]
         if z is not None and k + "_inputs" in z.files:
             sets[name] = (torch.from_numpy(z[k + "_inputs"]).float(), torch.from_numpy(z[k + "_gt"]).float())
+        elif z is not None and pair is not None and k + "_hvo" in z.files:
+            sets[name] = pair(torch.from_numpy(z[k + "_hvo"]).float())
         elif name == "Train_Set":
             n = min(args.eval_size, len(x))
             sets[name] = (x[:n], y[:n])
@@ -255,17 +309,36 @@ def main(argv=None):
     if args.deterministic:
         model.engine.lib.cdll.gt_set_deterministic(1)
     parallel.broadcast_parameters(model.engine.params)
-    x, y = load_data(args, hp, params["model"]["embedding_size_src"])
+    infill_kw = hp.get("infill")
+    if infill_kw is not None:
+        # ONE array of full grooves; training draws the pair on the device at every visit.  What the host-side consumers below need as
+        # (x, y) tensors -- the train evaluation subset -- is paired ONCE with a fixed state (step 0, the run's seed) through the same call
+        import numpy as np
+        from transformergrooveinfilling_amd import infill
+        hvo = torch.from_numpy(np.load(hp["infill_npz"])["hvo"]).float()
+        if hvo.dim() != 3 or tuple(hvo.shape[1:]) != (32, 27):
+            raise SystemExit("--infill-npz: hvo must be (N,32,27), got %s" % (tuple(hvo.shape),))
+        if args.host_loader:
+            raise SystemExit("--infill-npz draws the pairs on the device: it cannot be combined with --host-loader")
+        x, y, _ = (t.cpu() for t in infill.pair_once(hvo[:args.eval_size], infill_kw, seed=args.seed, device=device))
+    else:
+        x, y = load_data(args, hp, params["model"]["embedding_size_src"])
 
     class _Triples(TensorDataset):           # the reference's dataset yields (x, y, idx) (ref:dataset.py:355-356)
         def __getitem__(self, i):
             return self.tensors[0][i], self.tensors[1][i], i
 
     ds = _Triples(x, y)
-    eval_sets = load_eval_sets(args, x, y, params["model"]["embedding_size_src"]) if rank == 0 else {}
+    pair = None
+    if infill_kw is not None:
+        pair = lambda h: tuple(t.cpu() for t in infill.pair_once(h, infill_kw, seed=args.seed, device=device)[:2])
+    eval_sets = load_eval_sets(args, x, y, params["model"]["embedding_size_src"], pair) if rank == 0 else {}
     test = eval_sets.get("Test_Set", (None, None))
     val = eval_sets.get("Validation_Set", (None, None))
-    if not args.host_loader:
+    if infill_kw is not None:
+        sampler = loader = parallel.DeviceBatchLoader.infilling(hvo, infill_kw, hp["batch_size"], device, rank, world, seed=args.seed)
+        ds = range(loader.n)                  # (only its length is used below: the grooves that can be paired)
+    elif not args.host_loader:
         # the whole dataset in HBM, batches gathered on the device
         sampler = loader = parallel.DeviceBatchLoader(x, y, hp["batch_size"], device, rank, world, seed=args.seed)
     elif world > 1:

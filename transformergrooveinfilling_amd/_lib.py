@@ -54,6 +54,12 @@ class GtLossOpts(ctypes.Structure):
                 ("voice_weight", ctypes.c_float * GT_VOICES), ("focal_gamma", ctypes.c_float), ("term_weight", ctypes.c_float * 3)]
 
 
+class GtInfillOpts(ctypes.Structure):
+    """gt_infill_opts: host memory, read when gt_gather_infill is enqueued"""
+    _fields_ = [("voice_mask", ctypes.c_int32), ("min_remove", ctypes.c_int32), ("max_remove", ctypes.c_int32),
+                ("count_weight", ctypes.c_int32 * GT_VOICES)]
+
+
 _vp, _cfgp = ctypes.c_void_p, ctypes.POINTER(GtConfig)
 _SIGS = {
     "gt_last_error": (ctypes.c_char_p, []),
@@ -96,6 +102,10 @@ _SIGS = {
     "gt_voice_metrics": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     # xs, ys, idx, n_seq, batch, src_dim, x, y, stream
     "gt_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
+    # hvo_set, idx, n_seq, batch, io, state, x, y, removed, stream
+    "gt_gather_infill": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(GtInfillOpts), _vp, _vp, _vp, _vp, _vp]),
+    # hvo_pred, hvo_in, removed, n_seq, mode, hvo_out, stream
+    "gt_infill_merge": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]),
     # cfg, algo, params, grads, m, v, ws, state, zero_grads, stream
     "gt_optimizer_step_ws": (ctypes.c_int, [_cfgp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "gt_grad_buckets": (ctypes.c_int, [_cfgp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
@@ -233,6 +243,47 @@ def make_loss_opts(penalty_h=1.0, penalty_vo=None, pos_weight=1.0, voice_weight=
     if not 0.0 <= g <= 8.0:
         raise ValueError("focal_gamma must lie in [0, 8], got %r" % (focal_gamma,))
     return GtLossOpts(ph, pvo, (ctypes.c_float * GT_VOICES)(*pw), (ctypes.c_float * GT_VOICES)(*vw), g, (ctypes.c_float * 3)(*tw))
+
+
+def _infill_struct(mask, lo, hi, w):
+    """the validated GtInfillOpts of (voice_mask, min_remove, max_remove, weights of the sizes min_remove..max_remove); ValueError for what
+    the library would refuse (include/groove_hip.h)"""
+    if not 0 < mask < (1 << GT_VOICES):
+        raise ValueError("infill voices must be a non-empty subset of 0..%d (mask 0x%x)" % (GT_VOICES - 1, mask))
+    if not 1 <= lo <= hi <= GT_VOICES:
+        raise ValueError("need 1 <= min_remove <= max_remove <= %d, got %d / %d" % (GT_VOICES, lo, hi))
+    if len(w) != hi - lo + 1:
+        raise ValueError("infill prob needs one weight per size %d..%d, got %d" % (lo, hi, len(w)))
+    if any(not 0 <= a <= 1024 for a in w) or not any(w):
+        raise ValueError("infill prob: integer weights in 0..1024, not all zero, got %r" % (w,))
+    return GtInfillOpts(mask, lo, hi, (ctypes.c_int32 * GT_VOICES)(*(list(w) + [0] * (GT_VOICES - len(w)))))
+
+
+def make_infill_opts(voices=(2,), min_remove=1, max_remove=None, prob=None):
+    """gt_infill_opts from the reference's voices_params (ref:utils.py:69-115): voices = "voice_idx" (the voices that may be removed),
+    min_remove / max_remove = "min_n_voices_to_remove" / "max_n_voices_to_remove" (default: min_remove), prob = the integer weight of each
+    combination of size min_remove, min_remove + 1, ... (default: all 1).  ValueError for what the library would refuse."""
+    voices = [int(v) for v in ([voices] if not hasattr(voices, "__len__") else voices)]
+    if any(not 0 <= v < GT_VOICES for v in voices):
+        raise ValueError("infill voices must be a non-empty subset of 0..%d, got %r" % (GT_VOICES - 1, voices))
+    lo = int(min_remove)
+    hi = lo if max_remove is None else int(max_remove)
+    w = [1] * max(0, hi - lo + 1) if prob is None else list([prob] if not hasattr(prob, "__len__") else prob)
+    if any(float(a) != int(a) for a in w):
+        raise ValueError("infill prob must be integer weights, got %r" % (prob,))
+    return _infill_struct(sum(1 << v for v in set(voices)), lo, hi, [int(a) for a in w])
+
+
+def infill_opts_tuple(io):
+    """the hashable form of a GtInfillOpts (StepEngine.infill_opts; part of a captured graph's key): its 12 integers in field order"""
+    return (io.voice_mask, io.min_remove, io.max_remove) + tuple(io.count_weight)
+
+
+def infill_opts_struct(t):
+    """the validated GtInfillOpts of such a tuple (weights past max_remove - min_remove are ignored, as by the library)"""
+    if not isinstance(t, tuple) or len(t) != 12 or any(int(a) != a for a in t):
+        raise ValueError("infill options must be the 12-integer tuple infill_opts_tuple() returns, got %r" % (t,))
+    return _infill_struct(int(t[0]), int(t[1]), int(t[2]), [int(a) for a in t[3:3 + max(0, int(t[2]) - int(t[1]) + 1)]])
 
 
 def torch_like(v):

@@ -2058,6 +2058,41 @@ extern "C" int gt_gather_batch(const float* xs, const float* ys, const int64_t* 
             (int)src_dim, n_seq);
   return launch_status("gt_gather_batch");
 }
+// The gather that also draws the infilling pair (gt_misc.h gather_infill_kernel).  The options are read from the host struct here and
+// baked into the launch, as gt_optimizer_prepare's hyper-parameters are; seed and step are read on the device.
+extern "C" int gt_gather_infill(const float* hvo_set, const int64_t* idx, int64_t n_seq, int32_t batch, const gt_infill_opts* io,
+                                const gt_step_state* state, float* x, float* y, int32_t* removed, gt_stream_t stream) {
+  if (!hvo_set || !idx || !io || !state || !x || !y) return gt_fail("gt_gather_infill: hvo_set / idx / io / state / x / y must not be NULL");
+  if (batch <= 0 || n_seq <= 0) return gt_fail("gt_gather_infill: batch / n_seq must be > 0");
+  if (io->voice_mask == 0 || (io->voice_mask & ~((1 << GT_VOICES) - 1)))
+    return gt_fail("gt_gather_infill: voice_mask 0x%x must name at least one of the %d voices and no other bit", (unsigned)io->voice_mask, GT_VOICES);
+  if (io->min_remove < 1 || io->max_remove < io->min_remove || io->max_remove > GT_VOICES)
+    return gt_fail("gt_gather_infill: need 1 <= min_remove (%d) <= max_remove (%d) <= %d", (int)io->min_remove, (int)io->max_remove, GT_VOICES);
+  InfillArgs a{io->voice_mask, io->min_remove, io->max_remove, {}};
+  bool any = false;
+  for (int k = 0; k <= io->max_remove - io->min_remove; ++k) {
+    if (io->count_weight[k] < 0 || io->count_weight[k] > 1024)
+      return gt_fail("gt_gather_infill: count_weight[%d] = %d outside 0..1024", k, (int)io->count_weight[k]);
+    a.weight[k] = io->count_weight[k];
+    any = any || io->count_weight[k] != 0;
+  }
+  if (!any) return gt_fail("gt_gather_infill: every count_weight of the sizes %d..%d is 0", (int)io->min_remove, (int)io->max_remove);
+  gt_prof_tag("gather_infill", 0.0, (double)batch * (3.0 * 32 * GT_TGT * 4.0 + 12.0));
+  gt_launch(gather_infill_kernel, dim3((unsigned)((batch + GT_GI_SEQ - 1) / GT_GI_SEQ)), dim3(GT_GI_THREADS), (hipStream_t)stream, hvo_set, idx,
+            x, y, (int*)removed, (int)batch, n_seq, a, state);
+  return launch_status("gt_gather_infill");
+}
+extern "C" int gt_infill_merge(const float* hvo_pred, const float* hvo_in, const int32_t* removed, int64_t n_seq, int32_t mode, float* hvo_out,
+                               gt_stream_t stream) {
+  if (!hvo_pred || !hvo_in || !hvo_out) return gt_fail("gt_infill_merge: hvo_pred / hvo_in / hvo_out must not be NULL");
+  if (n_seq <= 0 || n_seq >= (1ll << 26)) return gt_fail("gt_infill_merge: n_seq %lld out of range", (long long)n_seq);
+  if (mode != 0 && mode != 1) return gt_fail("gt_infill_merge: mode %d (0 = the reference's sum, 1 = the input's hits win whole)", (int)mode);
+  const int64_t cells = n_seq * 32 * GT_VOICES;
+  gt_prof_tag("infill_merge", 0.0, (double)n_seq * (3.0 * 32 * GT_TGT * 4.0 + (removed ? 4.0 : 0.0)));
+  gt_launch(infill_merge_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), (hipStream_t)stream, hvo_pred, hvo_in, (const int*)removed,
+            hvo_out, cells, (int)mode);
+  return launch_status("gt_infill_merge");
+}
 
 // ------------------------------------------------------------------------------------ predict
 // vs != nullptr (gt_predict_voices): the per-voice head kernel decides and writes prob_out; thres / use_thres are then unused

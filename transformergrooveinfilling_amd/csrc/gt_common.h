@@ -145,12 +145,15 @@ struct DropArgs {
   uint32_t thr;              // p * 2^24; 0 -> disabled
   float scale;               // 1/(1-p)
 };
+// key(site) of the spec: one per (seed, step, site); every stream hashes its element indices against it
+__host__ __device__ static inline uint32_t gt_site_key(const uint32_t seed_lo, const uint32_t seed_hi, const uint32_t step, const uint32_t site) {
+  uint32_t k = (seed_lo ^ gt_fmix32(step)) ^ (site * 0x9E3779B9u);
+  k = gt_fmix32(k) ^ seed_hi;
+  return gt_fmix32(k + 0x7F4A7C15u);
+}
 __device__ static inline uint32_t gt_drop_key(const DropArgs& d) {
   if (d.thr == 0u || d.st == nullptr) return 0u;
-  uint32_t s = d.st->seed_lo ^ gt_fmix32(d.st->step);
-  uint32_t k = s ^ (d.site * 0x9E3779B9u);
-  k = gt_fmix32(k) ^ d.st->seed_hi;
-  return gt_fmix32(k + 0x7F4A7C15u);
+  return gt_site_key(d.st->seed_lo, d.st->seed_hi, d.st->step, d.site);
 }
 // multiplier for element idx: scale if kept, 0 if dropped
 __device__ static inline float gt_drop_mul(const DropArgs& d, uint32_t key, uint32_t idx) {

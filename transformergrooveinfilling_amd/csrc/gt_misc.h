@@ -1043,6 +1043,121 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const float* __restri
   else        reinterpret_cast<float4*>(y)[(size_t)b * qy + (r - qx)] = reinterpret_cast<const float4*>(ys)[(size_t)src * qy + (r - qx)];
 }
 
+// ---- infilling pairs drawn in the gather (ref:dataset.py:380-459 GrooveMidiDatasetInfillingSymbolic, ref:utils.py:69-115: the voice
+// combinations the reference freezes at preprocessing time): x[b] = groove idx[b] with the drawn voices' h / v / o columns zeroed, y[b] = the
+// groove with every other voice zeroed, the draw keyed on the device-resident step state -- a graph replay draws afresh.  Spec of the draw:
+// include/groove_hip.h (integers only; tests/infill_ref.py restates it).  A workgroup holds GT_GI_SEQ whole sequences, 128 threads each: the
+// 864 floats of a sequence are staged in LDS with float4 loads, nine threads reduce the activity flags from the hit columns, one thread draws
+// the mask, all write x and y from the LDS copy with float4 stores (3456 bytes per sequence: every sequence starts 16-byte aligned).
+#define GT_GI_SEQ 2
+#define GT_GI_THREADS (GT_GI_SEQ * 128)
+#define GT_GI_Q (32 * GT_TGT / 4)                              // float4 per sequence (216)
+struct InfillArgs { int voice_mask, min_remove, max_remove; int weight[GT_VOICES]; };
+__device__ static inline uint32_t gt_binom(const int n, const int k) {          // C(n, k), 0 <= k, n <= 9
+  constexpr uint8_t tab[10][10] = {{1, 0, 0, 0, 0, 0, 0, 0, 0, 0},         {1, 1, 0, 0, 0, 0, 0, 0, 0, 0},        {1, 2, 1, 0, 0, 0, 0, 0, 0, 0},
+                                   {1, 3, 3, 1, 0, 0, 0, 0, 0, 0},         {1, 4, 6, 4, 1, 0, 0, 0, 0, 0},        {1, 5, 10, 10, 5, 1, 0, 0, 0, 0},
+                                   {1, 6, 15, 20, 15, 6, 1, 0, 0, 0},      {1, 7, 21, 35, 35, 21, 7, 1, 0, 0},    {1, 8, 28, 56, 70, 56, 28, 8, 1, 0},
+                                   {1, 9, 36, 84, 126, 126, 84, 36, 9, 1}};
+  return tab[n][k];
+}
+// the removal bitmask of source sequence `src` whose active voices are the bits of `active` (0: nothing is removed -- ineligible)
+__device__ static inline int gt_infill_draw(const InfillArgs& a, const int active, const int64_t src, const uint32_t key) {
+  int n_tot = 0, n_act = 0;
+#pragma unroll
+  for (int c = 0; c < GT_VOICES; ++c) { n_tot += (active >> c) & 1; n_act += ((active & a.voice_mask) >> c) & 1; }
+  int hi = a.max_remove < n_act ? a.max_remove : n_act;
+  hi = hi < n_tot - 1 ? hi : n_tot - 1;
+  uint32_t T = 0;
+  for (int k = a.min_remove; k <= hi; ++k) T += (uint32_t)a.weight[k - a.min_remove] * gt_binom(n_act, k);
+  if (T == 0u) return 0;
+  const uint32_t base = (uint32_t)(src * 16);
+  const uint32_t pick = (uint32_t)(((uint64_t)gt_fmix32((base * 0x9E3779B1u) ^ key) * T) >> 32);
+  int need = hi;
+  uint32_t run = 0;
+  for (int k = a.min_remove; k <= hi; ++k) {
+    run += (uint32_t)a.weight[k - a.min_remove] * gt_binom(n_act, k);
+    if (run > pick) { need = k; break; }
+  }
+  int left = n_act, removed = 0;
+  for (int c = 0; c < GT_VOICES; ++c) {                        // selection sampling over the candidates in ascending voice order
+    if (!((active & a.voice_mask) >> c & 1)) continue;
+    const uint32_t r = gt_fmix32(((base + 1u + (uint32_t)c) * 0x9E3779B1u) ^ key);
+    if ((uint32_t)(((uint64_t)r * (uint32_t)left) >> 32) < (uint32_t)need) { removed |= 1 << c; --need; }
+    --left;
+  }
+  return removed;
+}
+__global__ __launch_bounds__(GT_GI_THREADS) void gather_infill_kernel(const float* __restrict__ set, const int64_t* __restrict__ idx,
+                                                                      float* __restrict__ x, float* __restrict__ y, int* __restrict__ removed,
+                                                                      const int B, const int64_t n_seq, const InfillArgs a,
+                                                                      const gt_step_state* __restrict__ st) {
+  __shared__ __attribute__((aligned(16))) float sg[GT_GI_SEQ][32 * GT_TGT];
+  __shared__ int s_act[GT_GI_SEQ][GT_VOICES + 1];              // [9]: the drawn mask
+  const int g = threadIdx.x >> 7, t = threadIdx.x & 127;
+  const int b = blockIdx.x * GT_GI_SEQ + g;
+  const bool live = b < B;                                     // the last workgroup may hold fewer sequences (it still meets every barrier)
+  const uint32_t seed_lo = st->seed_lo, seed_hi = st->seed_hi, step = st->step;      // (uniform; in flight beside the index and the groove)
+  int64_t src = 0;
+  if (live) {
+    src = idx[b];
+    src = src < 0 ? 0 : (src >= n_seq ? n_seq - 1 : src);      // as gather_batch_kernel: a bad index must not read outside the dataset
+    const float4* in = reinterpret_cast<const float4*>(set) + (size_t)src * GT_GI_Q;
+    for (int q = t; q < GT_GI_Q; q += 128) reinterpret_cast<float4*>(sg[g])[q] = in[q];
+  }
+  __syncthreads();
+  if (live && t < GT_VOICES) {
+    int on = 0;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) on |= (sg[g][r * GT_TGT + t] != 0.0f) ? 1 : 0;
+    s_act[g][t] = on;
+  }
+  __syncthreads();
+  if (live && t == 0) {
+    int active = 0;
+#pragma unroll
+    for (int c = 0; c < GT_VOICES; ++c) active |= s_act[g][c] << c;
+    const int m = gt_infill_draw(a, active, src, gt_site_key(seed_lo, seed_hi, step, GT_SITE_INFILL));      // (the dropout streams' key)
+    s_act[g][GT_VOICES] = m;
+    if (removed) removed[b] = m;
+  }
+  __syncthreads();
+  if (!live) return;
+  const int m = s_act[g][GT_VOICES];
+  float4* ox = reinterpret_cast<float4*>(x) + (size_t)b * GT_GI_Q;
+  float4* oy = reinterpret_cast<float4*>(y) + (size_t)b * GT_GI_Q;
+  for (int q = t; q < GT_GI_Q; q += 128) {
+    const float4 v = reinterpret_cast<const float4*>(sg[g])[q];
+    const float e[4] = {v.x, v.y, v.z, v.w};
+    float ex[4], ey[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool out = (m >> (((4 * q + j) % GT_TGT) % GT_VOICES)) & 1;      // the element's voice was removed
+      ex[j] = out ? 0.0f : e[j];
+      ey[j] = out ? e[j] : 0.0f;
+    }
+    ox[q] = make_float4(ex[0], ex[1], ex[2], ex[3]);
+    oy[q] = make_float4(ey[0], ey[1], ey[2], ey[3]);
+  }
+}
+// ... and the way back (ref:evaluator.py:364-372): a prediction put into the groove it was made from, one thread per (row, voice) cell.
+// out may alias pred (a thread reads its three values before it writes them); masked: pred counts only in the voices of removed[row / 32].
+__global__ __launch_bounds__(256) void infill_merge_kernel(const float* pred, const float* __restrict__ in, const int* __restrict__ removed,
+                                                           float* out, const int64_t cells, const int mode) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= cells) return;
+  const int64_t row = e / GT_VOICES;
+  const int c = (int)(e % GT_VOICES);
+  const size_t o = (size_t)row * GT_TGT + c;
+  float ph = pred[o], pv = pred[o + GT_VOICES], po = pred[o + 2 * GT_VOICES];
+  const float ih = in[o], iv = in[o + GT_VOICES], io = in[o + 2 * GT_VOICES];
+  if (removed != nullptr && !((removed[row >> 5] >> c) & 1)) { ph = 0.0f; pv = 0.0f; po = 0.0f; }
+  const bool hit = ih != 0.0f;
+  float h, v, w;
+  if (mode == 0) { h = hit ? ih : ph + ih; v = pv + iv; w = po + io; }
+  else { h = hit ? ih : ph; v = hit ? iv : pv; w = hit ? io : po; }
+  out[o] = h; out[o + GT_VOICES] = v; out[o + 2 * GT_VOICES] = w;
+}
+
 // ---- bf16 shadows of the encoder layers' weight matrices (gt_config.precision = 1, GemmArgs::B16): for each of the four matrices W
 // (R x C) of every layer, W16 = bf16(W) in place order and W16T = bf16(W^T) -- the copy that turns a dgrad (dX = dY W) into the forward's
 // NT form.  One workgroup per 32 x 32 tile, transposed through LDS; both outputs leave as 64-byte row segments.  Runs at the head of

@@ -20,7 +20,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, layout
+from . import _lib, infill, layout
 
 ALGO = {"sgd": 0, "adam": 1, "adamw": 1}      # "adamw": adam with DECOUPLED weight decay (StepEngine.decoupled)
 OVERLAP_MIN_BYTES = 16 << 20
@@ -61,6 +61,7 @@ class _Slot:
         self.voice_stats = None        # gt_train_step_loss's per-voice statistics and its scratch: made by the first step with loss
         self.loss_scratch = None       # options (StepEngine._loss_ready); the scratch is zeroed once, every call leaves it zero
         self.idx = torch.zeros(B, dtype=torch.int64, device=eng.device)     # static batch indices of the indexed step
+        self.removed = None            # train_step_indexed_infill: the removal bitmasks of the step's B draws (int32; made by its first step)
         self.graphs = {}               # step recipe -> captured hipGraph
         self.keep = {}                 # step recipe -> tensors whose raw pointers its graph holds
         self.use_graph = None          # StepEngine.graph_for's decision for this slot (use_graph="auto")
@@ -94,7 +95,7 @@ class StepEngine:
     def __init__(self, d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_layers=0,
                  dropout=0.0, embedding_size_src=16, batch_size=None, optimizer="sgd", learning_rate=0.05,
                  hit_loss_penalty=1.0, seed=0, device="cuda", world_size=1, use_graph="auto", lib=None, precision="fp32",
-                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False, loss_opts=None):
+                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False, loss_opts=None, infill_opts=None):
         self.device = torch.device(device)
         # The only way onto host memory is an EXPLICITLY passed library object (tests hand in the host-emulator build of
         # the same kernel sources to cover the multi-rank step sequence over gloo); nothing in the package does that.
@@ -137,6 +138,10 @@ class StepEngine:
         self.loss_opts = loss_opts
         self._lo_struct = (None, None)     # (tuple, its validated GtLossOpts)
         self.last_voice_stats = None       # module API: the 36 per-voice statistics of the last calculate_loss with options
+        # the voice removal train_step_indexed_infill's gather draws (gt_infill_opts): None, or the tuple _lib.infill_opts_tuple() returns
+        # (make_infill_opts).  Settable at any time; part of that step's graph key
+        self.infill_opts = infill_opts
+        self._io_struct = (None, None)     # (tuple, its validated GtInfillOpts)
         self.mbuf = None               # SGD's momentum buffers, flat like the gradients (zeros when momentum is first non-zero: torch's first step)
         self.names = layout.param_names(d_model, dim_feedforward, embedding_size_src, num_encoder_layers, num_decoder_layers)
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -740,12 +745,16 @@ class StepEngine:
         if self.loss_opts is not None:
             self._loss_ready(s)
         s.idx.copy_(idx, non_blocking=True)
-        key = (xs.data_ptr(), ys.data_ptr(), xs.shape[0])
 
         def gather():
             self.lib.call("gt_gather_batch", _ptr(xs), _ptr(ys), _ptr(s.idx), ctypes.c_int64(xs.shape[0]), int(s.B),
                           int(self.dims["embedding_size_src"]), _ptr(s.x), _ptr(s.y), self.stream)
 
+        return self._indexed_step(s, (xs.data_ptr(), ys.data_ptr(), xs.shape[0]), gather, (xs, ys), on_grads)
+
+    def _indexed_step(self, s, key, gather, keep, on_grads):
+        """The step behind an indexed gather (train_step_indexed / train_step_indexed_infill): `gather` enqueues the launch that fills the
+        slot's static inputs, `key` is what it bakes into a captured graph, `keep` the resident tensors whose raw pointers that graph holds."""
         if on_grads is not None:
             gather()
             return self.train_step(B=s.B, on_grads=on_grads)
@@ -762,13 +771,48 @@ class StepEngine:
                     self._note_fused_step(s)
                 self._replay(s, gkey, lambda: (gather(), self._enqueue_step(s, 0)))
             if gkey in s.graphs:
-                s.keep[gkey] = (xs, ys)           # the captured graph holds their raw pointers: keep the tensors alive with it
+                s.keep[gkey] = keep               # the captured graph holds their raw pointers: keep the tensors alive with it
                 for k in [k for k in s.keep if k not in s.graphs]:
                     del s.keep[k]
             self.poll_exchange(s)
             return s.stats
         gather()
         return self.train_step(B=s.B)
+
+    def make_infill_opts(self, voices=(2,), min_remove=1, max_remove=None, prob=None):
+        """A value for self.infill_opts: the validated, hashable tuple of a gt_infill_opts (the reference's voices_params: voice_idx,
+        min / max_n_voices_to_remove, prob)."""
+        return _lib.infill_opts_tuple(_lib.make_infill_opts(voices, min_remove, max_remove, prob))
+
+    def train_step_indexed_infill(self, hvo_set, idx, on_grads=None):
+        """train_step_indexed for the symbolic infilling experiments: ONE resident tensor of FULL grooves hvo_set (N,32,27); the gather at the
+        head of the step's hipGraph (gt_gather_infill) draws, per batch element, the voices to remove (self.infill_opts) from the engine's own
+        device step state -- every replay draws afresh once the update has advanced the step -- and fills both static step inputs: x = the
+        groove without them, y = the removed part.  The slot's `removed` (int32, B) holds the bitmasks of the last step."""
+        if self.dims["embedding_size_src"] != _lib.GT_TGT:
+            raise ValueError("train_step_indexed_infill needs a symbolic model (embedding_size_src 27: the input is an HVO groove), got %d"
+                             % self.dims["embedding_size_src"])
+        if self.infill_opts is None:
+            raise ValueError("train_step_indexed_infill: set infill_opts first (StepEngine.make_infill_opts)")
+        infill.check_set(hvo_set)
+        s = self.slot(idx.shape[0])
+        self._train_B = s.B
+        s.fwd_id += 1
+        if self.loss_opts is not None:
+            self._loss_ready(s)
+        if s.removed is None:
+            s.removed = torch.zeros(s.B, dtype=torch.int32, device=self.device)
+        s.idx.copy_(idx, non_blocking=True)
+        if self._io_struct[0] != self.infill_opts:           # (validated once per value, like the loss's options)
+            self._io_struct = (self.infill_opts, _lib.infill_opts_struct(self.infill_opts))
+        io = self._io_struct[1]
+        key = ("infill",) + self.infill_opts + (hvo_set.data_ptr(), hvo_set.shape[0])
+
+        def gather():
+            self.lib.call("gt_gather_infill", _ptr(hvo_set), _ptr(s.idx), ctypes.c_int64(hvo_set.shape[0]), int(s.B), ctypes.byref(io),
+                          _ptr(self.state), _ptr(s.x), _ptr(s.y), _ptr(s.removed), self.stream)
+
+        return self._indexed_step(s, key, gather, (hvo_set,), on_grads)
 
     def voice_metrics(self, hvo_pred, hvo_gt):
         """Per-voice evaluation metrics of predictions against ground truth, both (N,32,27) HVO tensors on the device

@@ -94,15 +94,41 @@ class DeviceBatchLoader:
         materialised outside the step (the fast path);
       * iteration -> (x, y, idx) like the reference's dataset (two index_select gathers), for any other consumer.
     Under DP ragged tails are dropped (matched collectives); single-process keeps the last partial batch, as DataLoader's
-    default does."""
+    default does.
+    ``DeviceBatchLoader.infilling(hvo, infill_opts, ...)`` is the form for the symbolic infilling experiments: ONE resident tensor of full
+    grooves (N,32,27); the pair is drawn on the device (gt_gather_infill).  Only the grooves that can be paired (infill.infill_eligible) are
+    permuted; ``index_batches()`` is as above (train_loop hands the indices to StepEngine.train_step_indexed_infill), iteration yields
+    (x, y, idx) drawn with this loader's own step state (the loader's seed, step = batches yielded so far)."""
 
     def __init__(self, x, y, batch_size, device, rank=0, world=1, seed=0):
-        self.x = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
-        self.y = torch.as_tensor(y, dtype=torch.float32).to(device).contiguous()
-        assert self.x.shape[0] == self.y.shape[0]
-        self.n, self.bs, self.rank, self.world, self.seed = int(self.x.shape[0]), int(batch_size), rank, world, seed
+        x = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
+        y = torch.as_tensor(y, dtype=torch.float32).to(device).contiguous()
+        assert x.shape[0] == y.shape[0]
+        self._setup(x, y, batch_size, device, rank, world, seed)
+
+    def _setup(self, x, y, batch_size, device, rank, world, seed, infill_opts=None, pool=None, lib=None):
+        """every field of either form.  pool: the indices a permutation draws from (None: all of x); infill_opts / lib: the infilling form"""
+        self.x, self.y = x, y
+        self.infill_opts, self.pool = infill_opts, pool
+        self.n = int(x.shape[0] if pool is None else pool.numel())
+        self.bs, self.rank, self.world, self.seed = int(batch_size), rank, world, seed
         self.device, self.epoch = device, 0
         self.batch_size = self.bs
+        self._lib, self._state, self._drawn = lib, None, 0      # iteration of the infilling form: its library, device step state, batches drawn
+
+    @classmethod
+    def infilling(cls, hvo, infill_opts, batch_size, device, rank=0, world=1, seed=0, lib=None):
+        """The loader over ONE tensor of full grooves (N,32,27) plus infill options (anything infill.as_opts takes).  lib: the library
+        iteration calls (default: the process-wide HIP library; index_batches() needs none)."""
+        from . import infill
+        x = torch.as_tensor(hvo, dtype=torch.float32).to(device).contiguous()
+        io = infill.as_opts(infill_opts)
+        pool = infill.infill_eligible(x, io).cpu()
+        if pool.numel() == 0:
+            raise ValueError("no groove of the set can be paired with these infill options (none has a removable voice beside another active one)")
+        self = cls.__new__(cls)
+        self._setup(x, None, batch_size, device, rank, world, seed, io, pool, lib)
+        return self
 
     def set_epoch(self, epoch):
         self.epoch = epoch
@@ -116,11 +142,24 @@ class DeviceBatchLoader:
         g = torch.Generator()
         g.manual_seed(self.seed * 1000003 + self.epoch)
         perm = torch.randperm(self.n, generator=g)                      # host generator: identical on every rank and platform
+        if self.pool is not None:
+            perm = self.pool[perm]                                      # (infilling: the eligible grooves only)
         per_rank = self.n // self.world
         mine = perm[self.rank: per_rank * self.world: self.world].to(self.device)   # ONE small H2D copy per epoch
         for i in range(len(self)):
             yield mine[i * self.bs:(i + 1) * self.bs]
 
     def __iter__(self):
+        if self.infill_opts is not None:
+            from . import infill
+            if self._state is None:
+                self._state = infill.make_state(self.seed, 0, self.x.device)
+            for idx in self.index_batches():
+                step = torch.tensor([self._drawn & 0x7FFFFFFF], dtype=torch.int32).view(torch.uint8)
+                self._state[8:12].copy_(step, non_blocking=True)          # gt_step_state.step: a fresh draw per batch
+                self._drawn += 1
+                x, y, _ = infill.gather(self.x, idx, self.infill_opts, self._state, self._lib)
+                yield x, y, idx
+            return
         for idx in self.index_batches():
             yield self.x.index_select(0, idx), self.y.index_select(0, idx), idx

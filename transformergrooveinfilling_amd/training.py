@@ -13,6 +13,7 @@ import re
 
 import torch
 
+from . import _lib
 from .model import GrooveTransformer, GrooveTransformerEncoder, _GrooveBase, engine_of
 
 try:                                    # Weights & Biases is optional here (ref:train.py:106-113,150,252)
@@ -436,6 +437,10 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
     indexed = fast and hasattr(dataloader, "index_batches") and getattr(dataloader, "x", None) is not None \
         and dataloader.x.device == eng.device
     batches = ((None, None, i) for i in dataloader.index_batches()) if indexed else dataloader
+    # ... or ONE resident tensor of full grooves: the gather draws the voices to remove (gt_gather_infill) with the loader's options
+    infilling = indexed and getattr(dataloader, "infill_opts", None) is not None
+    if infilling:
+        eng.infill_opts = _lib.infill_opts_tuple(dataloader.infill_opts)
     # wandb.watch(model, log_freq=1000) (ref:train.py:150) hooks the Parameters' gradients; the fused step never materialises a .grad
     # autograd could hook (it consumes and re-zeroes the flat gradient buffer inside its last launch).  Equivalent: every
     # model.watch_log_freq batches (0 = never) the step runs split -- backward, gradients visible, update -- and their histograms
@@ -456,8 +461,11 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
             n_batches += 1
             model._watch_step = getattr(model, "_watch_step", 0) + 1
             on_grads = watch_cb if (watch and model._watch_step % watch == 0) else None
-            if indexed:
+            if infilling:
+                stats = eng.train_step_indexed_infill(dataloader.x, _idx, on_grads=on_grads)
+            elif indexed:
                 stats = eng.train_step_indexed(dataloader.x, dataloader.y, _idx, on_grads=on_grads)
+            if indexed:
                 X = _idx                           # (only its length is used below)
                 if (batch + 1) % log_every == 0:
                     last = _metrics_dict("train/", eng.mean_stats(eng.slot(X.shape[0])).tolist(), clipped, voice_of(eng.slot(X.shape[0])))
