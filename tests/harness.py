@@ -123,12 +123,13 @@ class Runner:
                       self.d_hvo.ptr if want_grad else None, self.stream)
         return self.stats.numpy().copy(), self.d_hvo.numpy().reshape(self.B, 32, 27).copy()
 
-    def backward(self, d_hvo=None, train=False):
+    def backward(self, d_hvo=None, train=False, accumulate=0):
+        """accumulate: gt_backward's argument -- 1 adds onto what self.grads holds (the nn.Module path), 0 overwrites it"""
         if d_hvo is not None:
             self.d_hvo = self.Buf(np.asarray(d_hvo, np.float32).reshape(self.M, 27))
         self.lib.call("gt_backward", ctypes.byref(self.c), self.params.ptr, self.grads.ptr, self.x.ptr,
                       self.tgt_in.ptr if self.tgt_in else None, self.hvo.ptr, self.d_hvo.ptr, self.ws.ptr, self.state.ptr,
-                      int(train), 0, self.stream)
+                      int(train), int(accumulate), self.stream)
         self._grads_dirty = True
         return self.unflatten(self.grads.numpy())
 
@@ -246,6 +247,39 @@ def parse_dispatch(stderr_text):
         assert len(kv) % 2 == 0 and tuple(kv[0::2]) == DISPATCH_KEYS[fam], ln
         out.append((fam, {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in zip(kv[0::2], kv[1::2])}))
     return out
+
+
+def trace_dispatch(fn):
+    """fn() with GT_TRACE_DISPATCH=1 and file descriptor 2 sent to a temporary file (the library writes the lines with fprintf: below
+    sys.stderr) -- works under pytest's capture and in a plain subprocess alike.  Returns (fn's result, parsed [dispatch] lines); whatever
+    else arrived on stderr meanwhile is passed on, the trace lines too when fn raises."""
+    import tempfile
+    sys.stderr.flush()
+    saved = os.dup(2)
+    old = os.environ.get("GT_TRACE_DISPATCH")
+    text, failed = "", True
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        os.dup2(tmp.fileno(), 2)
+        os.environ["GT_TRACE_DISPATCH"] = "1"
+        try:
+            out = fn()
+            failed = False
+        finally:
+            if old is None:
+                del os.environ["GT_TRACE_DISPATCH"]
+            else:
+                os.environ["GT_TRACE_DISPATCH"] = old
+            sys.stderr.flush()
+            os.dup2(saved, 2)
+            os.close(saved)
+            tmp.seek(0)
+            text = tmp.read().decode(errors="replace")
+            rest = "".join(ln + "\n" for ln in text.splitlines() if failed or not ln.startswith("[dispatch] "))
+            if rest:
+                sys.stderr.write(rest)
+    trace = parse_dispatch(text)
+    assert trace, "no [dispatch] line: the trace is off"
+    return out, trace
 
 
 def dispatched(trace, family, **kv):

@@ -17,7 +17,9 @@ from oracle import numpy_groove as ng
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 OUT_TOL, GRAD_TOL = 2e-5, 2e-4
 # the last check's largest error / bar ratios ("out": outputs against OUT_TOL, "grad": the worst gradient tensor against GRAD_TOL, "update":
-# check_update's ratio, "bf16_op": the worst per-operation ratio of check_ops_bf16, "bf16_e2e": the end-to-end sanity bound) -- figures for reports (profiles/dispatch_edges.txt); nothing asserts on them
+# check_update's ratio, "bf16_op": the worst per-operation ratio of check_ops_bf16, "bf16_e2e": the end-to-end sanity bound,
+# "probe": the worst tensor of the worst probe of check_grad_probes against GRAD_TOL, "accumulate": check_accumulate's worst element) -- figures for
+# reports (profiles/dispatch_edges.txt, profiles/grad_probes.txt); nothing asserts on them
 FIGURES = {}
 
 
@@ -55,18 +57,10 @@ def adopt_device_kinks(r, C, cfg):
     return adopted
 
 
-def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=True, flags=0):
-    """forward + loss + backward (+ saved activations) against the fp64 numpy oracle."""
-    cfg = dict(cfg, dropout=p)
-    P = ng.init_params(cfg, seed=seed, perturb=0.05)
-    x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
-    Ld = cfg.get("num_decoder_layers", 0)
-    tgt = shift_right(y) if Ld else None
-    rng = (1234, 99, 7)
-    r = Runner(cfg, B, backend, rng=rng, seq=seq, flags=flags)
-    r.set_params(P)
-    hvo = r.forward(x, tgt, train=p > 0)
-    (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=rng if p > 0 else None, dtype=np.float64)
+def _check_forward_and_loss(r, hvo, hvo_ref, C, y, penalty, check_ws):
+    """The forward half of check_step: outputs, saved activations, loss statistics and d loss / d hvo of Runner r (after r.forward) against
+    the fp64 oracle's (h, v, o) and cache C.  Clears FIGURES and records "out"; returns the oracle's (dh, dv, do)."""
+    h, v, o = hvo_ref
     ref = np.concatenate([h, v, o], -1)
     FIGURES.clear()
     FIGURES["out"] = float(np.abs(hvo - ref).max() / OUT_TOL)
@@ -85,6 +79,22 @@ def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=
     near = int((np.abs(h) < 1e-4).sum())
     assert abs(stats[1] - rstats[1]) <= (near + 0.01) / h.size + 1e-6, (stats[1], rstats[1], near)
     assert rel_err(d_hvo, np.concatenate(dpred, -1)) < 1e-5
+    return dpred
+
+
+def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=True, flags=0):
+    """forward + loss + backward (+ saved activations) against the fp64 numpy oracle."""
+    cfg = dict(cfg, dropout=p)
+    P = ng.init_params(cfg, seed=seed, perturb=0.05)
+    x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
+    Ld = cfg.get("num_decoder_layers", 0)
+    tgt = shift_right(y) if Ld else None
+    rng = (1234, 99, 7)
+    r = Runner(cfg, B, backend, rng=rng, seq=seq, flags=flags)
+    r.set_params(P)
+    hvo = r.forward(x, tgt, train=p > 0)
+    (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=rng if p > 0 else None, dtype=np.float64)
+    dpred = _check_forward_and_loss(r, hvo, (h, v, o), C, y, penalty, check_ws)
     G = r.backward(train=p > 0)
     adopted = adopt_device_kinks(r, C, cfg)
     assert adopted <= kink_bound(r, cfg), adopted
@@ -98,6 +108,261 @@ def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=
         FIGURES["grad"] = max(FIGURES.get("grad", 0.0), err / GRAD_TOL)
         assert err < GRAD_TOL, (k, err)
     return r, P, G, Gr
+
+
+# ---- each sequence's share of the parameter gradients (check_grad_probes), accumulation (check_accumulate) ---------------------------------
+# check_step's gradient bar is relative to the WHOLE batch's tensor, a sum over all 32 B tokens: one sequence's share of it is 1.4e-2 ...
+# 2e-2 of the tensor's largest entry at 64 sequences and 3e-3 ... 6e-3 at 256, one token row's 2e-4 ... 3e-3 -- a sequence counted at 98 %,
+# or a row lost at a partition's boundary, passes it.  gt_backward is linear in d_hvo and sequences meet only in the parameter gradients,
+# so ONE forward and one backward per PROBE -- a d_hvo that is zero outside one sequence, or one token row -- puts the same bar,
+# GRAD_TOL, on that sequence's (row's) contribution alone.  The oracle's own fp32 run differs from its fp64 run by <= 8.3e-7 on such
+# probes (d128 B 17, d32 encoder-decoder B 5, d256 B 64, d32 / H16 B 16): the bar keeps 240 x over the reference.
+PROBE_FLOOR = 1e-3               # every oracle tensor of every probe must reach this (the smallest seen: 1.5e-2): the 1e-5 floor never engages
+MAX_PROBES = 12
+
+
+def gradient_gaps(r):
+    """the flat gradient buffer's elements outside every tensor of the layout: alignment gaps and the guard element (the last one)"""
+    inside = np.zeros(r.total, bool)
+    for off, size, _, _ in r.entries:
+        inside[off:off + size] = True
+    assert not inside[-1], "the guard element lies inside a tensor"
+    return ~inside
+
+
+def assert_gaps_zero(r, gaps, tag):
+    """gt_clip_grad_norm sums the whole buffer: whatever a backward leaves outside the tensors counts as gradient"""
+    g = r.grads.numpy()
+    bad = np.flatnonzero(g[gaps] != 0)
+    assert bad.size == 0, "%s: %d non-zero elements outside the gradient tensors, first at flat index %d" % (tag, bad.size, np.flatnonzero(gaps)[bad[0]])
+
+
+def probe_d_hvo(B, place, seed):
+    """d loss / d hvo of one probe.  place = ("seq", s): sequence s; ("row", t): token row t of the 32 B (sequence t // 32, step t % 32).
+    U(-1, 1) in float32 inside, exactly zero outside."""
+    d = np.zeros((B * 32, 27), np.float32)
+    rnd = np.random.default_rng(seed)
+    kind, at = place
+    if kind == "seq":
+        assert 0 <= at < B, place
+        d[32 * at:32 * at + 32] = rnd.uniform(-1, 1, (32, 27)).astype(np.float32)
+    else:
+        assert kind == "row" and 0 <= at < 32 * B, place
+        d[at] = rnd.uniform(-1, 1, 27).astype(np.float32)
+    return d.reshape(B, 32, 27)
+
+
+def probe_places(B, token_rows=(), split_rows=True, limit=None):
+    """Where the token dimension of the weight gradients is cut.  Always sequences 0 and B - 1 and the last row of the batch; split_rows:
+    rows 15 and 16 of sequence B // 2 (the two 16-row halves of the two-workgroups-per-sequence kernels); token_rows: the caller's
+    boundaries (chunk ends from the dispatch trace, ride_last_k, the tail's chunk), in the caller's order, rows outside the batch dropped.
+    No place twice, at most limit (MAX_PROBES) of them."""
+    M = 32 * B
+    places = [("seq", 0), ("seq", B - 1)]
+    if split_rows:
+        places += [("row", 32 * (B // 2) + 15), ("row", 32 * (B // 2) + 16)]
+    places.append(("row", M - 1))
+    places += [("row", int(t)) for t in token_rows if 0 <= t < M]
+    out = []
+    for pl in places:
+        if pl not in out:
+            out.append(pl)
+    return out[:min(limit or MAX_PROBES, MAX_PROBES)]
+
+
+def chunk_rows(trace, M):
+    """token rows either side of the first chunk boundary, and the first row of the last chunk, for every distinct k_chunk among the
+    trace's queued weight-gradient problems over M tokens (family "wgrad_queue"); the chunk length of the largest gradient first"""
+    size = {}
+    for d in harness.dispatched(trace, "wgrad_queue"):
+        if d["K"] == M and d["k_chunk"] < M:
+            size[d["k_chunk"]] = max(size.get(d["k_chunk"], 0), d["M"] * d["N"])
+    rows = []
+    for kc in sorted(size, key=lambda k: (-size[k], k)):
+        rows += [kc - 1, kc, (M - 1) // kc * kc]
+    return rows
+
+
+def rider_rows(M):
+    """the rider path's cuts (csrc/groove_hip.hip backward_impl, csrc/gt_seq_wg.h seq_wg_phase_unit, restated): the last phase's riders take
+    the tokens [0, ride_last_k) and the tail launch the rest; the tail's own problems are cut into ks = 2 chunks of `per` tokens"""
+    ride_last_k = (M * 50 // 100) // 64 * 64
+    ks = 2
+    per = ((M // 8 + ks - 1) // ks) * 8
+    return [ride_last_k - 1, ride_last_k, per - 1, per]
+
+
+def probe_compare(G, Gr, place):
+    """One probe's gradients G (name -> array) against the oracle's Gr: max |G - Gr| / max(max |Gr|, 1e-5) < GRAD_TOL per tensor -- check_step's
+    bar, relative to THIS probe's tensor.  AssertionError naming the probe, the tensor and the element; ValueError when an oracle tensor
+    stays under PROBE_FLOOR (the probe says nothing about that tensor: take another probe seed).  Returns the worst err / GRAD_TOL."""
+    assert set(G) == set(Gr), sorted(set(G) ^ set(Gr))
+    worst = 0.0
+    for k in Gr:
+        ref = np.asarray(Gr[k], np.float64)
+        top = float(np.abs(ref).max())
+        if top < PROBE_FLOOR:
+            raise ValueError("probe %s: max |G_ref| of %s is %.3g < %g -- pick another probe seed" % (place, k, top, PROBE_FLOOR))
+        diff = np.abs(np.asarray(G[k], np.float64).reshape(ref.shape) - ref)
+        err = float(diff.max() / max(top, 1e-5))
+        worst = max(worst, err / GRAD_TOL)
+        if not err < GRAD_TOL:
+            i = tuple(int(j) for j in np.unravel_index(int(np.argmax(diff)), ref.shape))
+            raise AssertionError("probe %s: %s element %s: device %.9g oracle %.9g, error %.3g of the probe's max |G_ref| %.3g (bar %g)"
+                                 % (place, k, i, np.asarray(G[k]).reshape(ref.shape)[i], ref[i], err, top, GRAD_TOL))
+    return worst
+
+
+def _deterministic(lib, on):
+    import contextlib
+
+    @contextlib.contextmanager
+    def cm():
+        if on:
+            lib.cdll.gt_set_deterministic(1)
+        try:
+            yield
+        finally:
+            if on:                                   # (back to what the environment asks for: the library's default)
+                lib.cdll.gt_set_deterministic(1 if os.environ.get("GT_DETERMINISTIC", "")[:1] == "1" else 0)
+    return cm()
+
+
+def check_grad_probes(backend, cfg, B, p, probes, seq=True, flags=0, precision=0, deterministic=False, penalty=0.47, seed=3, probe_seed=100):
+    """One forward, then one backward per probe (probe_d_hvo), each against the oracle's backward of the same probe from the SAME fp64
+    forward cache (device's ReLU decisions adopted once, as in check_step); check_step's forward assertions unchanged.  After every
+    backward the buffer's gaps and guard element are exactly zero.
+    probes: a list of places (probe_places), or a callable (trace, M) -> such a list, given the dispatch trace of one full step (forward,
+    loss backward) that runs first in either case.  precision 1: the per-operation check of the bf16 path (check_ops_bf16, bars
+    unchanged) per probe instead of the end-to-end comparison -- with a sparse dlogits its weight-gradient lines are sharp by themselves.
+    deterministic: under gt_set_deterministic(1), put back afterwards.
+    Records FIGURES["probe"] (worst error / bar); returns (r, trace of the full step, places)."""
+    cfg = dict(cfg, dropout=p)
+    if precision:
+        cfg["precision"] = precision
+    lib = harness.emu_lib() if backend == "emu" else harness._lib.get_lib()
+    with _deterministic(lib, deterministic):
+        return _check_grad_probes(backend, cfg, B, p, probes, seq, flags, penalty, seed, probe_seed)
+
+
+def _check_grad_probes(backend, cfg, B, p, probes, seq, flags, penalty, seed, probe_seed):
+    precision = cfg.get("precision", 0)
+    P = ng.init_params(cfg, seed=seed, perturb=0.05)
+    x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
+    Ld = cfg.get("num_decoder_layers", 0)
+    tgt = shift_right(y) if Ld else None
+    rng = (1234, 99, 7)
+    train = p > 0
+    r = Runner(cfg, B, backend, rng=rng, seq=seq, flags=flags)
+    r.set_params(P)
+    gaps = gradient_gaps(r)
+    hvo, trace = harness.trace_dispatch(lambda: r.forward(x, tgt, train=train))
+    (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=rng if train else None, dtype=np.float64)
+    if precision == 0:
+        _check_forward_and_loss(r, hvo, (h, v, o), C, y, penalty, True)
+    else:                                            # check_step_bf16's end-to-end sanity bound on the forward
+        (h0, v0, o0), _ = ng.forward(P, dict(cfg, precision=0), x, tgt=tgt, rng=rng if train else None, dtype=np.float64)
+        ref, ref0 = np.concatenate([h, v, o], -1), np.concatenate([h0, v0, o0], -1)
+        eq = _rms(ref0 - ref)
+        assert eq > 1e-5, "the bf16 rounding has no visible effect on this case: pick another"
+        assert np.abs(hvo - ref).max() < BF16_OUT_MAX, "forward max-abs %g" % np.abs(hvo - ref).max()
+        frac = BF16_E2E_FRAC if r.precision_in_force() < 2 else 2.5
+        FIGURES.clear()
+        FIGURES["bf16_e2e"] = _rms(hvo - ref) / (frac * eq + 1e-5)
+        assert _rms(hvo - ref) <= frac * eq + 1e-5, "forward rms %g vs bf16 effect %g" % (_rms(hvo - ref), eq)
+        stats, _ = r.loss(y, penalty)
+        rstats, _ = ng.calculate_loss((h, v, o), y.astype(np.float64), penalty)
+        assert abs(stats[0] - rstats[0]) < 1e-2 * max(1.0, abs(rstats[0]))
+    _, bwd_trace = harness.trace_dispatch(lambda: r.backward(train=train))          # the whole batch's backward: the path every probe takes
+    trace = trace + bwd_trace
+    assert_gaps_zero(r, gaps, "whole batch")
+    if precision == 0:
+        adopted = adopt_device_kinks(r, C, cfg)
+        assert adopted <= kink_bound(r, cfg), adopted
+    places = list(probes(trace, r.M)) if callable(probes) else list(probes)
+    assert 1 <= len(places) <= MAX_PROBES and len(set(places)) == len(places), places
+    ran = 0
+    for i, place in enumerate(places):
+        d = probe_d_hvo(B, place, probe_seed + i)
+        G = r.backward(d, train=train)
+        assert_gaps_zero(r, gaps, "probe %s" % (place,))
+        if precision == 0:
+            Gr = ng.backward(P, cfg, C, (d[..., :9], d[..., 9:18], d[..., 18:]), dtype=np.float64)
+            ratio = probe_compare(G, Gr, place)
+        else:
+            FIGURES.pop("bf16_op", None)
+            try:
+                check_ops_bf16(r, P, cfg, x, tgt, rng, p, G, forward_checks=(i == 0))
+            except AssertionError as e:
+                raise AssertionError("probe %s: %s" % (place, e)) from None
+            ratio = FIGURES["bf16_op"]
+        FIGURES["probe"] = max(FIGURES.get("probe", 0.0), ratio)
+        ran += 1
+    assert ran == len(places), (ran, len(places))
+    return r, trace, places
+
+
+ACC_TOL = 2e-6                   # check_bucketed_backward's bar for two summation orders of the same gradient
+
+
+def check_accumulate(backend, cfg, B, p, seq=True, flags=0, penalty=0.47, seed=3):
+    """gt_backward(accumulate = 1) -- what the nn.Module path always passes, and what selects the adding store modes of the sequence-resident
+    weight-gradient units -- onto a NON-ZERO gradient buffer.  G0: multiples of 2^-10 in [-1, 1] inside the tensors, zero in the gaps and the
+    guard element.  d: the loss's d_hvo.
+    (a) buffer = G0; backward(d, accumulate=1)             must equal  G0 + backward(d, accumulate=0)
+    (b) buffer = G0; backward(d1, accumulate=0) (overwrites); backward(d2, accumulate=1)   must equal  backward(d1 + d2, accumulate=0),
+        d1 = d on the first half of the sequences, d2 = d on the second half.
+    Bar per element: ACC_TOL x max |expected buffer| + np.spacing(|expected|) -- check_bucketed_backward's bar, whose max is taken over the
+    whole flat buffer too.  In (a) that buffer is G0 + g, so the bar is about 2e-6: up to 32 partial tiles adding onto an element of size 1
+    round by 2^-24 each (worst case 1.9e-6); a store in place of an add, or a chunk added twice, is off by |G0| or |g| themselves.
+    Gaps and guard element stay zero.  Records FIGURES["accumulate"] (worst error / bar); returns the Runner."""
+    cfg = dict(cfg, dropout=p)
+    P = ng.init_params(cfg, seed=seed, perturb=0.05)
+    x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
+    tgt = shift_right(y) if cfg.get("num_decoder_layers", 0) else None
+    train = p > 0
+    r = Runner(cfg, B, backend, rng=(1234, 99, 7), seq=seq, flags=flags)
+    r.set_params(P)
+    gaps = gradient_gaps(r)
+    r.forward(x, tgt, train=train)
+    _, d = r.loss(y, penalty)
+    rnd = np.random.default_rng(seed + 40)
+    G0 = np.zeros(r.total, np.float32)
+    for off, size, _, _ in r.entries:
+        G0[off:off + size] = (rnd.integers(-1024, 1025, size) / 1024.0).astype(np.float32)
+    d1, d2 = d.copy(), d.copy()
+    d1[B // 2:] = 0
+    d2[:B // 2] = 0
+    assert np.abs(d1).max() > 0 and np.abs(d2).max() > 0
+
+    def run(dh, accumulate, start=None):
+        if start is not None:
+            r.grads = r.Buf(start.copy())
+        r.backward(dh, train=train, accumulate=accumulate)
+        return r.grads.numpy().astype(np.float64)
+
+    def close(got, want, what):
+        bar = ACC_TOL * np.abs(want).max() + np.spacing(np.abs(want))
+        err = np.abs(got - want)
+        FIGURES["accumulate"] = max(FIGURES.get("accumulate", 0.0), float((err / bar).max()))
+        if (err > bar).any():
+            i = int(np.argmax(err - bar))
+            name = [n for (n, _), (off, size, _, _) in zip(r.names, r.entries) if off <= i < off + size]
+            raise AssertionError("%s: %s flat element %d: got %.9g want %.9g, |err| %.3g > bar %.3g (%d elements over)"
+                                 % (what, name[0] if name else "gap", i, got[i], want[i], err[i], bar[i], int((err > bar).sum())))
+
+    FIGURES.pop("accumulate", None)
+    g = run(d, 0, np.zeros(r.total, np.float32))
+    assert np.abs(g).max() > 0
+    assert_gaps_zero(r, gaps, "accumulate = 0")
+    ga = run(d, 1, G0)                               # (a)
+    close(ga, G0.astype(np.float64) + g, "(a) backward(d, accumulate=1) onto G0")
+    assert_gaps_zero(r, gaps, "(a)")
+    run(d1, 0, G0)                                   # (b): the first call overwrites G0
+    gb = run(d2, 1)
+    close(gb, g, "(b) backward(d1) then backward(d2, accumulate=1)")
+    assert_gaps_zero(r, gaps, "(b)")
+    return r
 
 
 # ---- bf16 operand path (gt_config.precision = 1, BASELINE configs[4]) -------------------------------------------------------
@@ -137,9 +402,10 @@ def _close(dev, ref, what, tol=BF16_OP_TOL, where=None, stored16=False, rms_tol=
         assert _rms(err) <= rms_tol * scale, "%s: rms err %.3g of max |ref| %.3g (ratio %.3g)" % (what, _rms(err), scale, _rms(err) / scale)
 
 
-def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None):
+def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     """Teacher-forced per-operation parity of the bf16 path (bar (1) above).  r: Runner after forward (and, with G = the device's
-    gradients, after loss + backward).  Returns the number of operations checked."""
+    gradients, after loss + backward).  forward_checks=False: only the backward half is compared (a second backward from the same forward:
+    check_grad_probes) -- the forward half is still walked for its operands.  Returns the number of operations checked."""
     rb = ng.round_bf16
     f64 = lambda a: np.asarray(a, np.float64)
     P = {k: f64(v) for k, v in P.items()}
@@ -187,13 +453,14 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None):
         return a.transpose(0, 2, 1, 3).reshape(M, heads * hd)
 
     n = 0
+    fclose = _close if forward_checks else (lambda *a, **k: None)
     # ---------------------------------------------------------------------------------------------- forward
     def input_layer(xin, pre, a0name, outname, site):
         nonlocal n
         a = lin(f64(xin).reshape(M, -1), P[pre + "weight"], P[pre + "bias"])
         safe = np.abs(a) > 1e-4
-        _close(ws(a0name), a, pre + "pre-activation")
-        _close(ws(outname), (np.maximum(a, 0) + pe) * mask(site, a.size, a.shape), pre + "output", where=safe)
+        fclose(ws(a0name), a, pre + "pre-activation")
+        fclose(ws(outname), (np.maximum(a, 0) + pe) * mask(site, a.size, a.shape), pre + "output", where=safe)
         n += 2
 
     def attn_block(name, gl, xin, inw, qkvname, ctxname, outname, xhname, normname, site, q_rows=None):
@@ -202,21 +469,21 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None):
         out = lin(ws(ctxname, gl), P[name + "out_proj.weight"], P[name + "out_proj.bias"])
         out = (hrb(out) if enc else out) * mask(site, M * d, (M, d))
         y, xh = ln(xin + out, P[normname + ".weight"], P[normname + ".bias"])
-        _close(ws(outname, gl), y, "%s out-proj + norm (layer %d)" % (name, gl), **(HID if enc else dict(tol=2e-5)))
-        _close(ws(xhname, gl), xh, "%s xhat (layer %d)" % (name, gl), **(HID if enc else dict(tol=2e-5)))
+        fclose(ws(outname, gl), y, "%s out-proj + norm (layer %d)" % (name, gl), **(HID if enc else dict(tol=2e-5)))
+        fclose(ws(xhname, gl), xh, "%s xhat (layer %d)" % (name, gl), **(HID if enc else dict(tol=2e-5)))
         n += 2
         return ws(outname, gl)
 
     def ffn_block(pre, gl, xin, normname, outname="xout"):
         nonlocal n
         hp = lin(xin, P[pre + "linear1.weight"], P[pre + "linear1.bias"])
-        _close(ws("hact", gl), np.maximum(hp, 0) * mask(ng.layer_site(gl, ng.S_FFN), hp.size, hp.shape),
+        fclose(ws("hact", gl), np.maximum(hp, 0) * mask(ng.layer_site(gl, ng.S_FFN), hp.size, hp.shape),
                pre + "linear1", where=np.abs(hp) > 1e-4, stored16=r.bf16_only("hact", gl))
         enc = P2 and gl < L - 1          # (the top encoder layer's linear2 feeds the two-norm pass from fp32)
         f = lin(ws("hact", gl), P[pre + "linear2.weight"], P[pre + "linear2.bias"])
         f = (hrb(f) if enc else f) * mask(ng.layer_site(gl, ng.S_DROPF), M * d, (M, d))
         y, xh = ln(xin + f, P[pre + normname + ".weight"], P[pre + normname + ".bias"])
-        _close(ws(outname, gl), y, pre + "linear2 + norm", **(HID if enc else dict(tol=2e-5)))
+        fclose(ws(outname, gl), y, pre + "linear2 + norm", **(HID if enc else dict(tol=2e-5)))
         n += 2
         return ws(outname, gl)
 
@@ -226,7 +493,7 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None):
     for l in range(L):
         pre = "Encoder.Encoder.layers.%d." % l
         enc_in.append(cur)
-        _close(ws("qkv", l), lin(cur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "in_proj",
+        fclose(ws("qkv", l), lin(cur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "in_proj",
                stored16=r.bf16_only("qkv", l))
         n += 1
         if P2:      # the attention core on bf16-STORED q / k / v (fp32 arithmetic; attn_fwd_lds_kernel): probabilities and ctx
@@ -234,14 +501,14 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None):
             q_, k_, v_ = (split_heads(qkv[:, i * d:(i + 1) * d]) for i in range(3))
             sc = q_ @ k_.transpose(0, 1, 3, 2) / np.sqrt(hd)
             pr = np.exp(sc - sc.max(-1, keepdims=True)); pr /= pr.sum(-1, keepdims=True)
-            _close(f64(r.ws_get("P", l)).reshape(pr.shape), pr, pre + "attention probabilities over bf16-stored q / k", tol=2e-5)
+            fclose(f64(r.ws_get("P", l)).reshape(pr.shape), pr, pre + "attention probabilities over bf16-stored q / k", tol=2e-5)
             pm = pr * mask(ng.layer_site(l, ng.S_ATTN), pr.size, pr.shape)
-            _close(ws("ctx", l), merge_heads(pm @ v_), pre + "attention output over bf16-stored v", stored16=True)
+            fclose(ws("ctx", l), merge_heads(pm @ v_), pre + "attention output over bf16-stored v", stored16=True)
             n += 2
         x1 = attn_block(pre + "self_attn.", l, cur, None, "qkv", "ctx", "x1", "xhat1", pre + "norm1", ng.layer_site(l, ng.S_DROP1))
         cur = ffn_block(pre, l, x1, "norm2")
     mem, _ = ln(cur, P["Encoder.Encoder.norm.weight"], P["Encoder.Encoder.norm.bias"])
-    _close(ws("memory"), mem, "final encoder norm", tol=2e-5)
+    fclose(ws("memory"), mem, "final encoder norm", tol=2e-5)
     final = ws("memory")
     dec_in = []
     if Ld:
@@ -250,20 +517,20 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None):
         for l in range(Ld):
             pre, gl = "Decoder.Decoder.layers.%d." % l, L + l
             dec_in.append(ycur)
-            _close(ws("qkv", gl), lin(ycur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "self in_proj")
+            fclose(ws("qkv", gl), lin(ycur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "self in_proj")
             y1 = attn_block(pre + "self_attn.", gl, ycur, None, "qkv", "ctx", "x1", "xhat1", pre + "norm1", ng.layer_site(gl, ng.S_DROP1))
             wx, bx = P[pre + "multihead_attn.in_proj_weight"], P[pre + "multihead_attn.in_proj_bias"]
-            _close(ws("qx", gl), lin(y1, wx[:d], bx[:d]), pre + "cross q in_proj")
-            _close(ws("kvx", gl), lin(final, wx[d:], bx[d:]), pre + "cross kv in_proj")
+            fclose(ws("qx", gl), lin(y1, wx[:d], bx[:d]), pre + "cross q in_proj")
+            fclose(ws("kvx", gl), lin(final, wx[d:], bx[d:]), pre + "cross kv in_proj")
             n += 3
             y2 = attn_block(pre + "multihead_attn.", gl, y1, None, "qx", "ctxx", "x2", "xhatx", pre + "norm2", ng.layer_site(gl, ng.S_DROP2))
             ycur = ffn_block(pre, gl, y2, "norm3")
         fin, _ = ln(ycur, P["Decoder.Decoder.norm.weight"], P["Decoder.Decoder.norm.bias"])
-        _close(ws("dec_final"), fin, "final decoder norm", tol=2e-5)
+        fclose(ws("dec_final"), fin, "final decoder norm", tol=2e-5)
         final = ws("dec_final")
     logits = lin(final, P["OutputLayer.Linear.weight"], P["OutputLayer.Linear.bias"])
     want = np.concatenate([logits[:, :9], 1 / (1 + np.exp(-logits[:, 9:18])), 0.5 * np.tanh(logits[:, 18:])], 1)
-    _close(r.hvo.numpy().reshape(M, 27), want, "output layer + heads")
+    fclose(r.hvo.numpy().reshape(M, 27), want, "output layer + heads")
     n += 1
     if G is None:
         return n
