@@ -100,6 +100,22 @@ __device__ __forceinline__ float seq_row16_sum(float v) {
 #endif
   return v;
 }
+// the same over aligned groups of N = 4 / 8 / 16 lanes: the first log2(N) steps of it
+template <int N>
+__device__ __forceinline__ float seq_group_sum(float v) {
+  static_assert(N == 4 || N == 8 || N == 16, "a quad, a half row or a row");
+#ifdef GT_EMU
+  v += __shfl_xor(v, 1); v += __shfl_xor(v, 2);
+  if (N >= 8) v += __shfl_xor(v, 4);
+  if (N >= 16) v += __shfl_xor(v, 8);
+#else
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
+  if (N >= 8) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
+  if (N >= 16) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
+#endif
+  return v;
+}
 
 // ---- pair exchange between the two COLUMN PARTNERS of a QUAD forward (see seq_fwd_kernel): each of the two workgroups holds a partial
 // [16][128] result (its half of a contraction) as one 16 x 16 accumulator tile per wave and needs the other's.  A value travels as an
@@ -765,7 +781,8 @@ __device__ __forceinline__ void seq_ln_part(const float* sP, float* part, const 
 // ================================================================================================================ attention
 // The transposed-score scheme of gt_attn.h (S^T = K Q^T so that softmax rows are in-lane and P feeds the next MFMA without any
 // data movement) on LDS operands: q / k / v (and dctx in the backward) are tiles of this workgroup, read with 32-bit LDS
-// addresses.  Wave pair p = wave >> 1 takes head h4 + p, wave & 1 the query (role 2: key) tile.
+// addresses.  Wave pair p = wave >> 1 takes head h4 + p, wave & 1 the query (role 2: key) tile
+// (SPLIT backward: the role, on the workgroup's own tile).
 // HDC: head-dim class the kernel is compiled for -- 0: head_dim < 16 (operands zero-padded to 16 columns), else 16 / 32 / 64
 template <int HDC> struct SeqHd { static constexpr int HD = HDC ? HDC : 16; static constexpr bool PAD = HDC == 0; };
 // PAD: columns >= head_dim read as 0 (the address is clamped to the head's first column: always inside the tile)
@@ -880,7 +897,11 @@ __device__ __forceinline__ void seq_attn_fwd(const SeqAttn& a, float* ctx, const
 // Backward, two roles per wave with a workgroup barrier between them (gt_attn.h): role 1 (query tile w) -> dq in registers and
 // the row sums rd -> srd (32 floats of LDS per head); role 2 (key tile w) -> dk, dv in registers; after another barrier
 // seq_attn_bwd_store writes dq / dk / dv over q / k / v of the head (the dqkv tile IS the qkv tile).
-template <int HD, bool PAD>
+// SPLIT (16 own rows per workgroup): the row sums do not come from role 1 -- rd_i = sum_j dP_ij P_ij = dctx_i . ctx_i over the head's columns,
+// ctx = (P o mask) V being what the forward saved for the out-proj weight gradient; the phase's state load leaves them in LDS (seq_bwd_body).
+// So the roles do not depend on each other: wave & 1 is the ROLE, both on tile rb / 16 -- role 1 -> dq of the own query rows (RDIN: rd is
+// read, not summed), role 2 -> dk, dv of the own key rows -- at the same time, ONE barrier in front of the in-place store of the own rows.
+template <int HD, bool PAD, bool RDIN = false>
 __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dctx, const int lddc, const SeqDropK& dk, const uint32_t key,
                                               const int w, const int lane, float* srd, f32x4 (&dq_out)[HD / 16]) {
   constexpr int NQ = HD / 16;
@@ -907,6 +928,7 @@ __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dct
   float4 pv[2];
 #pragma unroll
   for (int tj = 0; tj < 2; ++tj) pv[tj] = *reinterpret_cast<const float4*>(a.P + (unsigned)(i * 32 + 16 * tj + 4 * g));
+  float rd = RDIN ? srd[i] : 0.f;
   f32x4 dt[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};           // dPd^T tiles [tj]
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -915,7 +937,7 @@ __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dct
     dt[0] = GT_MFMA16(v0[q].z, df[q].z, dt[0]); dt[1] = GT_MFMA16(v1[q].z, df[q].z, dt[1]);
     dt[0] = GT_MFMA16(v0[q].w, df[q].w, dt[0]); dt[1] = GT_MFMA16(v1[q].w, df[q].w, dt[1]);
   }
-  float p[2][4], dp[2][4], rd = 0.f;
+  float p[2][4], dp[2][4];
 #pragma unroll
   for (int tj = 0; tj < 2; ++tj) {
     const uint32_t idx0 = a.pidx + (uint32_t)(i * 32 + 16 * tj + 4 * g);
@@ -923,11 +945,13 @@ __device__ __forceinline__ void seq_attn_bwd1(const SeqAttn& a, const float* dct
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       dp[tj][r] = dt[tj][r] * seq_dmul(dk, key, idx0 + r);
-      rd += dp[tj][r] * p[tj][r];
+      if (!RDIN) rd += dp[tj][r] * p[tj][r];
     }
   }
-  rd += __shfl_xor(rd, 16); rd += __shfl_xor(rd, 32);
-  if (g == 0) srd[i] = rd;
+  if (!RDIN) {
+    rd += __shfl_xor(rd, 16); rd += __shfl_xor(rd, 32);
+    if (g == 0) srd[i] = rd;
+  }
   float ds[2][4];
 #pragma unroll
   for (int tj = 0; tj < 2; ++tj)
@@ -1009,7 +1033,22 @@ __device__ __forceinline__ void seq_attn_bwd2(const SeqAttn& a, const float* dct
       }
   }
 }
-// rows 16 w + 4 g + r, columns 16 ct + l16 of the head: dq over q, dk over k (+ d columns), dv over v (+ 2 d)
+// rows 16 w + 4 g + r, columns 16 ct + l16 of the head: one of dq / dk / dv over the head's q / k / v (dst: its first column)
+template <int HD, bool PAD>
+__device__ __forceinline__ void seq_attn_bwd_store1(float* dst, const int ldq, const int hd, const int w, const int lane, const f32x4 (&t)[HD / 16]) {
+  constexpr int NQ = HD / 16;
+  const int hdr = PAD ? hd : HD;
+  const int l16 = lane & 15, g = lane >> 4;
+  float* row = dst + (16 * w + 4 * g) * ldq + l16;
+#pragma unroll
+  for (int ct = 0; ct < NQ; ++ct)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (PAD && 16 * ct + l16 >= hdr) continue;
+      row[r * ldq + 16 * ct] = t[ct][r];
+    }
+}
+// dq over q, dk over k (+ d columns), dv over v (+ 2 d)
 template <int HD, bool PAD>
 __device__ __forceinline__ void seq_attn_bwd_store(float* dq, const int ldq, const int d, const int hd, const int w, const int lane,
                                                    const f32x4 (&dq_out)[HD / 16], const f32x4 (&dk_out)[HD / 16], const f32x4 (&dv_out)[HD / 16]) {
@@ -1747,14 +1786,17 @@ __global__ __launch_bounds__(GT_SEQ_NT) void seq_fwd_kernel(SeqArgs a) {
 // for l = L-1 .. 0: 1 + 2 (L-1-l) = norm2 of layer l, 2 + 2 (L-1-l) = norm1 of layer l.  The host registers them in this order.
 // SPLIT (two workgroups per sequence, 16 rows each, one launch per phase): only the attention backward couples the rows (dk / dv
 // contract over all queries), so a phase ends at dctx -- own rows to the hand-over buffer a.dctx -- and the next one begins with the
-// attention backward of the WHOLE sequence, computed by both workgroups of the pair (a fifth of a phase; no exchange, no
-// second launch), each keeping its own rows of dq / dk / dv.  phase 0: output-layer dgrad .. out-proj dgrad of layer L-1;
+// attention backward, each workgroup of the pair computing ITS OWN 16 rows of dq / dk / dv from the whole sequence's q / k / v / dctx /
+// ctx / P (no exchange, no second launch): dq of the own queries and dk / dv of the own keys at the same time on different waves, the
+// row sums both need taken from dctx . ctx instead of from the other half's queries (seq_attn_bwd1).
+// phase 0: output-layer dgrad .. out-proj dgrad of layer L-1;
 // phase p: attention backward + in-proj dgrad of layer L-p, then norm2 backward .. out-proj dgrad of layer L-p-1 (or the input
 // layer's backward).
 // QUAD (round 4): backward phase 0 -- the one phase without riders, so half of the chip idles -- with four workgroups per sequence, as in
 // the forward: the column partners of a row half split the FFN2 dgrad by columns of dhid and the FFN1 dgrad by its contraction (one
 // pair exchange of the [16][128] partial results), split the out-proj dgrad's columns (dctx goes to the hand-over buffer anyway), and
 // compute the output-layer dgrad and the LayerNorm backward passes twice; partner 0 writes what both computed.  Phase 0 only.
+struct SeqRdPre { float4 a0, c0, a1, c1; };                 // (SPLIT) a thread's pieces of the dctx and ctx tiles, requested at a phase's start
 template <int DP> struct SeqBwdLds {
   using G = SeqGeo<DP>;
   static constexpr int U = DP > 64 ? G::UNI : G::QKV + G::FFN, P = 2 * GT_SEQ_WAVES * DP;
@@ -1980,9 +2022,10 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     GT_BARRIER();
     GT_STAMP(sb + 4);
   };
-  // ---- attention backward of the whole sequence (four heads at a time: q / k / v from the LDS tile, P from global (saved), dctx
-  // from LDS; dq / dk / dv replace q / k / v of the head in place -- every wave of the round has finished reading before anyone
-  // stores: third barrier), own rows of dqkv -> global (operand of the in-proj weight gradient), in-proj dgrad (K = 3 d: split over
+  // ---- attention backward (four heads at a time: q / k / v from the LDS tile, P from global (saved), dctx from LDS; dq / dk / dv
+  // replace q / k / v of the head in place -- every wave of the round has finished reading before anyone stores: the barrier in
+  // front of the store; whole sequence: all 32 rows, two roles per wave; SPLIT: the own 16 rows, one role per wave -- see
+  // seq_attn_bwd1), own rows of dqkv -> global (operand of the in-proj weight gradient), in-proj dgrad (K = 3 d: split over
   // the waves) -> partial tiles; ends with a barrier
   // (PFB) the chain of layer l - 1 follows the attention backward + in-proj dgrad of layer l: its two norms' saved operands (x-hat, rstd, gamma: three
   // small loads per thread each) are requested at the phase's START.  Measured alternatives for these AND the chain's bigger operands (the own rows of
@@ -2001,47 +2044,130 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     }
   };
   SeqPRow prow = SeqPRow();                                  // head_dim-2 attention: this thread's P row, requested at the start of the phase
-  auto attn_inproj = [&](const int l) {
+  // ---- SPLIT, the start of a phase > 0: the dctx tile of the whole sequence -> sZ and the attention backward's row sums rd[h][i] = dctx_i . ctx_i
+  // over head h's columns (see seq_attn_bwd1) -> sR[32 h + i] (free until the in-proj dgrad).  Two forms, by head_dim class:
+  // * 16 / 32 / 64 (rd_tile_request + rd_tile_finish): the thread that carries 16 bytes of dctx to LDS REQUESTS the same 16 bytes of ctx with
+  //   them (both tiles are [32][d]; one piece per thread, two at d_model 128), and after the other state tiles are on their way stores the dctx
+  //   piece -- sZ is complete only after rd_tile_finish --, multiplies the two and sums over the head_dim / 4 neighbouring lanes that hold the
+  //   row's head.  All of it in front of the phase's state barrier: no barrier of its own.
+  // * < 16, any value, any number of heads (rd_small_stage + rd_small_rows): the ctx tile goes to LDS like the state tiles (sC, free until the
+  //   chain's norm2 backward) and a pass behind the state barrier, one (row, head) pair per thread, sums from LDS; a barrier of its own.
+  //   (Summed from global memory in front of the barrier instead -- a loop with loads in it -- every later wait of the phase covered everything
+  //   in flight, the chain's operands requested at the phase's start included.)
+  // The kernels that hold the head_dim-2 passes take neither form (OWN, below).
+  constexpr bool RD2 = 32 * (DP / 4) > GT_SEQ_NT;            // a second 16-byte piece per thread (d_model 128)
+  auto rd_tile_request = [&](const float* gd, const float* gc) {
+    static_assert(G::RES >= 32 * DP && 32 * (DP / 4) <= 2 * GT_SEQ_NT, "row sums of every head in sR; two 16-byte pieces per thread cover a tile");
+    SeqRdPre p = SeqRdPre();
+    const int q4 = d >> 2, n = 32 * q4;
+    const int e0 = tid < n ? tid : 0;                          // (outside the tile: piece 0, not used)
+    const unsigned o0 = (unsigned)((e0 / q4) * d + (e0 % q4) * 4);
+    p.a0 = *reinterpret_cast<const float4*>(gd + o0); p.c0 = *reinterpret_cast<const float4*>(gc + o0);
+    if constexpr (RD2) {
+      const int e1 = tid + GT_SEQ_NT < n ? tid + GT_SEQ_NT : 0;
+      const unsigned o1 = (unsigned)((e1 / q4) * d + (e1 % q4) * 4);
+      p.a1 = *reinterpret_cast<const float4*>(gd + o1); p.c1 = *reinterpret_cast<const float4*>(gc + o1);
+    }
+    return p;
+  };
+  auto rd_tile_finish = [&](const SeqRdPre& p) {
+    const int q4 = d >> 2;
+    auto one = [&](const int e_, const float4& av, const float4& cv) {
+      const bool ok = e_ < 32 * q4;
+      const int e = ok ? e_ : 0, r = e / q4, c = (e % q4) * 4;
+      if (ok) *reinterpret_cast<float4*>(sZ + r * SX + c) = av;
+      const float s = seq_group_sum<HD / 4>(ok ? av.x * cv.x + av.y * cv.y + av.z * cv.z + av.w * cv.w : 0.f);
+      if (ok && c % HD == 0) sR[32 * (c / HD) + r] = s;
+    };
+    one(tid, p.a0, p.c0);
+    if constexpr (RD2) one(tid + GT_SEQ_NT, p.a1, p.c1);
+  };
+  auto rd_small_stage = [&](const float* gd, const float* gc) {
+    static_assert(G::RES >= 32 * DP, "row sums of every head in sR");
+    load_rows(sZ, SX, gd, d, 0, 32);
+    load_rows(sC, SX, gc, d, 0, 32);
+  };
+  auto rd_small_rows = [&]() {
+    for (int e = tid; e < 32 * a.H; e += GT_SEQ_NT) {
+      const int i = e / a.H, h = e - i * a.H;
+      const float* zr = sZ + i * SX + h * a.hd, *cr = sC + i * SX + h * a.hd;
+      float s = 0.f;
+      for (int c = 0; c < a.hd; ++c) s += zr[c] * cr[c];
+      sR[32 * h + i] = s;
+    }
+    GT_BARRIER();
+  };
+  // the head_dim-2 form exists in these kernels (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
+  constexpr bool VATTN = PAD && SPLIT && (DP == 32 || DP == 64);
+  // OWN: the SPLIT attention backward computes the workgroup's own rows only (seq_attn_bwd1).  Not in the kernels that hold the head_dim-2 form:
+  // they serve the reference's own YAML shapes, whose launches measured 0.3 - 0.4 us longer with the own-rows code beside their passes (in
+  // whichever form: profiles/split_attn_bwd_bench.txt), so head_dim < 16 at d_model 32 / 64 keeps the two-role form over the whole sequence
+  constexpr bool OWN = SPLIT && !VATTN;
+  // va (std::true_type / std::false_type): the head_dim-2 passes or the MFMA roles -- a compile-time choice, so that neither form's
+  // instruction stream runs through the other's branches and waits.  Returns the in-proj dgrad's first chunk, in flight.
+  auto attn_bwd = [&](const int l, auto va) {
+    constexpr bool VA = decltype(va)::value;
     const float* kb = ws + a.pack_b + (int64_t)l * a.kstride;
     float* wl = ws + (int64_t)l * a.wstride;
-    float* tl = ws + (int64_t)l * a.tstride;
-    const int sb = 102 + 10 * (a.L - 1 - l);
     const bool preq = SPLIT && seq_splitk_pre_ok(3 * d, d);
     SeqB<8> bqpre = SeqB<8>();
-    bool vattn = false;
-    if constexpr (PAD && SPLIT && (DP == 32 || DP == 64)) {        // (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
-      vattn = a.hd == DP / 16 && a.H == 16;
-      if (vattn) {                                              // (sR is free here: H x 32 row sums)
-        static_assert(G::FFN >= 16 * 1024 && G::RES >= 2 * 16 * 32 && !ALIAS, "head_dim-2 attention backward: P image in the FFN tile, row sums + keep bits in sR");
-        SeqAttnSmallG<DP / 16> G;
-        seq_attn_bwd_small_a<DP / 16>(G, sQ, SQ, d, a.H, ascale, prow, sH, sZ, SX, dk, sR, tid);
-        GT_BARRIER();
-        GT_STAMP(400 + 4 * a.phase + 1);
-        seq_attn_bwd_small_b<DP / 16>(G, sQ, SQ, d, a.H, ascale, sH, sZ, SX, dk, sR, rb, NROW, tid);
-        GT_BARRIER();
-        GT_STAMP(400 + 4 * a.phase + 2);
-        seq_attn_bwd_small_store<DP / 16>(G, sQ, SQ, d, a.H, rb, NROW, tid);
-        if (preq) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
-      }
-    }
-    if (!vattn) {
+    if constexpr (VA) {                                         // (sR is free here: H x 32 row sums)
+      constexpr int HV = VA ? DP / 16 : 2;                      // (dependent on va: nothing of this form is instantiated in the other kernels)
+      static_assert(!VA || (VATTN && G::FFN >= 16 * 1024 && G::RES >= 2 * 16 * 32 && !ALIAS), "head_dim-2 attention backward: P image in the FFN tile, row sums + keep bits in sR");
+      SeqAttnSmallG<HV> G;
+      seq_attn_bwd_small_a<HV>(G, sQ, SQ, d, a.H, ascale, prow, sH, sZ, SX, dk, sR, tid);
+      GT_BARRIER();
+      GT_STAMP(400 + 4 * a.phase + 1);
+      seq_attn_bwd_small_b<HV>(G, sQ, SQ, d, a.H, ascale, sH, sZ, SX, dk, sR, rb, NROW, tid);
+      GT_BARRIER();
+      GT_STAMP(400 + 4 * a.phase + 2);
+      seq_attn_bwd_small_store<HV>(G, sQ, SQ, d, a.H, rb, NROW, tid);
+      if (preq) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
+    } else {
       const uint32_t key = seq_key(dk, GT_SITE_LAYER0 + 8 * l + GT_SITE_ATTN);
+      if constexpr (OWN && PAD) rd_small_rows();
       for (int h4 = 0; h4 < a.H; h4 += GT_SEQ_WAVES / 2) {
         const int h = h4 + (wave >> 1);
         const bool active = h < a.H;
         SeqAttn at;
         at.q = sQ + h * a.hd; at.k = at.q + d; at.v = at.q + 2 * d; at.ldq = SQ; at.hd = a.hd; at.scale = ascale;
         at.pidx = (uint32_t)((b * a.H + h) * 1024); at.P = wl + a.w0.P + (size_t)(b * a.H + h) * 1024;
-        f32x4 dq_out[HD / 16], dk_out[HD / 16], dv_out[HD / 16];
-        if (active) seq_attn_bwd1<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dq_out);
-        GT_BARRIER();
-        if (active) seq_attn_bwd2<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dk_out, dv_out);
-        // the in-proj dgrad's first chunk: in flight across the two barriers, the dq / dk / dv store and the dqkv tile's way to global
-        if (preq && h4 + GT_SEQ_WAVES / 2 >= a.H) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
-        GT_BARRIER();
-        if (active) seq_attn_bwd_store<HD, PAD>(sQ + h * a.hd, SQ, d, a.hd, wave & 1, lane, dq_out, dk_out, dv_out);
+        if constexpr (OWN) {
+          // own rows only: wave & 1 is the role, the row sums are in sR -- one barrier, in front of the in-place store
+          const int w = rb >> 4;
+          const bool role2 = (wave & 1) != 0;
+          f32x4 o1[HD / 16], o2[HD / 16];                          // role 1: dq, -; role 2: dk, dv
+          if (active) {
+            if (!role2) seq_attn_bwd1<HD, PAD, true>(at, sZ + h * a.hd, SX, dk, key, w, lane, sR + 32 * h, o1);
+            else seq_attn_bwd2<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, w, lane, sR + 32 * h, o1, o2);
+          }
+          // the in-proj dgrad's first chunk: in flight across the barrier, the dq / dk / dv store and the dqkv tile's way to global
+          if (preq && h4 + GT_SEQ_WAVES / 2 >= a.H) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
+          GT_BARRIER();
+          if (active) {
+            float* const hq = sQ + h * a.hd;
+            if (!role2) seq_attn_bwd_store1<HD, PAD>(hq, SQ, a.hd, w, lane, o1);
+            else { seq_attn_bwd_store1<HD, PAD>(hq + d, SQ, a.hd, w, lane, o1); seq_attn_bwd_store1<HD, PAD>(hq + 2 * d, SQ, a.hd, w, lane, o2); }
+          }
+        } else {
+          f32x4 dq_out[HD / 16], dk_out[HD / 16], dv_out[HD / 16];
+          if (active) seq_attn_bwd1<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dq_out);
+          GT_BARRIER();
+          if (active) seq_attn_bwd2<HD, PAD>(at, sZ + h * a.hd, SX, dk, key, wave & 1, lane, srd + 32 * (wave >> 1), dk_out, dv_out);
+          // the in-proj dgrad's first chunk: in flight across the two barriers, the dq / dk / dv store and the dqkv tile's way to global
+          if (preq && h4 + GT_SEQ_WAVES / 2 >= a.H) bqpre = seq_splitk_first(kb, 3 * d, d, wave, lane);
+          GT_BARRIER();
+          if (active) seq_attn_bwd_store<HD, PAD>(sQ + h * a.hd, SQ, d, a.hd, wave & 1, lane, dq_out, dk_out, dv_out);
+        }
       }
     }
+    return bqpre;
+  };
+  auto inproj_dgrad = [&](const int l, const SeqB<8>& bqpre) {
+    const float* kb = ws + a.pack_b + (int64_t)l * a.kstride;
+    float* tl = ws + (int64_t)l * a.tstride;
+    const int sb = 102 + 10 * (a.L - 1 - l);
+    const bool preq = SPLIT && seq_splitk_pre_ok(3 * d, d);
     GT_BARRIER();
     GT_STAMP(sb + 5);
     seq_tile_out(tl + a.t0.dqkv + r0 * 3 * d, sQ, SQ, 3 * d, tid, rb, NROW);
@@ -2078,7 +2204,7 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
   } else if (!SPLIT) {
     GT_STAMP(100);
     prologue();
-    for (int l = a.L - 1; l >= 0; --l) { chain(l, l == a.L - 1); attn_inproj(l); }
+    for (int l = a.L - 1; l >= 0; --l) { chain(l, l == a.L - 1); inproj_dgrad(l, attn_bwd(l, std::false_type{})); }
     input_bwd();
     GT_STAMP(102 + 10 * a.L);
   } else if (a.phase == 0) {
@@ -2091,18 +2217,34 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     const int l = a.L - a.phase;
     GT_STAMP(160 + 2 * a.phase);
     const int64_t hand = (int64_t)a.B * 32 * d;                                                             // floats per hand-over buffer
-    if constexpr (PAD && SPLIT && (DP == 32 || DP == 64)) {
-      if (a.hd == DP / 16 && a.H == 16)
+    // the phase's state -> LDS: dctx of the whole sequence (OWN: and, for the row sums, its ctx), its saved q / k / v, dz1 of layer l (own rows)
+    const float* const gdctx = ws + a.dctx + ((a.phase - 1) & 1) * hand + r0 * d;
+    const float* const gctx = ws + (int64_t)l * a.wstride + a.w0.ctx + r0 * d;
+    bool va = false;
+    if constexpr (VATTN) {
+      va = a.hd == DP / 16 && a.H == 16;
+      if (va)
         prow = seq_attn_bwd_small_load(ws + (int64_t)l * a.wstride + a.w0.P + (size_t)(b * a.H) * 1024,
                                        reinterpret_cast<const uint32_t*>(ws + a.amask + (int64_t)l * a.amask_stride) + b * a.H * 32, tid);
     }
-    load_rows(sZ, SX, ws + a.dctx + ((a.phase - 1) & 1) * hand + r0 * d, d, 0, 32);                         // dctx of the whole sequence
-    load_rows(sQ, SQ, ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * d, 3 * d, 0, 32);                   // its saved q / k / v
-    load_rows(sDZ, SX, ws + (int64_t)l * a.tstride + a.t0.dzB + r0 * d, d, rb, NROW);                        // dz1 of layer l, own rows
+    SeqRdPre rdp = SeqRdPre();
+    if constexpr (OWN && !PAD) rdp = rd_tile_request(gdctx, gctx);              // (sZ: complete after rd_tile_finish below)
+    else if constexpr (OWN) rd_small_stage(gdctx, gctx);
+    else load_rows(sZ, SX, gdctx, d, 0, 32);
+    load_rows(sQ, SQ, ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * d, 3 * d, 0, 32);
+    load_rows(sDZ, SX, ws + (int64_t)l * a.tstride + a.t0.dzB + r0 * d, d, rb, NROW);
     chain_prefetch(l);
+    if constexpr (OWN && !PAD) rd_tile_finish(rdp);
     GT_BARRIER();
     GT_STAMP(400 + 4 * a.phase);
-    attn_inproj(l);
+    SeqB<8> bqpre;
+    if constexpr (VATTN) {
+      if (va) bqpre = attn_bwd(l, std::true_type{});
+      else bqpre = attn_bwd(l, std::false_type{});
+    } else {
+      bqpre = attn_bwd(l, std::false_type{});
+    }
+    inproj_dgrad(l, bqpre);
     if (l > 0) {
       chain(l - 1, false);
       seq_tile_out(ws + a.dctx + (a.phase & 1) * hand + r0 * d, sZ, SX, d, tid, rb, NROW);
