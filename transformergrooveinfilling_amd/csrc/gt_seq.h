@@ -220,6 +220,30 @@ __device__ __forceinline__ void seq_mm_edge(const float* sA, const int lda, cons
   for (int u = 0; u < NK; ++u) { if (16 * u < K) seq_mma<HALF>(acc0, acc1, b[u], sA, lda, l16, 16 * u + 4 * lg); }
   epi(n0, acc0, acc1, bi);
 }
+// the same in two halves (seq_fb_kernel's output layer): the fragments and the bias are REQUESTED a stage ahead of the product that uses them
+template <int NK> struct SeqEdgeB { float b[NK][4], bi[4]; };
+template <bool BKM, bool VEC, int NK>
+__device__ __forceinline__ void seq_mm_edge_load(SeqEdgeB<NK>& e, const int K, const float* __restrict__ W, const int ldw, const int N,
+                                                 const float* __restrict__ bias, const int wave, const int lane, const float* zp) {
+  const int l16 = lane & 15, lg = lane >> 4;
+  const int n0 = wave * 16;
+  if (n0 >= N) return;                                   // wave-uniform
+#pragma unroll
+  for (int u = 0; u < NK; ++u) { if (16 * u < K) seq_ldb<BKM, VEC>(e.b[u], W, ldw, n0 + l16, N, 16 * u + 4 * lg, K, zp); }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) e.bi[r] = *((bias != nullptr && n0 + 4 * lg + r < N) ? bias + n0 + 4 * lg + r : zp);
+}
+template <int NK, bool HALF, typename Epi>
+__device__ __forceinline__ void seq_mm_edge_run(const SeqEdgeB<NK>& e, const float* sA, const int lda, const int K, const int N, const int wave,
+                                                const int lane, Epi epi) {
+  const int l16 = lane & 15, lg = lane >> 4;
+  const int n0 = wave * 16;
+  if (n0 >= N) return;
+  f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < NK; ++u) { if (16 * u < K) seq_mma<HALF>(acc0, acc1, e.b[u], sA, lda, l16, 16 * u + 4 * lg); }
+  epi(n0, acc0, acc1, e.bi);
+}
 
 // ---- Fragment-ordered weights.  For a product C = A * B with B(k, n) taken from a weight matrix W (forward: B(k, n) = W[n][k];
 // dgrad: B(k, n) = W[k][n]) the pack holds, for column tile t and k-step u (16 k each; nkt k-steps in the whole contraction),
@@ -1330,9 +1354,12 @@ template <int DP> struct SeqGeo {
 // (The body is a device function over ONE LDS buffer -- lds, SeqFwdLds<DP>::N floats -- so that a kernel can run it and then the
 //  backward's body on the same storage.  Returns false when this workgroup is done with the launch.)
 template <int DP> struct SeqFwdLds { static constexpr int N = 3 * SeqGeo<DP>::TILE + SeqGeo<DP>::RES + SeqGeo<DP>::UNI; };
-template <int DP, int HDC, bool EXACT, bool SPLIT, bool QUAD = false>
+// FB (seq_fb_kernel only): the backward body follows on the same LDS buffer.  The loss tail then leaves dlogits in LDS where the backward's
+// prologue expects them, and the wave partials of the loss in sX1: the backward body publishes them and takes the ticket (seq_bwd_body).
+template <int DP, int HDC, bool EXACT, bool SPLIT, bool QUAD = false, bool FB = false>
 __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds) {
   static_assert(!QUAD || (SPLIT && EXACT && DP == 128), "QUAD: the SPLIT kernels of d_model 128");
+  static_assert(!FB || QUAD, "FB: the fused launch of the QUAD schedule");
   using G = SeqGeo<DP>;
   constexpr int SX = G::SX, SH = G::SH, SQ = G::SQ, SRS = G::SRS, CW = G::CW, NK = G::NK;
   constexpr int HD = SeqHd<HDC>::HD;
@@ -1637,11 +1664,22 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
   };
   // ---- final encoder norm -> memory, then the output layer: [h logits | sigmoid v | 0.5 tanh o]
   auto output_layer = [&]() {
+    // (FB) the cold operands of the two stages behind the final norm -- the output product's weight fragments and bias (waves 0 and 1), this
+    // thread's three targets of the loss -- are requested HERE, in flight under the norm: each was a round trip of its own in front of a
+    // dependent stage.  (The fused launch always computes the loss: loss_y is there.)
+    SeqEdgeB<NK> ob;
+    float ly0 = 0.f, ly1 = 0.f, ly2 = 0.f;
+    if constexpr (FB) {
+      seq_mm_edge_load<false, true, NK>(ob, d, prm + a.out_w, d, GT_TGT, prm + a.out_b, wave, lane, zp);
+      if (tid < NROW * GT_VOICES) {
+        const float* yp = a.loss_y + (r0 + rb + tid / GT_VOICES) * GT_TGT + tid % GT_VOICES;
+        ly0 = yp[0]; ly1 = yp[GT_VOICES]; ly2 = yp[2 * GT_VOICES];
+      }
+    }
     seq_ln_fwd<DP, HALF>([&](int row, int c0, float (&z)[CW]) { SeqVec<CW>::ld(z, &sX[row * SX + c0]); }, sC, SX, d, prm + a.encn_w, prm + a.encn_b,
                          ws + a.memory + r0 * d, ws + a.enc_xhat + r0 * d, ws + a.enc_rstd + r0, tid, rb);
     GT_BARRIER();
-    seq_mm_edge<false, true, NK, HALF>(sC + rb * SX, SX, d, prm + a.out_w, d, GT_TGT, prm + a.out_b, wave, lane, zp,
-                                       [&](int n0, const f32x4& c0, const f32x4& c1, const float (&bi)[4]) {
+    auto out_epi = [&](int n0, const f32x4& c0, const f32x4& c1, const float (&bi)[4]) {
 #pragma unroll
       for (int h2 = 0; h2 < NH; ++h2) {
         const f32x4& c = h2 ? c1 : c0;
@@ -1657,7 +1695,9 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
           }
         }
       }
-    });
+    };
+    if constexpr (FB) seq_mm_edge_run<NK, HALF>(ob, sC + rb * SX, SX, d, GT_TGT, wave, lane, out_epi);
+    else seq_mm_edge<false, true, NK, HALF>(sC + rb * SX, SX, d, prm + a.out_w, d, GT_TGT, prm + a.out_b, wave, lane, zp, out_epi);
     if (a.loss_y == nullptr) return;
     const unsigned lwg_n = QUAD ? gridDim.x >> 1 : gridDim.x, lwg_id = QUAD ? (unsigned)half_id : blockIdx.x;   // workgroups that run the output layer
     // ---- fused loss: one thread per (own row, voice); partial sums of this workgroup -> loss_part[blockIdx][4]; the last workgroup
@@ -1670,13 +1710,25 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
       const int row = rb + tid / GT_VOICES, j = tid % GT_VOICES;
       const size_t base = (r0 + row) * GT_TGT + j;
       float gh, gv, go;
-      gt_loss_elem<true>(sR[row * 28 + j], sR[row * 28 + j + GT_VOICES], sR[row * 28 + j + 2 * GT_VOICES], a.loss_y[base],
-                         a.loss_y[base + GT_VOICES], a.loss_y[base + 2 * GT_VOICES], a.loss_penalty, invM, bce, mv, mo, ok, gh, gv, go);
+      if constexpr (!FB) { ly0 = a.loss_y[base]; ly1 = a.loss_y[base + GT_VOICES]; ly2 = a.loss_y[base + 2 * GT_VOICES]; }
+      gt_loss_elem<true>(sR[row * 28 + j], sR[row * 28 + j + GT_VOICES], sR[row * 28 + j + 2 * GT_VOICES], ly0, ly1, ly2, a.loss_penalty, invM,
+                         bce, mv, mo, ok, gh, gv, go);
       ws[a.dlogits + base] = gh; ws[a.dlogits + base + GT_VOICES] = gv; ws[a.dlogits + base + 2 * GT_VOICES] = go;
+      // (FB) ... and into the A tile of the output-layer dgrad: own rows x 27, zero-padded to 32 columns, in sC -- the backward's sC, free since
+      // the barrier above (the output product was its only reader); the global copy stays: the tail's output-layer weight gradient reads it
+      if constexpr (FB) { sC[row * SX + j] = gh; sC[row * SX + j + GT_VOICES] = gv; sC[row * SX + j + 2 * GT_VOICES] = go; }
+    }
+    if constexpr (FB) {
+      constexpr int ZC = 32 - GT_TGT;
+      const int t = tid - NROW * GT_VOICES;
+      if (t >= 0 && t < NROW * ZC) sC[(rb + t / ZC) * SX + GT_TGT + t % ZC] = 0.f;
     }
     bce = gt_wave_sum(bce); mv = gt_wave_sum(mv); mo = gt_wave_sum(mo); ok = gt_wave_sum(ok);
     if (lane == 0) { red[wave * 4 + 0] = bce; red[wave * 4 + 1] = mv; red[wave * 4 + 2] = mo; red[wave * 4 + 3] = ok; }
     GT_BARRIER();
+    // (FB: the eight waves' partials stay in red -- sX1, the backward's sDZ, which nothing writes before the norm2 backward; the backward
+    // body's prologue adds them, publishes them and takes the ticket from a wave that is idle there, and nobody waits for the result)
+    if constexpr (FB) return;
     if (tid == 0 && cpart != 0) red[32] = 0.0f;                // (QUAD, fused with backward phase 0: partner 1 computed dlogits for itself; the statistics are partner 0's)
     if (tid == 0 && cpart == 0) {
 #pragma unroll
@@ -1775,6 +1827,30 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
   }
   return true;
 }
+// seq_fb_kernel: the last arriver of the loss ticket -- the wave whose lane 0 holds lwg_n - 1 in tick -- adds all partials in the fixed order of
+// output_layer's own finish (quantity q: lane l takes workgroups l, l + 64, ..., then the xor tree), writes the statistics and re-arms the
+// ticket.  One wave, no barrier; the four quantities of a workgroup are requested together (one round trip per 64 workgroups).
+__device__ __forceinline__ void seq_loss_finish(const SeqArgs& a, const unsigned tick, const unsigned lwg_n, const int lane) {
+  if (__shfl((lane == 0 && tick == lwg_n - 1) ? 1.0f : 0.0f, 0) == 0.0f) return;
+  const float invM = 1.0f / (float)(a.B * 32);
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (unsigned bk = lane; bk < lwg_n; bk += 64) {
+    float v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = gt_pub_load(a.loss_part + bk * 4 + q);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] += v[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s[q] = gt_wave_sum(s[q]) * invM;
+  if (lane == 0) {
+    a.loss_stats[0] = s[0] + s[1] + s[2];
+    a.loss_stats[1] = s[3] * (1.0f / GT_VOICES);
+    a.loss_stats[2] = 0.f;
+    a.loss_stats[3] = s[0]; a.loss_stats[4] = s[1]; a.loss_stats[5] = s[2]; a.loss_stats[6] = 0.f; a.loss_stats[7] = 0.f;
+    *a.loss_ticket = 0u;                                      // re-arm for the next step
+  }
+}
 template <int DP, int HDC, bool EXACT, bool SPLIT, bool QUAD = false>
 __global__ __launch_bounds__(GT_SEQ_NT) void seq_fwd_kernel(SeqArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[SeqFwdLds<DP>::N];
@@ -1856,13 +1932,29 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
 
   // ---- output layer dgrad: dmem = dlogits Wout (A tile: own rows x 27, zero-padded to 32 columns); final norm backward -> the
   // gradient w.r.t. the last layer's output (sZ, in place; its dz is not a weight-gradient operand)
+  unsigned tick = ~0u;                                       // (QUAD, a.fb_handover) what the loss ticket returned: lane 0 of the last wave, partner 0
+  constexpr bool PFQ = QUAD;                                // QUAD phase 0: the two first LayerNorm backward passes' saved operands are requested at the prologue's head
+  SeqLnBwdPre<CW> lbep, lbqp;                                // (final norm, norm2 of layer L - 1)
   auto prologue = [&]() {
-    for (int e = tid; e < NROW * 32; e += GT_SEQ_NT) {
-      const int r = rb + (e >> 5), c = e & 31;
-      sC[r * SX + c] = *(c < GT_TGT ? ws + a.dlogits + (r0 + r) * GT_TGT + c : zp);
+    // (PFQ) x-hat / rstd / gamma of the final norm's backward and of the last layer's norm2 backward: three small loads per thread each, in
+    // flight under the output-layer dgrad (and the final norm's backward) instead of one round trip at the head of each pass
+    // (no branch around the loads: threads 256 .. 511 request a copy they do not use, as at d_model 32 / 64)
+    if constexpr (PFQ) {
+      const float* wq = ws + (int64_t)(a.L - 1) * a.wstride;
+      seq_ln_bwd_pre<CW>(lbep, d, ws + a.enc_xhat + r0 * d, ws + a.enc_rstd + r0, prm + a.encn_w, tid, rb);
+      seq_ln_bwd_pre<CW>(lbqp, d, wq + a.w0.xhat2 + r0 * d, wq + a.w0.rstd2 + r0, prm + (int64_t)(a.L - 1) * a.pstride + a.p0.n2w, tid, rb);
     }
-    if (!SPLIT) load_rows(sH, SH, ws + a.w0.hact + (int64_t)(a.L - 1) * a.wstride + r0 * F, F, 0, 32);
-    GT_BARRIER();
+    // (QUAD, a.fb_handover: the forward body's loss tail wrote this very tile -- same rows, same sC -- before the barrier between the bodies)
+    bool din = false;
+    if constexpr (QUAD) din = a.fb_handover != 0;
+    if (!din) {
+      for (int e = tid; e < NROW * 32; e += GT_SEQ_NT) {
+        const int r = rb + (e >> 5), c = e & 31;
+        sC[r * SX + c] = *(c < GT_TGT ? ws + a.dlogits + (r0 + r) * GT_TGT + c : zp);
+      }
+      if (!SPLIT) load_rows(sH, SH, ws + a.w0.hact + (int64_t)(a.L - 1) * a.wstride + r0 * F, F, 0, 32);
+      GT_BARRIER();
+    }
     seq_mm_edge<true, true, 2, HALF>(sC + rb * SX, SX, GT_TGT, prm + a.out_w, d, d, nullptr, wave, lane, zp,
                                      [&](int n0, const f32x4& c0, const f32x4& c1, const float (&)[4]) {
       const int col = n0 + 4 * lg;
@@ -1870,10 +1962,27 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
       if (!HALF) *reinterpret_cast<float4*>(&sZ[(16 + l16) * SX + col]) = make_float4(c1[0], c1[1], c1[2], c1[3]);
     });
     GT_BARRIER();
+    // (QUAD, a.fb_handover) THE LOSS TICKET.  The two LayerNorm backward passes that follow run on waves 0 .. 3; the last wave, idle in both and
+    // with no store of hvo or dlogits behind it, adds the forward body's wave partials (still in its red = sDZ; lane q: quantity q, waves in
+    // order, as output_layer does), publishes them as write-through stores, drains them and takes the ticket.  Nobody waits for the add:
+    // nothing in this phase depends on it, the wave meets its return at the next wait for a load of its own (the FFN2 dgrad's fragments, two
+    // passes later), and the last arriver finishes the statistics in the NEXT window of this kind, the norm1 backward (chain).  Exactly once
+    // per output-layer workgroup and launch: behind the forward pair exchange, and partner 0 -- the statistics are its alone -- cannot
+    // abandon the pass in the host emulator once it is here (partner 1's backward granules were sent before partner 0 got past the forward's).
+    if constexpr (QUAD) {
+      if (a.fb_handover != 0 && cpart == 0 && wave == GT_SEQ_WAVES - 1) {
+        if (lane < 4) {
+          float t = sDZ[lane];
+          for (int w = 1; w < GT_SEQ_WAVES; ++w) t += sDZ[w * 4 + lane];
+          gt_pub_store(a.loss_part + half_id * 4 + lane, t);
+        }
+        if (lane == 0) tick = gt_pub_ticket(a.loss_ticket);
+      }
+    }
     {
       SeqDropK nd = dk; nd.thr = 0u;
       seq_ln_bwd<DP, HALF>([&](int row, int c0, float (&g)[CW]) { SeqVec<CW>::ld(g, &sZ[row * SX + c0]); }, sZ, sC, SX, d, ws + a.enc_xhat + r0 * d,
-                           ws + a.enc_rstd + r0, prm + a.encn_w, nd, 0u, 0u, nullptr, nullptr, sP, tid, rb);
+                           ws + a.enc_rstd + r0, prm + a.encn_w, nd, 0u, 0u, nullptr, nullptr, sP, tid, rb, PFQ ? &lbep : nullptr);
     }
     GT_BARRIER();
     if (sv0) seq_ln_part<DP, HALF>(sP, part_at(0), d, tid);
@@ -1909,7 +2018,14 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     const int fc0 = QUAD ? cpart * (F >> 1) : 0, fcn = QUAD ? F >> 1 : F;
     const int hq4 = fcn >> 2, hn = 16 * hq4;
     auto hoff = [&](const int u) { const int e = tid + u * GT_SEQ_NT, ec = e < hn ? e : hn - 1; return (unsigned)((rb + ec / hq4) * F + fc0 + (ec % hq4) * 4); };
-    if (SPLIT) {
+    // (QUAD, a.fb_handover -- seq_fb_kernel, fromg: this workgroup's forward body has just run on the same LDS buffer, and the forward's sH and this
+    // sH are one address (the first five regions of SeqFwdLds<128> and SeqBwdLds<128> coincide): the tile FFN1 wrote -- rows rb .., columns
+    // fc0 .. fc0 + fcn, the very values seq_tile_out_cols sent to w0.hact -- is still there.  INVARIANT: nothing between the forward's FFN2 and
+    // the FFN2 dgrad below writes sU: norm2 writes sX, the output layer sC / sR / sX1, the prologue sC / sZ / sP, the norm2 backward sDZ / sC / sP.
+    // Whoever adds a stage in between keeps its hands off sU, or this request and copy come back.)
+    bool hin = false;
+    if constexpr (QUAD) hin = a.fb_handover != 0 && fromg;
+    if (SPLIT && !hin) {
       const float* src = wl + a.w0.hact + r0 * F;
       hp0 = *reinterpret_cast<const float4*>(src + hoff(0)); hp1 = *reinterpret_cast<const float4*>(src + hoff(1));
       hp2 = *reinterpret_cast<const float4*>(src + hoff(2)); hp3 = *reinterpret_cast<const float4*>(src + hoff(3));
@@ -1928,9 +2044,9 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
           for (int e = 0; e < CW; ++e) g[e] += r[e];
         }
       }, sDZ, sC, SX, d, wl + a.w0.xhat2 + r0 * d, wl + a.w0.rstd2 + r0, pl + a.p0.n2w, dk, key, idxd, sv0 ? tl + a.t0.dzA + r0 * d : nullptr,
-                           (dk.thr && sv0) ? tl + a.t0.dzAm + r0 * d : nullptr, sP, tid, rb, (PFBLN && have_lbp) ? &lb2p : nullptr);
+                           (dk.thr && sv0) ? tl + a.t0.dzAm + r0 * d : nullptr, sP, tid, rb, PFQ ? &lbqp : (PFBLN && have_lbp) ? &lb2p : nullptr);
     }
-    if (SPLIT) {
+    if (SPLIT && !hin) {
       auto hst = [&](const int u, const float4& v) { const int e = tid + u * GT_SEQ_NT; if (e < hn) *reinterpret_cast<float4*>(sH + (rb + e / hq4) * SH + fc0 + (e % hq4) * 4) = v; };
       hst(0, hp0); hst(1, hp1); hst(2, hp2); hst(3, hp3);
     }
@@ -1985,6 +2101,10 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
     // ---- norm1 backward: g1 = parts + dz2 -> dz1 -> sDZ, dz1 * mask(dropout1) -> sC.  Whole: the saved qkv tile of this layer is
     // requested now (ALIAS: over the FFN tile, which the FFN1 dgrad has finished reading); SPLIT loads it at the next phase's start
     if (!SPLIT) load_rows(sQ, SQ, wl + a.w0.qkv + r0 * 3 * d, 3 * d, 0, 32);
+    // (QUAD, a.fb_handover) the last arriver of the loss ticket finishes the statistics here, on the wave that took it, idle in this pass too
+    if constexpr (QUAD) {
+      if (a.fb_handover != 0 && cpart == 0 && wave == GT_SEQ_WAVES - 1) seq_loss_finish(a, tick, gridDim.x >> 1, lane);
+    }
     {
       const uint32_t key = seq_key(dk, site0 + GT_SITE_DROP1);
       const int parts = seq_splitk_parts(d);
@@ -2265,14 +2385,17 @@ __global__ __launch_bounds__(GT_SEQ_NT) void seq_bwd_kernel(SeqArgs a) {
 // last-workgroup-end: 4 us) and phase 0's reload of what this workgroup had just written.  Both partners run the whole forward phase here
 // (the last layer's pair exchange in both directions, the output layer and dlogits twice, the statistics once), then the backward body on
 // the same LDS buffer: it reads its operands from global memory as ever -- this workgroup's own stores of a moment ago, ordered by the
-// barrier below (workgroup scope: one CU, one L1).
+// barrier below (workgroup scope: one CU, one L1) -- EXCEPT what is still in that buffer (b.fb_handover): the last layer's hact half in sU
+// (chain) and dlogits in sC (output_layer's loss tail -> prologue); the global copies are written all the same, for the riders and the tail.
+// The loss ticket moves into the backward body: taken by a wave that is idle under the LayerNorm backward passes, waited for by nobody.
 template <int HDC>
 __global__ __launch_bounds__(GT_SEQ_NT) void seq_fb_kernel(SeqArgs a) {
   constexpr int N = SeqBwdLds<128>::N > SeqFwdLds<128>::N ? SeqBwdLds<128>::N : SeqFwdLds<128>::N;
   __shared__ __attribute__((aligned(16))) float lds[N];
-  if (!seq_fwd_body<128, HDC, true, true, true>(a, lds)) return;
+  if (!seq_fwd_body<128, HDC, true, true, true, true>(a, lds)) return;
   __syncthreads();
   SeqArgs b = a;
   b.phase = 0;
+  b.fb_handover = 1;                                            // (the backward body's copy only: the forward body reads fuse_b0)
   seq_bwd_body<128, 32, true, true, true>(b, lds);
 }

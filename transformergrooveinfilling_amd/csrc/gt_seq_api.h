@@ -29,6 +29,8 @@ struct SeqArgs {
   int64_t xchg;                                              // QUAD forward: the pair-exchange region (8 header granules, then one 16 KB slot per
                                                              // workgroup; zero between launches -- gt_workspace_init); -1: none
   int64_t xchg_b; int fuse_b0;                               // QUAD, fused step: the last forward launch goes on into backward phase 0 (seq_fb_kernel), whose pair exchange uses the region at xchg_b
+  int fb_handover;                                           // set by seq_fb_kernel on the BACKWARD body's copy of the arguments only: this workgroup's forward
+                                                             // body has just run on the same LDS buffer and left the last layer's hact half, dlogits and the loss's wave partials in it
   int spin_max;                                              // bound of the pair exchange's polling loop (gt_set_xchg_spin_max; default GT_XCHG_SPIN_MAX)
   int quad_pro;                                              // QUAD forward: input layer + in-proj(0) ran as a prologue launch (phase -1)
   int phase;                                                 // SPLIT kernels: which phase this launch runs
