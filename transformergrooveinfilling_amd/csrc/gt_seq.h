@@ -1354,6 +1354,44 @@ template <int DP> struct SeqGeo {
 // (The body is a device function over ONE LDS buffer -- lds, SeqFwdLds<DP>::N floats -- so that a kernel can run it and then the
 //  backward's body on the same storage.  Returns false when this workgroup is done with the launch.)
 template <int DP> struct SeqFwdLds { static constexpr int N = 3 * SeqGeo<DP>::TILE + SeqGeo<DP>::RES + SeqGeo<DP>::UNI; };
+// A SPLIT phase's state tiles, requested as ONE group (the EXACT d_model-128 kernels): a tile copy written as a loop -- load, wait, LDS store
+// per trip -- pays one cold round trip through the fabric per trip (the tiles were written by other workgroups a launch earlier), six or
+// seven in a row at a phase's head.  seq_tile_request issues a thread's NP 16-byte pieces of a tile back to back into named registers (an
+// indexed array went to scratch), seq_tile_store writes them to LDS once every request of the group is out.  Piece u is element tid + u *
+// GT_SEQ_NT of nrows x Q4 pieces: rows rb .. of a tile whose rows are ld floats apart in global memory, Q4 pieces from column c0 on.
+// NP * GT_SEQ_NT pieces cover the tile exactly (the caller's static_assert): no bound, no clamp, no branch around a load.
+// Measured at the headline shape: the backward heads' "state" window 6.7-7.7 k -> 3.6-3.8 k cycles and their phases 3 k shorter, the
+// forward heads' "load state" 5.8-6.6 k -> 5.7-5.9 k; 0.1908-0.1909 -> 0.1885-0.1888 ms per step.
+struct SeqTilePre { float4 p0, p1, p2, p3, p4, p5; };
+template <int NP, int Q4>
+__device__ __forceinline__ SeqTilePre seq_tile_request(const float* src, const int ld, const int rb, const int c0, const int tid) {
+  static_assert(NP >= 1 && NP <= 6, "six named pieces");
+  SeqTilePre t = SeqTilePre();
+  auto at = [&](const int u) {
+    const int e = tid + u * GT_SEQ_NT;
+    return *reinterpret_cast<const float4*>(src + (unsigned)((rb + e / Q4) * ld + c0 + (e % Q4) * 4));
+  };
+  t.p0 = at(0);
+  if constexpr (NP > 1) t.p1 = at(1);
+  if constexpr (NP > 2) t.p2 = at(2);
+  if constexpr (NP > 3) t.p3 = at(3);
+  if constexpr (NP > 4) t.p4 = at(4);
+  if constexpr (NP > 5) t.p5 = at(5);
+  return t;
+}
+template <int NP, int Q4>
+__device__ __forceinline__ void seq_tile_store(float* dst, const int str, const int rb, const int c0, const int tid, const SeqTilePre& t) {
+  auto st = [&](const int u, const float4& v) {
+    const int e = tid + u * GT_SEQ_NT;
+    *reinterpret_cast<float4*>(dst + (rb + e / Q4) * str + c0 + (e % Q4) * 4) = v;
+  };
+  st(0, t.p0);
+  if constexpr (NP > 1) st(1, t.p1);
+  if constexpr (NP > 2) st(2, t.p2);
+  if constexpr (NP > 3) st(3, t.p3);
+  if constexpr (NP > 4) st(4, t.p4);
+  if constexpr (NP > 5) st(5, t.p5);
+}
 // FB (seq_fb_kernel only): the backward body follows on the same LDS buffer.  The loss tail then leaves dlogits in LDS where the backward's
 // prologue expects them, and the wave partials of the loss in sX1: the backward body publishes them and takes the ticket (seq_bwd_body).
 template <int DP, int HDC, bool EXACT, bool SPLIT, bool QUAD = false, bool FB = false>
@@ -1795,6 +1833,18 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
     if (l == 0 && !pro) {
       input_layer(AllRows{});
       in_proj(0, AllRows{});
+    } else if constexpr (SPLIT && EXACT && DP == 128) {
+      // the same three tiles as below, six 16-byte pieces per thread, requested as one group (seq_tile_request)
+      static_assert(16 * (DP / 4) == GT_SEQ_NT && 32 * (2 * DP / 4) == 4 * GT_SEQ_NT, "1 + 4 + 1 pieces per thread cover the three tiles");
+      const float* gx = ws + (l == 0 ? a.x0 : (int64_t)(l - 1) * a.wstride + a.w0.xout) + r0 * DP;
+      const float* gq = ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * DP;
+      const SeqTilePre px = seq_tile_request<1, DP / 4>(gx, DP, rb, 0, tid);
+      const SeqTilePre pkv = seq_tile_request<4, 2 * DP / 4>(gq, 3 * DP, 0, DP, tid);
+      const SeqTilePre pq = seq_tile_request<1, DP / 4>(gq, 3 * DP, rb, 0, tid);
+      seq_tile_store<1, DP / 4>(sX, SX, rb, 0, tid, px);
+      seq_tile_store<4, 2 * DP / 4>(sQ, SQ, 0, DP, tid, pkv);
+      seq_tile_store<1, DP / 4>(sQ, SQ, rb, 0, tid, pq);
+      GT_BARRIER();
     } else {
       load_rows(sX, SX, ws + (l == 0 ? a.x0 : (int64_t)(l - 1) * a.wstride + a.w0.xout) + r0 * d, d, rb, NROW);   // own rows of the layer input
       // k / v of the whole sequence, q of the own rows (the other half's queries are its own business: a sixth of the bytes less)
@@ -2348,13 +2398,27 @@ __device__ __forceinline__ void seq_bwd_body(const SeqArgs& a, float* const lds)
                                        reinterpret_cast<const uint32_t*>(ws + a.amask + (int64_t)l * a.amask_stride) + b * a.H * 32, tid);
     }
     SeqRdPre rdp = SeqRdPre();
-    if constexpr (OWN && !PAD) rdp = rd_tile_request(gdctx, gctx);              // (sZ: complete after rd_tile_finish below)
-    else if constexpr (OWN) rd_small_stage(gdctx, gctx);
-    else load_rows(sZ, SX, gdctx, d, 0, 32);
-    load_rows(sQ, SQ, ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * d, 3 * d, 0, 32);
-    load_rows(sDZ, SX, ws + (int64_t)l * a.tstride + a.t0.dzB + r0 * d, d, rb, NROW);
-    chain_prefetch(l);
-    if constexpr (OWN && !PAD) rd_tile_finish(rdp);
+    if constexpr (OWN && !PAD && EXACT && DP == 128) {
+      // all of the state as one group (seq_tile_request): 6 + 1 + 4 pieces per thread, then the chain's small operands, then the LDS stores.
+      // qkv and dz in front of the dctx / ctx pieces: their stores are plain copies that leave while the last pieces -- the ones the row sums
+      // wait for -- arrive (the other order, rd first: "state" 3.8-4.4 k cycles against 3.6-3.8 k, the step 0.4-0.7 us longer)
+      static_assert(32 * (3 * DP / 4) == 6 * GT_SEQ_NT && 16 * (DP / 4) == GT_SEQ_NT, "6 + 1 pieces per thread cover the qkv and dz tiles");
+      const SeqTilePre pq = seq_tile_request<6, 3 * DP / 4>(ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * DP, 3 * DP, 0, 0, tid);
+      const SeqTilePre pz = seq_tile_request<1, DP / 4>(ws + (int64_t)l * a.tstride + a.t0.dzB + r0 * DP, DP, rb, 0, tid);
+      rdp = rd_tile_request(gdctx, gctx);                                       // (sZ: complete after rd_tile_finish below)
+      chain_prefetch(l);
+      seq_tile_store<6, 3 * DP / 4>(sQ, SQ, 0, 0, tid, pq);
+      seq_tile_store<1, DP / 4>(sDZ, SX, rb, 0, tid, pz);
+      rd_tile_finish(rdp);
+    } else {
+      if constexpr (OWN && !PAD) rdp = rd_tile_request(gdctx, gctx);              // (sZ: complete after rd_tile_finish below)
+      else if constexpr (OWN) rd_small_stage(gdctx, gctx);
+      else load_rows(sZ, SX, gdctx, d, 0, 32);
+      load_rows(sQ, SQ, ws + (int64_t)l * a.wstride + a.w0.qkv + r0 * 3 * d, 3 * d, 0, 32);
+      load_rows(sDZ, SX, ws + (int64_t)l * a.tstride + a.t0.dzB + r0 * d, d, rb, NROW);
+      chain_prefetch(l);
+      if constexpr (OWN && !PAD) rd_tile_finish(rdp);
+    }
     GT_BARRIER();
     GT_STAMP(400 + 4 * a.phase);
     SeqB<8> bqpre;
