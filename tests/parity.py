@@ -1079,3 +1079,109 @@ def check_bucketed_backward(backend, cfg, B, p, n_buckets, exact, seq=True):
     if n_buckets == 2:
         o1, c1 = buckets[1]
         assert np.abs(gw[o1:o1 + c1]).max() > 0 and np.abs(g2[o1:o1 + c1] - gw[o1:o1 + c1]).max() > 0   # the first half really stops early
+
+
+# ---- what a fused step hands from its forward to its backward stays inside that call (check_step_handoffs) -------------------------------
+# The launches of each form on d128 / H4 / F64 / L2 at batch 2 as (family, phase or kind), written down from the GT_TRACE_DISPATCH lines of
+# the commit BEFORE the hand-offs became arguments (profiles/step_handoffs_trace.txt): the QUAD schedule with riders and head_dim 32,
+# where gt_train_step's last forward launch runs backward phase 0 and takes the loss along.
+HANDOFF_CFG, HANDOFF_B = dict(d_model=128, n_heads=4, dim_feedforward=64, num_encoder_layers=2, num_decoder_layers=0, embedding_size_src=16), 2
+_FWD = [("seq_pack", None), ("seq_fwd", 0), ("seq_fwd", 1)]
+HANDOFF_WHOLE = _FWD + [("seq_bwd", 1), ("seq_bwd", 2), ("seq_tail", "tail"), ("update", "folded_pack")]          # gt_step_launches = 7
+HANDOFF_BACKWARD = [("kernel", None), ("seq_bwd", 0), ("seq_bwd", 1), ("seq_bwd", 2), ("seq_tail", "tail")]       # heads_bwd first
+HANDOFF_SKIP2, HANDOFF_SKIP3 = _FWD + [("seq_bwd", 1), ("seq_tail", "out_early")], [("seq_bwd", 2), ("seq_tail", "tail")]
+HANDOFF_STEP_LOSS = _FWD + [("kernel", None), ("seq_bwd", 0), ("seq_bwd", 1), ("seq_bwd", 2), ("seq_tail", "tail"), ("update", "folded_pack")]
+
+
+def check_step_handoffs(backend, read_trace):
+    """One Runner, back to back: a whole gt_train_step, gt_forward + gt_loss + gt_backward, gt_train_step(skip_update 2, then 3), a whole
+    gt_train_step_loss, a gt_train_step that fails (stats = NULL), another whole gt_train_step.  read_trace() returns the [dispatch] lines
+    since its last call (the caller has GT_TRACE_DISPATCH on).  Each part keeps its bar: whole steps check_train_step's (loss 2e-5,
+    check_update), forward / loss / backward check_step's, the two-call backward check_step's gradient bar."""
+    cfg, B, lr, pen = dict(HANDOFF_CFG, dropout=0.1), HANDOFF_B, 0.05, 0.38
+    r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=lr)
+    r.set_params(ng.init_params(cfg, seed=9, perturb=0.05))
+    x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=4)
+    y64 = y.astype(np.float64)
+    n = r.lib.cdll.gt_step_launches(ctypes.byref(r.c))
+    assert n == len(HANDOFF_WHOLE), n
+    seq = lambda tr: [(f, d.get("phase", d.get("kind"))) for f, d in tr]
+    fused = lambda tr: [d["fuse_b0"] for f, d in tr if f in ("seq_fwd", "seq_bwd")]
+
+    def oracle(before):
+        """the fp64 step from the device's parameters `before` with this step's masks -> (stats, cache, d loss / d hvo, gradients)"""
+        P64 = {k: np.asarray(v, np.float64) for k, v in before.items()}
+        hvo, C = ng.forward(P64, cfg, x, rng=(77, 5, r.step_state().step), dtype=np.float64)
+        stats, dpred = ng.calculate_loss(hvo, y64, pen)
+        return P64, hvo, stats, C, dpred
+
+    def grads_of(P64, C, dpred):
+        assert check_decisions_current(r, C) >= len(C["enc"]) + 1
+        assert adopt_device_kinks(r, C, cfg) <= kink_bound(r, cfg)
+        return ng.backward(P64, cfg, C, dpred, dtype=np.float64)
+
+    def whole_step(call, tag):
+        before = r.unflatten(r.params.numpy())
+        P64, _, want, C, dpred = oracle(before)
+        read_trace()
+        stats = call()
+        tr = read_trace()
+        assert abs(stats[0] - want[0]) < 2e-5 * max(1, abs(want[0])), (tag, stats[0], want[0])
+        check_update(before, r.unflatten(r.params.numpy()), grads_of(P64, C, dpred), lr, tag=tag)
+        return tr
+
+    def grads_within_bar(G, Gr, tag):
+        for k in Gr:
+            err = float(np.abs(G[k] - Gr[k]).max() / max(np.abs(Gr[k]).max(), 1e-5))
+            assert err < GRAD_TOL, (tag, k, err)
+
+    first = whole_step(lambda: r.train_step(x, y, pen), "first whole step")
+    assert seq(first) == HANDOFF_WHOLE and fused(first) == [0, 1, 1, 1], first
+    # a plain forward takes no loss along and runs no backward phase; the gt_backward after it runs phase 0 itself
+    P64, hvo_ref, _, C, _ = oracle(r.unflatten(r.params.numpy()))
+    read_trace()
+    hvo = r.forward(x, None, train=True)
+    fwd = read_trace()
+    assert seq(fwd) == _FWD and fused(fwd) == [0, 0], fwd
+    dpred = _check_forward_and_loss(r, hvo, hvo_ref, C, y, pen, True)
+    assert seq(read_trace()) == [("kernel", None)]
+    G = r.backward(train=True)
+    bwd = read_trace()
+    assert seq(bwd) == HANDOFF_BACKWARD and fused(bwd) == [0, 0, 0], bwd
+    grads_within_bar(G, grads_of(P64, C, dpred), "gt_backward")
+    # the two halves of the bucketed backward: the first call's forward runs phase 0, the second call starts at phase 2
+    P64, _, want, C, dpred = oracle(r.unflatten(r.params.numpy()))
+    read_trace()
+    stats = r.train_step(x, y, pen, skip_update=2)
+    half1 = read_trace()
+    r.train_step(x, y, pen, skip_update=3)
+    half2 = read_trace()
+    r._grads_dirty = True
+    assert seq(half1) == HANDOFF_SKIP2 and fused(half1) == [0, 1, 1], half1
+    assert seq(half2) == HANDOFF_SKIP3 and fused(half2) == [0], half2
+    assert abs(stats[0] - want[0]) < 2e-5 * max(1, abs(want[0])), (stats[0], want[0])
+    grads_within_bar(r.unflatten(r.grads.numpy()), grads_of(P64, C, dpred), "skip_update 2 + 3")
+    # gt_train_step_loss (neutral options: gt_loss's numbers): the loss between forward and backward, phase 0 a backward launch again
+    from transformergrooveinfilling_amd import _lib
+    lo = _lib.make_loss_opts(penalty_h=pen)
+    voice, scratch = r.Buf(np.zeros(36, np.float32)), r.Buf(np.zeros(int(r.lib.cdll.gt_loss_scratch_floats(ctypes.byref(r.c))), np.float32))
+
+    def step_loss():
+        r.grads = r.Buf(np.zeros(r.total, np.float32))
+        r._grads_dirty = False
+        r.lib.call("gt_train_step_loss", ctypes.byref(r.c), 0, r.params.ptr, r.grads.ptr, None, None, r.pe.ptr, r.x.ptr, r.y.ptr, ctypes.byref(lo),
+                   voice.ptr, scratch.ptr, r.hvo.ptr, r.stats.ptr, r.tgt.ptr, r.ws.ptr, r.state.ptr, 0, r.stream)
+        return r.stats.numpy().copy()
+    by_opts = whole_step(step_loss, "gt_train_step_loss")
+    assert len(by_opts) == n + 2 and seq(by_opts) == HANDOFF_STEP_LOSS and fused(by_opts) == [0, 0, 0, 0, 0], by_opts
+    # a call that fails launches nothing, changes nothing and leaves nothing behind for the step after it
+    keep = [b.numpy().copy() for b in (r.params, r.grads, r.state, r.hvo)]
+    read_trace()
+    rc = r.lib.cdll.gt_train_step(ctypes.byref(r.c), 0, r.params.ptr, r.grads.ptr, None, None, r.pe.ptr, r.x.ptr, r.y.ptr, ctypes.c_float(pen),
+                                  r.hvo.ptr, None, r.tgt.ptr, r.ws.ptr, r.state.ptr, 0, r.stream)
+    assert rc != 0 and b"stats" in r.lib.cdll.gt_last_error(), rc
+    assert read_trace() == [], "gt_train_step(stats = NULL) launched before it failed"
+    assert all(np.array_equal(a, b.numpy()) for a, b in zip(keep, (r.params, r.grads, r.state, r.hvo)))
+    last = whole_step(lambda: r.train_step(x, y, pen), "last whole step")
+    assert last == first, (first, last)
+    assert r.step_state().step == 3 and r.step_state().opt_step == 3

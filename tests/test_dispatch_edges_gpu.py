@@ -305,3 +305,12 @@ def test_seq_bucketed_backward_past_quad(capfd, request):
     ride = _schedule(trace)[2]
     assert nb == (2 if ride else 1), (nb, ride)
     assert ride == 1 and dispatched(trace, "seq_tail", kind="out_early")
+
+
+def test_step_handoffs_stay_inside_their_call(capfd):
+    """the GPU twin of tests/test_emu_kernels.py::test_step_handoffs_stay_inside_their_call (same shape, same launch sequences)"""
+    os.environ["GT_TRACE_DISPATCH"] = "1"
+    try:
+        parity.check_step_handoffs("hip", lambda: parse_dispatch(capfd.readouterr().err))
+    finally:
+        del os.environ["GT_TRACE_DISPATCH"]

@@ -414,6 +414,18 @@ def test_dispatch_trace_shape(capfd):
     np.testing.assert_equal(capfd.readouterr().err.count("[dispatch]"), 0)          # off again: nothing is printed
 
 
+def test_step_handoffs_stay_inside_their_call(capfd):
+    """What gt_train_step hands from its forward to its backward (the loss taken along, backward phase 0 already run, weight packs current)
+    reaches no other call: parity.check_step_handoffs, launch by launch from the trace.  GPU twin: tests/test_dispatch_edges_gpu.py."""
+    import os
+    from harness import parse_dispatch
+    os.environ["GT_TRACE_DISPATCH"] = "1"
+    try:
+        parity.check_step_handoffs("emu", lambda: parse_dispatch(capfd.readouterr().err))
+    finally:
+        del os.environ["GT_TRACE_DISPATCH"]
+
+
 def test_config_flag_no_ln_xchg_overrules_forced_exchange(capfd):
     """gt_config.flags (what StepEngine sets after an exchange time-out) against the process-wide switch: NO_LN_XCHG wins over a forced
     gt_set_ln_exchange(1) -- checked against the oracle, the trace proving that the norms ran as row passes"""

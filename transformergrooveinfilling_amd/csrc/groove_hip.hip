@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gt_attn.h"
@@ -431,8 +432,12 @@ extern "C" int gt_ws_find(const gt_config* cfg, const char* name, int layer, int
 static thread_local int g_bf16 = 0;                  // precision of the call being enqueued (set by make_ctx / the entry points)
 
 // ------------------------------------------------------------------------------------ launch helpers
+// The sequence-resident schedule of ONE call (seq_plan(), below the rules it wraps): an entry point asks once, and the forward, the
+// backward, the bucket cut and the update of that call all read the same answers.  hc: the head-dim class of the kernels' instantiations.
+struct SeqPlan { bool seq, split, quad, ride, fuse_b0; int hc; };
 struct Ctx {
   gt_config c;
+  SeqPlan plan;              // all false from make_ctx; forward, backward and the fused step fill it (seq_plan)
   PLayout P;
   WLayout W;
   int M, d, F, H, hd;
@@ -941,6 +946,7 @@ static int make_ctx(Ctx& x, const gt_config* cfg, const float* params, float* gr
   if (!params || !ws) return gt_fail("params / ws must not be NULL");
   g_bf16 = cfg->precision ? 1 : 0;
   x.c = *cfg;
+  x.plan = SeqPlan{};
   x.P = param_layout(*cfg);
   x.W = ws_layout(*cfg);
   x.M = cfg->batch * 32; x.d = cfg->d_model; x.F = cfg->dim_ff; x.H = cfg->n_heads; x.hd = x.d / x.H;
@@ -1036,7 +1042,6 @@ static int self_attn_fwd(const Ctx& x, const LayerP& p, const LayerW& w, const f
                        lsite(gl, GT_SITE_DROP1));
 }
 
-static bool use_seq(const gt_config& c);
 // ---- sequence-resident kernels (gt_seq.h): one workgroup per sequence walks the whole encoder -------------------------------
 // g_seq: 0 = off (GT_SEQ=0 / gt_set_seq(0)), 1 = every supported shape (GT_SEQ=1 / gt_set_seq(1): tests), 2 = by measurement (default):
 // always at d_model <= 64 (C1 1.9x, ClosedHH YAML 1.15x over one kernel per op) and at d_model 128 (two workgroups per sequence
@@ -1101,7 +1106,7 @@ extern "C" int gt_set_seq_ride(int on) { g_seq_ride = on < 0 ? -1 : on != 0; ret
 #define GT_SEQ_RIDE_LAST_PCT 50
 #endif
 static bool seq_ride(const gt_config& c) {
-  if (c.d_model != 128 || c.dim_ff % 16 != 0 || !seq_split(c)) return false;
+  if (c.d_model != 128 || c.dim_ff % 16 != 0) return false;     // (seq_plan asks for a SPLIT schedule only)
   if (g_seq_ride < 0) { const char* e = getenv("GT_SEQ_RIDE"); if (e) g_seq_ride = e[0] != '0'; }
   const int idle = seq_cu_count() - 2 * c.batch;
   if (g_seq_ride >= 0) return g_seq_ride != 0 && idle >= 1;
@@ -1113,7 +1118,7 @@ static bool seq_ride(const gt_config& c) {
 static int g_seq_quad = -1;
 extern "C" int gt_set_seq_quad(int on) { g_seq_quad = on < 0 ? -1 : on != 0; return 0; }
 static bool seq_quad(const gt_config& c) {
-  if (c.d_model != 128 || c.dim_ff % 32 != 0 || !seq_split(c) || 4 * c.batch > xchg_cus() || (c.flags & GT_CFG_NO_QUAD)) return false;
+  if (c.d_model != 128 || c.dim_ff % 32 != 0 || 4 * c.batch > xchg_cus() || (c.flags & GT_CFG_NO_QUAD)) return false;     // (of a SPLIT schedule: seq_plan)
   if (g_seq_quad < 0) { const char* e = getenv("GT_SEQ_QUAD"); if (e) g_seq_quad = e[0] != '0'; }
   return g_seq_quad != 0;
 }
@@ -1130,29 +1135,44 @@ static bool use_seq(const gt_config& c) {
   if (g_seq == 2 && c.d_model > 64 && c.d_model != 128 && c.batch < 64) return false;   // (128 itself: the SPLIT kernels win from batch 16 up)
   return g_seq && seq_supported(c);
 }
-// gt_train_step hands its loss over to the sequence-resident forward (one launch less): set around its gt_forward call
-struct SeqLoss { const float* y; float penalty; float* stats; unsigned* ticket; };
-static thread_local SeqLoss g_seq_loss = {nullptr, 0.f, nullptr, nullptr};
-static thread_local bool g_heads_loss_done = false;   // one-kernel-per-op path: the OutputLayer launch of this fused step computed the loss too (heads_fwd_kernel)
+// The rules above, asked once for a call (a checked gt_config).  Nothing is kept between calls: the process-wide setters and the
+// environment answer every time as they always did.
+static SeqPlan seq_plan(const gt_config& c) {
+  SeqPlan p{};
+  p.seq = use_seq(c);
+  if (!p.seq) return p;
+  const int hd = c.d_model / c.n_heads;
+  p.hc = hd < 16 ? 0 : hd;                        // head-dim class (one instantiation each: the attention bodies' registers differ 4x)
+  p.split = seq_split(c);
+  p.quad = p.split && seq_quad(c);                // four workgroups per sequence: column partners share the FFN
+  p.ride = p.split && seq_ride(c);
+  // the fused train step's last forward launch goes on into backward phase 0 (seq_fb_kernel): QUAD schedule, riders, head_dim 32
+  p.fuse_b0 = p.quad && p.ride && hd == 32;
+  return p;
+}
+// What a fused train step hands to its forward and takes back from it (train_step_impl; gt_forward passes none).
+struct FwdStep {
+  // in: the loss to take along in the launch that runs the output layer (y == nullptr: none), and GT_STEP_PACKS_CURRENT -- the
+  // fragment-ordered weight copies in ws are the previous fused update's (seq_update_pack_kernel)
+  const float* y; float penalty; float* stats; unsigned* ticket;
+  bool packs_current;
+  // out
+  bool loss_done;            // the sequence-resident launch, or heads_fwd_kernel on the one-kernel-per-op path, computed the loss too
+  bool b0_done;              // the last forward launch already ran backward phase 0 (seq_fb_kernel): the step's backward skips it
+};
 // flops of backward phase 0 of the SPLIT / QUAD schedule: the dgrads of the output layer and of the last layer's FFN2, FFN1, out-proj
 static double seq_b0_flops(const Ctx& x) { return 2.0 * x.M * (27.0 * x.d + 2.0 * x.d * x.F + (double)x.d * x.d); }
-static thread_local bool g_seq_b0_fused = false;     // the forward of this fused step already ran backward phase 0 (seq_fb_kernel): gt_train_step's backward skips it
-// gt_train_step with GT_STEP_PACKS_CURRENT: the fragment-ordered weight copies in ws are the previous fused update's (seq_update_pack_kernel)
-static thread_local bool g_seq_packs_current = false;
 // launches of one gt_train_step on the sequence-resident path (0: another path -- dozens to hundreds): pack, forward (phases), backward
 // (phases), LayerNorm-parameter reduce, grouped weight gradients (one or two tile classes), optimizer.  Hosts use it to choose
 // between replaying a captured graph and plain launches: below ~25 nodes the graph's per-node cost exceeds what it saves.
-// the fused train step's last forward launch goes on into backward phase 0 (seq_fb_kernel): QUAD schedule, riders, head_dim 32
-static bool seq_fuse_b0(const gt_config& c) {
-  return seq_split(c) && seq_quad(c) && seq_ride(c) && c.d_model / c.n_heads == 32;
-}
 extern "C" int gt_step_launches(const gt_config* cfg) {
   if (check_cfg(cfg)) return -1;
-  if (!use_seq(*cfg)) return 0;
+  const SeqPlan sp = seq_plan(*cfg);
+  if (!sp.seq) return 0;
   // (with GT_STEP_PACKS_CURRENT one less: no packing launch)
-  if (!seq_split(*cfg)) return 7;
+  if (!sp.split) return 7;
   // pack, L forward + L + 1 backward phases (QUAD at head_dim 32: the last forward launch runs backward phase 0 too), [grouped weight gradients x 2,] reduce / tail, update
-  return 2 * cfg->n_enc_layers + 1 + (seq_ride(*cfg) ? 3 : 5) - (seq_fuse_b0(*cfg) ? 1 : 0);
+  return 2 * cfg->n_enc_layers + 1 + (sp.ride ? 3 : 5) - (sp.fuse_b0 ? 1 : 0);
 }
 static SeqArgs mk_seq(const Ctx& x, const float* pe, const float* src, float* hvo) {
   SeqArgs a;
@@ -1181,50 +1201,138 @@ static SeqArgs mk_seq(const Ctx& x, const float* pe, const float* src, float* hv
   return a;
 }
 // the whole forward (input layer ... output heads) of every sequence: ONE launch
-static int seq_forward(const Ctx& x, const float* pe, const float* src, float* hvo_out) {
+static int seq_forward(const Ctx& x, const float* pe, const float* src, float* hvo_out, FwdStep* st) {
+  const SeqPlan& sp = x.plan;
   SeqArgs a = mk_seq(x, pe, src, hvo_out);
-  if (g_seq_loss.y != nullptr) {
-    a.loss_y = g_seq_loss.y; a.loss_penalty = g_seq_loss.penalty; a.loss_stats = g_seq_loss.stats; a.loss_ticket = g_seq_loss.ticket;
+  if (st && st->y != nullptr) {                   // the fused step's loss rides in the launch that runs the output layer (one launch less)
+    a.loss_y = st->y; a.loss_penalty = st->penalty; a.loss_stats = st->stats; a.loss_ticket = st->ticket;
     a.loss_part = x.ws + x.W.loss_part;
+    st->loss_done = true;
   }
   const double fl = 2.0 * x.M * ((double)x.c.src_dim * x.d + x.c.n_enc_layers * (4.0 * x.d * x.d + 64.0 * x.d + 2.0 * x.d * x.F) + 27.0 * x.d);
-  if (!g_seq_packs_current) {   // fragment-ordered copies of this step's weights, for the forward and the backward kernel
+  if (!(st && st->packs_current)) {   // fragment-ordered copies of this step's weights, for the forward and the backward kernel
     const int64_t frags = 2 * (int64_t)x.c.n_enc_layers * x.W.pack_stride / 256;
     gt_prof_tag("seq_pack", 0.0, 12.0 * x.c.n_enc_layers * x.W.pack_stride);
     gt_dispatch("seq_pack B %d d %d F %d L %d", x.c.batch, x.d, x.F, x.c.n_enc_layers);
     gt_seq_launch_pack(a, (unsigned)((frags + 3) / 4), x.s);
   }
-  const int hc = x.hd < 16 ? 0 : x.hd;             // head-dim class (one instantiation each: the attention bodies' registers differ 4x)
   // fused train step on the QUAD schedule: the last phase's launch goes on into backward phase 0 (seq_fb_kernel)
-  const bool fuse_b0 = seq_fuse_b0(x.c) && a.loss_y != nullptr;
+  const bool fuse_b0 = sp.fuse_b0 && a.loss_y != nullptr;
   // (its dgrad products -- output layer, FFN2, FFN1, out-proj of the last layer -- are counted where they run)
   gt_prof_tag("seq_fwd", fl + (fuse_b0 ? seq_b0_flops(x) : 0.0), 4.0 * x.M * (x.c.src_dim + x.c.n_enc_layers * (9.0 * x.d + x.F) + 27.0));
-  if (seq_split(x.c)) {
-    const bool quad = seq_quad(x.c);                           // four workgroups per sequence: column partners share the FFN
+  if (sp.split) {
     // GT_SEQ_QUAD_PRO=1: input layer + in-proj(0) as a prologue launch of their own instead of four times over inside phase 0 --
     // measured neutral at the headline shape (0.2076 vs 0.2073 ms: one more launch for 17 k fewer cycles of phase 0), so off
     static const int quad_pro = [] { const char* e = getenv("GT_SEQ_QUAD_PRO"); return (e && e[0] == '1') ? 1 : 0; }();
-    a.quad_pro = quad ? quad_pro : 0;
-    g_seq_b0_fused = false;
+    a.quad_pro = sp.quad ? quad_pro : 0;
     for (int p = a.quad_pro ? -1 : 0; p < x.c.n_enc_layers; ++p) {   // one launch per encoder layer (gt_seq.h, SPLIT) [+ QUAD's prologue]
       SeqArgs ap = a;
       ap.phase = p;
       if (p > (a.quad_pro ? -1 : 0)) gt_prof_tag("seq_fwd", 0.0, 0.0);          // (flops and bytes of the whole forward are on the first phase's tag)
-      gt_dispatch("seq_fwd phase %d split 1 quad %d ride %d fuse_b0 %d B %d d %d F %d L %d", p, quad, seq_ride(x.c), fuse_b0 && p == x.c.n_enc_layers - 1,
+      gt_dispatch("seq_fwd phase %d split 1 quad %d ride %d fuse_b0 %d B %d d %d F %d L %d", p, sp.quad, sp.ride, fuse_b0 && p == x.c.n_enc_layers - 1,
                   x.c.batch, x.d, x.F, x.c.n_enc_layers);
       if (fuse_b0 && p == x.c.n_enc_layers - 1) {
         ap.fuse_b0 = 1;
         gt_seq_launch_fb(ap, 4 * x.c.batch, x.s);
-        g_seq_b0_fused = true;
+        st->b0_done = true;
       } else {
-        gt_seq_launch_fwd(ap, x.d, hc, true, (quad ? 4 : 2) * x.c.batch, x.s, quad);
+        gt_seq_launch_fwd(ap, x.d, sp.hc, true, (sp.quad ? 4 : 2) * x.c.batch, x.s, sp.quad);
       }
     }
     return 0;
   }
-  const dim3 grid(x.c.batch);
   gt_dispatch("seq_fwd phase 0 split 0 quad 0 ride 0 fuse_b0 0 B %d d %d F %d L %d", x.c.batch, x.d, x.F, x.c.n_enc_layers);
-  gt_seq_launch_fwd(a, x.d, hc, false, x.c.batch, x.s);
+  gt_seq_launch_fwd(a, x.d, sp.hc, false, x.c.batch, x.s);
+  return 0;
+}
+// the whole backward chain of every sequence in ONE launch (SPLIT: one per phase).  The weight gradients (contractions over all
+// sequences) and the LayerNorm parameter gradients ride in the phases and finish in the tail launch (sp.ride: nothing is left for the
+// caller), or are queued here for the caller's grouped dispatch and reduce (backward_impl's finish()).
+// phase: backward_impl's; cut_layer: first encoder layer of the upper gradient bucket (grad_split); b0_done: FwdStep's
+static int seq_backward(const Ctx& x, const float* xin, int accumulate, int phase, int cut_layer, gt_step_state* bump_state, bool grads_zero,
+                        bool b0_done) {
+  const SeqPlan& sp = x.plan;
+  const WLayout& W = x.W;
+  const PLayout& P = x.P;
+  const int L = x.c.n_enc_layers, B = x.c.batch, S = x.c.src_dim, d = x.d, M = x.M;
+  float* ws = x.ws; float* grads = x.grd;
+  // LayerNorm jobs in the order the kernel fills their partial blocks (one [2][d] row per sequence)
+  const int nwg = sp.split ? 2 * B : B;                        // partial rows per LayerNorm instance: one per workgroup
+  bool ok = ln_job(x, P.encn_w, nwg) != nullptr;
+  for (int j = L - 1; j >= 0; --j) ok = ok && ln_job(x, P.enc[j].n2w, nwg) && ln_job(x, P.enc[j].n1w, nwg);
+  if (!ok) return gt_fail("too many LayerNorm instances for the partials table");
+  SeqArgs a = mk_seq(x, nullptr, xin, nullptr);
+  // dgrad products (the four Linear dgrads = the forward's GEMM flops; attention backward (dP, dV, dQ, dK) = twice the forward's
+  // QK^T + PV; the SPLIT mode's second copy of it is not counted) -- plus, with riders, the weight gradients these launches carry
+  double fl = 2.0 * M * (L * (4.0 * d * d + 128.0 * d + 2.0 * d * x.F) + 27.0 * d);
+  if (sp.ride) {
+    // rider workgroups behind the 2 x batch sequence workgroups: as many as the busiest phase has units, at most the idle CUs
+    a.grd = grads; a.nseq = 2 * B; a.wg_accumulate = (accumulate && !grads_zero) ? 1 : 0;
+    const int per_layer = gt_seq_wg_tiles(d, x.F) + gt_seq_wg_tiles(x.F, d) + gt_seq_wg_tiles(d, d), win = gt_seq_wg_tiles(3 * d, d);
+    const int lnu = (2 * d + 63) / 64;                            // LayerNorm column blocks per job
+    const int idle = seq_cu_count() - a.nseq, busiest = per_layer + (L > 1 ? win : 0) + 2 * lnu + (L == 1 ? lnu : 0);
+    const int R = idle < busiest ? (idle > 0 ? idle : 1) : busiest;
+    // the last phase's sequence work is short (attention backward + in-proj dgrad of layer 0): its riders take only the first
+    // GT_SEQ_RIDE_LAST_PCT % of the tokens of each tile, the tail launch -- the whole chip -- adds the rest
+    a.ride_last_k = (int)((int64_t)M * GT_SEQ_RIDE_LAST_PCT / 100) / 64 * 64;
+    fl += 2.0 * M * ((L - 1) * 3.0 * d * d + L * ((double)d * d + 2.0 * d * x.F))
+          - 2.0 * (M - a.ride_last_k) * (per_layer + (L > 1 ? win : 0)) * 2048.0;
+    if (b0_done) fl -= seq_b0_flops(x);                         // (phase 0 ran, and was counted, in the forward's last launch)
+    gt_prof_tag("seq_bwd", fl, 4.0 * M * (L * (14.0 * d + 2.0 * x.F) + 27.0) + 4.0 * M * L * (8.0 * d + 2.0 * x.F));   // + the riders' operands, once
+    // bucketed backward (data-parallel overlap): phase 1 = the launches up to the cut of grad_split, phase 2 = the rest + tail
+    const int pcut = L - cut_layer + 1;                          // last backward phase of the first half (two buckets)
+    const int p_lo = phase == 2 ? pcut + 1 : 0, p_hi = phase == 1 ? pcut : L;
+    a.ln_nwg = nwg;
+    for (int p = p_lo; p <= p_hi; ++p) {
+      if (p == 0 && b0_done) continue;
+      SeqArgs ap = a;
+      ap.phase = p;
+      if (p > p_lo && !(b0_done && p == 1)) gt_prof_tag("seq_bwd", 0.0, 0.0);
+      gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d", p, p == 0 && sp.quad, p == 0 ? 0 : R, b0_done, B, d, x.F, L);
+      // phase 0 has no riders: four workgroups per sequence there (column partners, gt_seq.h QUAD) while they fit the chip
+      if (p == 0 && sp.quad) gt_seq_launch_bwd(ap, d, sp.hc, true, 2 * a.nseq, x.s, true);
+      else gt_seq_launch_bwd(ap, d, sp.hc, true, a.nseq + (p == 0 ? 0 : R), x.s);
+    }
+    if (phase == 1) {      // bucket 0 reaches to the END of the buffer: the output layer's gradient now, by a launch of its own
+      a.phase = 0; a.tail_phase = 0; a.tail_ksplit = 2; a.bump = nullptr;
+      gt_prof_tag("seq_tail", 2.0 * M * 27.0 * d, 4.0 * M * (27.0 + d));
+      gt_dispatch("seq_tail kind out_early B %d d %d F %d L %d", B, d, x.F, L);
+      gt_seq_launch_tail(a, (unsigned)(gt_seq_wg_tiles(GT_TGT, d) * 2), x.s);
+      return 0;
+    }
+    a.out_early = phase == 2 ? 1 : 0;
+    // the tail: the rest of the last phase's tiles, then in-proj of layer 0 + input layer (token range split in two: two partial
+    // tiles adding onto zero commute, so this stays reproducible), the step-counter bump
+    const int tiles = win + gt_seq_wg_tiles(d, S) + (a.out_early ? 0 : gt_seq_wg_tiles(GT_TGT, d));
+    const int ks = M / 8 < 2 ? M / 8 : 2;
+    a.phase = L + 1; a.tail_phase = L + 1; a.tail_ksplit = ks; a.bump = bump_state;
+    const int nrest = a.ride_last_k < M ? per_layer + (L > 1 ? win : 0) : 0;
+    gt_prof_tag("seq_tail", 2.0 * M * (3.0 * d * d + (a.out_early ? 0.0 : 27.0 * d) + (double)d * S) + 2.0 * (M - a.ride_last_k) * nrest * 2048.0,
+                4.0 * M * (4.0 * d + S));
+    gt_dispatch("seq_tail kind tail B %d d %d F %d L %d", B, d, x.F, L);
+    gt_seq_launch_tail(a, (unsigned)(nrest + tiles * ks), x.s);
+    return 0;
+  }
+  gt_prof_tag("seq_bwd", fl, 4.0 * M * (L * (14.0 * d + 2.0 * x.F) + 27.0));
+  for (int p = 0; p <= (sp.split ? L : 0); ++p) {              // SPLIT: one launch per phase; else the one launch
+    SeqArgs ap = a;
+    ap.phase = p;
+    if (p > 0) gt_prof_tag("seq_bwd", 0.0, 0.0);
+    gt_dispatch("seq_bwd phase %d split %d quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d", p, sp.split, B, d, x.F, L);
+    gt_seq_launch_bwd(ap, d, sp.hc, sp.split, nwg, x.s);
+  }
+  wgrad(x, ws + W.dlogits, GT_TGT, ws + W.memory, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);
+  for (int j = L - 1; j >= 0; --j) {
+    const LayerP& p = P.enc[j];
+    const LayerW& w = W.layers[j];
+    const Tmp t = tmp_set(x, j);
+    const float* lin = (j == 0) ? ws + W.x0 : ws + W.layers[j - 1].xout;
+    wgrad(x, t.dzAm, d, ws + w.hact, x.F, grads + p.w2, grads + p.b2, d, x.F);
+    wgrad(x, t.dhid, x.F, ws + w.x1, d, grads + p.w1, grads + p.b1, x.F, d);
+    wgrad(x, t.dzBm, d, ws + w.ctx, d, grads + p.sa.out_w, grads + p.sa.out_b, d, d);
+    wgrad(x, t.dqkv, 3 * d, lin, d, grads + p.sa.in_w, grads + p.sa.in_b, 3 * d, d);
+  }
+  wgrad(x, ws + W.dctx, d, xin, S, grads + P.in_w, grads + P.in_b, d, S);
   return 0;
 }
 
@@ -1344,14 +1452,14 @@ static void decoder_step(const Ctx& x, const float* pe, const float* tgt, int t,
   g.bias = x.prm + x.P.out_b;
   gemm_launch<false, false, EPI_HEADS>(g, x.s);
 }
-static void output_layer_fwd(const Ctx& x, float* hvo_out) {
+static void output_layer_fwd(const Ctx& x, float* hvo_out, FwdStep* st = nullptr) {
   const float* fin = x.ws + (x.c.n_dec_layers > 0 ? x.W.dec_final : x.W.memory);
   if (heads_fwd_ok(x.M, x.d, x.d, fin, x.prm + x.P.out_w)) {
-    // the fused train step hands the loss over as well (g_seq_loss, as for the sequence-resident launches): one launch for OutputLayer + loss
+    // the fused train step hands the loss over as well (as to the sequence-resident launches): one launch for OutputLayer + loss
     HeadsLoss hl = {nullptr, 0.f, nullptr, nullptr, nullptr, nullptr};
-    if (g_seq_loss.y != nullptr) {
-      hl = HeadsLoss{g_seq_loss.y, g_seq_loss.penalty, g_seq_loss.stats, x.ws + x.W.loss_part, g_seq_loss.ticket, x.ws + x.W.dlogits};
-      g_heads_loss_done = true;
+    if (st && st->y != nullptr) {
+      hl = HeadsLoss{st->y, st->penalty, st->stats, x.ws + x.W.loss_part, st->ticket, x.ws + x.W.dlogits};
+      st->loss_done = true;
     }
     static const bool trace = [] { const char* e = getenv("GT_TRACE_HEADS"); return e && e[0] == '1'; }();     // (tests: which launches took the kernel)
     if (trace) fprintf(stderr, "[heads] M %d d %d precision %d loss %d\n", x.M, x.d, x.c.precision, hl.y != nullptr);
@@ -1366,20 +1474,25 @@ static void output_layer_fwd(const Ctx& x, float* hvo_out) {
   gemm_launch<false, false, EPI_HEADS>(g, x.s);
 }
 
+// st: the hand-offs of a fused train step (FwdStep; nullptr: a plain forward -- no loss taken along, weights packed, no backward phase)
+static int forward_impl(const Ctx& x, const float* pe, const float* xin, const float* tgt_in, float* hvo_out, FwdStep* st) {
+  if (!pe || !xin || !hvo_out) return gt_fail("gt_forward: pe / x / hvo_out must not be NULL");
+  if (x.c.n_dec_layers > 0 && !tgt_in) return gt_fail("gt_forward: encoder-decoder model needs tgt_in");
+  if (x.plan.seq) {
+    seq_forward(x, pe, xin, hvo_out, st);
+    return launch_status("gt_forward");
+  }
+  if (encoder_fwd(x, pe, xin)) return -1;
+  if (x.c.n_dec_layers > 0 && decoder_fwd(x, pe, tgt_in)) return -1;
+  output_layer_fwd(x, hvo_out, st);
+  return launch_status("gt_forward");
+}
 extern "C" int gt_forward(const gt_config* cfg, const float* params, const float* pe, const float* xin, const float* tgt_in,
                           float* hvo_out, float* ws, const gt_step_state* state, int train, gt_stream_t stream) {
   Ctx x;
   if (make_ctx(x, cfg, params, nullptr, ws, state, train, stream)) return -1;
-  if (!pe || !xin || !hvo_out) return gt_fail("gt_forward: pe / x / hvo_out must not be NULL");
-  if (cfg->n_dec_layers > 0 && !tgt_in) return gt_fail("gt_forward: encoder-decoder model needs tgt_in");
-  if (use_seq(*cfg)) {
-    seq_forward(x, pe, xin, hvo_out);
-    return launch_status("gt_forward");
-  }
-  if (encoder_fwd(x, pe, xin)) return -1;
-  if (cfg->n_dec_layers > 0 && decoder_fwd(x, pe, tgt_in)) return -1;
-  output_layer_fwd(x, hvo_out);
-  return launch_status("gt_forward");
+  x.plan = seq_plan(x.c);
+  return forward_impl(x, pe, xin, tgt_in, hvo_out, nullptr);
 }
 
 // ------------------------------------------------------------------------------------ loss
@@ -1481,13 +1594,12 @@ static void input_layer_bwd(const Ctx& x, const LayerP& first, const Tmp& t, con
   wgrad(x, da_out, x.d, in, S, x.grd + w, x.grd + b, x.d, S);
 }
 
-// d_hvo == nullptr: ws.dlogits already holds d loss / d logits (the fused loss kernel wrote it)
 // Gradient buckets for data-parallel overlap, in the order backward completes them.  Parameters are laid out
 // [in | enc layers | enc norm | (dec in | dec layers | dec norm) | out] and backward walks that list from its end, so
 // "everything from tensor X to the end" is final early: X = the decoder input layer of an encoder-decoder model, else
 // encoder layer L/2.  split_layer: first encoder layer of the upper bucket (enc-dec: L, i.e. no encoder layer).
 struct GradSplit { int nb; int split_layer; int64_t off[2], cnt[2]; };
-static GradSplit grad_split(const gt_config& c, const PLayout& P) {
+static GradSplit grad_split(const gt_config& c, const PLayout& P, const SeqPlan& sp) {
   GradSplit g;
   g.nb = 1; g.split_layer = 0; g.off[0] = 0; g.cnt[0] = P.total; g.off[1] = g.cnt[1] = 0;
   int64_t cut = 0;
@@ -1495,11 +1607,11 @@ static GradSplit grad_split(const gt_config& c, const PLayout& P) {
   else if (c.n_enc_layers >= 2) { g.split_layer = c.n_enc_layers / 2; cut = P.enc[g.split_layer].sa.in_w; }
   // sequence-resident path: one bucket -- unless the weight gradients ride in the backward phases (gt_seq_wg.h): after phase p < L
   // everything from encoder layer L - p + 1 on is final; the cut is after phase min((L + 2) / 2, L - 1)
-  if (use_seq(c)) {
+  if (sp.seq) {
     const int L = c.n_enc_layers;
     int pcut = (L + 2) / 2;                       // (the LAST phase's tiles are finished by the tail launch: the cut lies before it)
     if (pcut > L - 1) pcut = L - 1;
-    if (pcut >= 1 && seq_ride(c)) { g.split_layer = L - pcut + 1; cut = g.split_layer < L ? P.enc[g.split_layer].sa.in_w : P.encn_w; }
+    if (pcut >= 1 && sp.ride) { g.split_layer = L - pcut + 1; cut = g.split_layer < L ? P.enc[g.split_layer].sa.in_w : P.encn_w; }
     else cut = 0;
   }
   if (cut > 0) {
@@ -1511,18 +1623,24 @@ extern "C" int gt_grad_buckets(const gt_config* cfg, int64_t* offsets, int64_t* 
   if (check_cfg(cfg)) return -1;
   if (!offsets || !counts) return gt_fail("gt_grad_buckets: offsets / counts must not be NULL");
   const PLayout P = param_layout(*cfg);
-  const GradSplit g = grad_split(*cfg, P);
+  const GradSplit g = grad_split(*cfg, P, seq_plan(*cfg));
   for (int i = 0; i < 2; ++i) { offsets[i] = g.off[i]; counts[i] = g.cnt[i]; }
   return g.nb;
 }
 
+// d loss / d logits from d loss / d hvo -- unless ws.dlogits already holds it (d_hvo == nullptr: the fused loss kernel wrote it)
+static void heads_bwd(const Ctx& x, const float* hvo, const float* d_hvo) {
+  if (d_hvo == nullptr) return;
+  gt_prof_tag("heads_bwd", 0, 12.0 * x.M * GT_TGT);
+  gt_launch(heads_bwd_kernel, dim3((x.M * GT_TGT + 255) / 256), dim3(256), x.s, d_hvo, hvo, x.ws + x.W.dlogits, x.M * GT_TGT);
+}
 // phase 0: the whole backward; 1: only until bucket 0 of grad_split() is final; 2: the rest (after a phase-1 call on the
-// same workspace -- the hand-over temporaries live there)
-static int backward_impl(const gt_config* cfg, const float* params, float* grads, const float* xin, const float* tgt_in,
-                         const float* hvo, const float* d_hvo, float* ws, const gt_step_state* state, int train, int accumulate,
-                         gt_stream_t stream, int phase = 0, gt_step_state* bump_state = nullptr, bool grads_zero = false) {
-  Ctx x;
-  if (make_ctx(x, cfg, params, grads, ws, state, train, stream)) return -1;
+// same workspace -- the hand-over temporaries live there).  b0_done: the caller's forward ran backward phase 0 already (FwdStep).
+// x: the caller's context with its plan, by value -- the queues of this call hang off the copy.
+static int backward_impl(Ctx x, const float* xin, const float* tgt_in, const float* hvo, const float* d_hvo, int accumulate, int phase,
+                         gt_step_state* bump_state, bool grads_zero, bool b0_done) {
+  const gt_config* cfg = &x.c;
+  const float* params = x.prm; float* grads = x.grd; float* ws = x.ws;
   if (!grads || !xin) return gt_fail("gt_backward: grads / x must not be NULL");
   const int L = cfg->n_enc_layers, Ld = cfg->n_dec_layers, d = x.d, M = x.M;
   if (Ld > 0 && !tgt_in) return gt_fail("gt_backward: encoder-decoder model needs tgt_in");
@@ -1538,8 +1656,8 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
   lnjobs.err = xchg_err(x.W, ws);
   x.ln = &lnjobs;
   const int top = L + Ld - 1;                       // global index of the last layer
-  const GradSplit split = grad_split(*cfg, P);
-  if (split.nb < 2) {                               // nothing to split: phase 1 does everything, phase 2 nothing
+  const GradSplit cut = grad_split(*cfg, P, x.plan);
+  if (cut.nb < 2) {                                 // nothing to split: phase 1 does everything, phase 2 nothing
     if (phase == 2) return 0;
     phase = 0;
   }
@@ -1555,113 +1673,18 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     return launch_status("gt_backward");
   };
 
-  if (use_seq(*cfg)) {
+  if (x.plan.seq) {
     // ---- sequence-resident path (gt_seq.h): the whole backward chain of every sequence in ONE launch; the weight gradients
-    // (contractions over all sequences) and the LayerNorm parameter gradients leave as the grouped dispatch / the reduce
-    if (d_hvo != nullptr) {
-      gt_prof_tag("heads_bwd", 0, 12.0 * M * GT_TGT);
-      gt_launch(heads_bwd_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, d_hvo, hvo, ws + W.dlogits, M * GT_TGT);
-    }
-    // LayerNorm jobs in the order the kernel fills their partial blocks (one [2][d] row per sequence)
-    const GradSplit split_ = split;                              // (the bucket cut; `split` below is the two-workgroups-per-sequence mode)
-    const bool split = seq_split(*cfg);
-    const int nwg = split ? 2 * cfg->batch : cfg->batch;       // partial rows per LayerNorm instance: one per workgroup
-    bool ok = ln_job(x, P.encn_w, nwg) != nullptr;
-    for (int j = L - 1; j >= 0; --j) ok = ok && ln_job(x, P.enc[j].n2w, nwg) && ln_job(x, P.enc[j].n1w, nwg);
-    if (!ok) return gt_fail("too many LayerNorm instances for the partials table");
-    const bool ride = split && seq_ride(*cfg);
-    {
-      SeqArgs a = mk_seq(x, nullptr, xin, nullptr);
-      // dgrad products (the four Linear dgrads = the forward's GEMM flops; attention backward (dP, dV, dQ, dK) = twice the forward's
-      // QK^T + PV; the SPLIT mode's second copy of it is not counted) -- plus, with riders, the weight gradients these launches carry
-      double fl = 2.0 * M * (L * (4.0 * d * d + 128.0 * d + 2.0 * d * x.F) + 27.0 * d);
-      const int hc = x.hd < 16 ? 0 : x.hd;
-      if (ride) {
-        // rider workgroups behind the 2 x batch sequence workgroups: as many as the busiest phase has units, at most the idle CUs
-        a.grd = grads; a.nseq = 2 * cfg->batch; a.wg_accumulate = (accumulate && !grads_zero) ? 1 : 0;
-        const int per_layer = gt_seq_wg_tiles(d, x.F) + gt_seq_wg_tiles(x.F, d) + gt_seq_wg_tiles(d, d), win = gt_seq_wg_tiles(3 * d, d);
-        const int lnu = (2 * d + 63) / 64;                            // LayerNorm column blocks per job
-        const int idle = seq_cu_count() - a.nseq, busiest = per_layer + (L > 1 ? win : 0) + 2 * lnu + (L == 1 ? lnu : 0);
-        const int R = idle < busiest ? (idle > 0 ? idle : 1) : busiest;
-        // the last phase's sequence work is short (attention backward + in-proj dgrad of layer 0): its riders take only the first
-        // GT_SEQ_RIDE_LAST_PCT % of the tokens of each tile, the tail launch -- the whole chip -- adds the rest
-        a.ride_last_k = (int)((int64_t)M * GT_SEQ_RIDE_LAST_PCT / 100) / 64 * 64;
-        fl += 2.0 * M * ((L - 1) * 3.0 * d * d + L * ((double)d * d + 2.0 * d * x.F))
-              - 2.0 * (M - a.ride_last_k) * (per_layer + (L > 1 ? win : 0)) * 2048.0;
-        if (g_seq_b0_fused) fl -= seq_b0_flops(x);                  // (phase 0 ran, and was counted, in the forward's last launch)
-        gt_prof_tag("seq_bwd", fl, 4.0 * M * (L * (14.0 * d + 2.0 * x.F) + 27.0) + 4.0 * M * L * (8.0 * d + 2.0 * x.F));   // + the riders' operands, once
-        // bucketed backward (data-parallel overlap): phase 1 = the launches up to the cut of grad_split, phase 2 = the rest + tail
-        const int pcut = L - split_.split_layer + 1;                 // last backward phase of the first half (split_.nb == 2)
-        const int p_lo = phase == 2 ? pcut + 1 : 0, p_hi = phase == 1 ? pcut : L;
-        a.ln_nwg = nwg;
-        const bool quad0 = seq_quad(*cfg);
-        const bool b0_done = g_seq_b0_fused && quad0;                // (phase 0 ran inside the forward's last launch)
-        g_seq_b0_fused = false;
-        for (int p = p_lo; p <= p_hi; ++p) {
-          if (p == 0 && b0_done) continue;
-          SeqArgs ap = a;
-          ap.phase = p;
-          if (p > p_lo && !(b0_done && p == 1)) gt_prof_tag("seq_bwd", 0.0, 0.0);
-          gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d", p, p == 0 && quad0, p == 0 ? 0 : R, b0_done, cfg->batch, d, x.F, L);
-          // phase 0 has no riders: four workgroups per sequence there (column partners, gt_seq.h QUAD) while they fit the chip
-          if (p == 0 && quad0) gt_seq_launch_bwd(ap, d, hc, true, 2 * a.nseq, x.s, true);
-          else gt_seq_launch_bwd(ap, d, hc, true, a.nseq + (p == 0 ? 0 : R), x.s);
-        }
-        if (phase == 1) {      // bucket 0 reaches to the END of the buffer: the output layer's gradient now, by a launch of its own
-          a.phase = 0; a.tail_phase = 0; a.tail_ksplit = 2; a.bump = nullptr;
-          gt_prof_tag("seq_tail", 2.0 * M * 27.0 * d, 4.0 * M * (27.0 + d));
-          gt_dispatch("seq_tail kind out_early B %d d %d F %d L %d", cfg->batch, d, x.F, L);
-          gt_seq_launch_tail(a, (unsigned)(gt_seq_wg_tiles(GT_TGT, d) * 2), x.s);
-          return launch_status("gt_backward");
-        }
-        a.out_early = phase == 2 ? 1 : 0;
-        // the tail: the rest of the last phase's tiles, then in-proj of layer 0 + input layer (token range split in two: two partial
-        // tiles adding onto zero commute, so this stays reproducible), the step-counter bump
-        const int tiles = win + gt_seq_wg_tiles(d, cfg->src_dim) + (a.out_early ? 0 : gt_seq_wg_tiles(GT_TGT, d));
-        const int ks = M / 8 < 2 ? M / 8 : 2;
-        a.phase = L + 1; a.tail_phase = L + 1; a.tail_ksplit = ks; a.bump = bump_state;
-        const int nrest = a.ride_last_k < M ? per_layer + (L > 1 ? win : 0) : 0;
-        gt_prof_tag("seq_tail", 2.0 * M * (3.0 * d * d + (a.out_early ? 0.0 : 27.0 * d) + (double)d * cfg->src_dim) + 2.0 * (M - a.ride_last_k) * nrest * 2048.0,
-                    4.0 * M * (4.0 * d + cfg->src_dim));
-        gt_dispatch("seq_tail kind tail B %d d %d F %d L %d", cfg->batch, d, x.F, L);
-        gt_seq_launch_tail(a, (unsigned)(nrest + tiles * ks), x.s);
-        return launch_status("gt_backward");
-      }
-      gt_prof_tag("seq_bwd", fl, 4.0 * M * (L * (14.0 * d + 2.0 * x.F) + 27.0));
-      if (split) {
-        for (int p = 0; p <= L; ++p) {
-          SeqArgs ap = a;
-          ap.phase = p;
-          if (p > 0) gt_prof_tag("seq_bwd", 0.0, 0.0);
-          gt_dispatch("seq_bwd phase %d split 1 quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d", p, cfg->batch, d, x.F, L);
-          gt_seq_launch_bwd(ap, d, hc, true, 2 * cfg->batch, x.s);
-        }
-      } else {
-        gt_dispatch("seq_bwd phase 0 split 0 quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d", cfg->batch, d, x.F, L);
-        gt_seq_launch_bwd(a, d, hc, false, cfg->batch, x.s);
-      }
-    }
-    wgrad(x, ws + W.dlogits, GT_TGT, ws + W.memory, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);
-    for (int j = L - 1; j >= 0; --j) {
-      const LayerP& p = P.enc[j];
-      const LayerW& w = W.layers[j];
-      const Tmp t = tmp_set(x, j);
-      const float* lin = (j == 0) ? ws + W.x0 : ws + W.layers[j - 1].xout;
-      wgrad(x, t.dzAm, d, ws + w.hact, x.F, grads + p.w2, grads + p.b2, d, x.F);
-      wgrad(x, t.dhid, x.F, ws + w.x1, d, grads + p.w1, grads + p.b1, x.F, d);
-      wgrad(x, t.dzBm, d, ws + w.ctx, d, grads + p.sa.out_w, grads + p.sa.out_b, d, d);
-      wgrad(x, t.dqkv, 3 * d, lin, d, grads + p.sa.in_w, grads + p.sa.in_b, 3 * d, d);
-    }
-    wgrad(x, ws + W.dctx, d, xin, cfg->src_dim, grads + P.in_w, grads + P.in_b, d, cfg->src_dim);
-    return finish();
+    // (contractions over all sequences) and the LayerNorm parameter gradients leave as the grouped dispatch / the reduce -- or,
+    // with riders, have left in the phases and the tail launch
+    heads_bwd(x, hvo, d_hvo);
+    if (seq_backward(x, xin, accumulate, phase, cut.split_layer, bump_state, grads_zero, b0_done)) return -1;
+    return x.plan.ride ? launch_status("gt_backward") : finish();
   }
   bool top_norm_done = false;                       // the top layer's closing norm was folded into the final norm's pass
   if (phase != 2) {
   // OutputLayer: dlogits, dW_out, then d(final) fused with the final norm's backward
-  if (d_hvo != nullptr) {
-    gt_prof_tag("heads_bwd", 0, 12.0 * M * GT_TGT);
-    gt_launch(heads_bwd_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, d_hvo, hvo, ws + W.dlogits, M * GT_TGT);
-  }
+  heads_bwd(x, hvo, d_hvo);
   const float* fin = ws + (Ld > 0 ? W.dec_final : W.memory);
   wgrad(x, ws + W.dlogits, GT_TGT, fin, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);
   // the final norm's backward and the top layer's closing norm's backward sit back to back: when the output-layer dgrad is
@@ -1738,7 +1761,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
     const Tmp t = tmp_set(x, L - 1);
     ln_bwd(x, ws + W.dctx, nullptr, ws + w.xhat2, ws + w.rstd2, P.enc[L - 1].n2w, t.dzA, t.dzAm, lsite(L - 1, GT_SITE_DROPF));
   }
-  for (int l = (phase == 2 && Ld == 0) ? split.split_layer - 1 : L - 1; l >= 0; --l) {
+  for (int l = (phase == 2 && Ld == 0) ? cut.split_layer - 1 : L - 1; l >= 0; --l) {
     const LayerP& p = P.enc[l];
     const LayerW& w = W.layers[l];
     const Tmp t = tmp_set(x, l);
@@ -1751,7 +1774,7 @@ static int backward_impl(const gt_config* cfg, const float* params, float* grads
       if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzB, ws + wp.xhat2, ws + wp.rstd2, P.enc[l - 1].n2w, tn.dzA, tn.dzAm,
                       lsite(l - 1, GT_SITE_DROPF)))
         return -1;
-      if (phase == 1 && Ld == 0 && l == split.split_layer) return finish();   // layers >= split are final; (dzA, dzAm) of l-1 handed over
+      if (phase == 1 && Ld == 0 && l == cut.split_layer) return finish();     // layers >= the cut are final; (dzA, dzAm) of l-1 handed over
     } else {
       input_layer_bwd(x, p, t, t.dzB, ws + W.a0, xin, cfg->src_dim, P.in_w, P.in_b, GT_SITE_PE_ENC, ws + W.dctx);
     }
@@ -1782,8 +1805,10 @@ extern "C" int gt_backward(const gt_config* cfg, const float* params, float* gra
                            const float* hvo, const float* d_hvo, float* ws, const gt_step_state* state, int train, int accumulate,
                            gt_stream_t stream) {
   if (!hvo || !d_hvo) return gt_fail("gt_backward: hvo / d_hvo must not be NULL");
-  g_seq_b0_fused = false;                           // (only gt_train_step's own forward may have run backward phase 0 already)
-  return backward_impl(cfg, params, grads, xin, tgt_in, hvo, d_hvo, ws, state, train, accumulate, stream);
+  Ctx x;
+  if (make_ctx(x, cfg, params, grads, ws, state, train, stream)) return -1;
+  x.plan = seq_plan(x.c);
+  return backward_impl(std::move(x), xin, tgt_in, hvo, d_hvo, accumulate, 0, nullptr, false, false);    // (a forward of its own ran no backward phase)
 }
 
 // ------------------------------------------------------------------------------------ optimizer
@@ -1814,6 +1839,19 @@ extern "C" int gt_optimizer_step(int algo, float* params, float* grads, float* m
                                  int zero_grads, gt_stream_t stream) {
   return optimizer_step_impl(algo, params, grads, m, v, n, state, zero_grads, stream, 0);
 }
+// The folded update of the sequence-resident path: the optimizer step over the WHOLE flat buffers of x (params = x.prm, x.grd) that also
+// writes the NEXT step's fragment-ordered weights into ws (its caller may then pass GT_STEP_PACKS_CURRENT and the packing launch at the
+// head of the step disappears).  step_advanced: as optimizer_step_impl's.  pe / xin / hvo_out: what the caller's step ran on, or NULL.
+static int seq_update_pack(const Ctx& x, int algo, float* params, float* m, float* v, const float* pe, const float* xin, float* hvo_out,
+                           gt_step_state* state, int step_advanced) {
+  if (algo != 0 && algo != 1) return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
+  if (algo == 1 && (!m || !v)) return gt_fail("gt_optimizer_step: adam needs m and v");
+  const SeqArgs a = mk_seq(x, pe, xin, hvo_out);
+  gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * x.P.total + 8.0 * x.c.n_enc_layers * x.W.pack_stride);
+  gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)x.P.total);
+  gt_seq_launch_update_pack(a, algo, params, x.grd, m, v, x.P.total, state, step_advanced, x.s);
+  return 0;
+}
 
 // gt_optimizer_step for a caller that steps with gt_train_step(skip_update = 1..3) (data-parallel: all-reduce in between): on the
 // sequence-resident path the update also writes the next step's fragment-ordered weight copies into ws, so that step may pass
@@ -1827,128 +1865,84 @@ extern "C" int gt_optimizer_step_ws(const gt_config* cfg, int algo, float* param
     return optimizer_step_impl(algo, params, grads, m, v, P.total, state, zero_grads, stream, 0, err, 1);
   }
   if (!params || !grads || !state) return gt_fail("gt_optimizer_step: params / grads / state must not be NULL");
-  if (algo != 0 && algo != 1) return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
-  if (algo == 1 && (!m || !v)) return gt_fail("gt_optimizer_step: adam needs m and v");
   Ctx x;
   if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
-  const SeqArgs a = mk_seq(x, nullptr, nullptr, nullptr);
-  gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
-  gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)P.total);
-  gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 0, (hipStream_t)stream);
+  if (seq_update_pack(x, algo, params, m, v, nullptr, nullptr, nullptr, state, 0)) return -1;
   gt_launch(step_inc_kernel, dim3(1), dim3(64), (hipStream_t)stream, state, xchg_err(x.W, ws),
             (const float*)(grads + P.total - 1));
   return launch_status("gt_optimizer_step_ws");
 }
-
 // ------------------------------------------------------------------------------------ fused train step
-// the update that ends a whole step (gt_train_step, gt_train_step_loss): the last launch of backward advanced the step counters already
-static int step_update(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe, const float* xin,
-                       float* hvo_out, float* ws, gt_step_state* state, gt_stream_t stream) {
-  PLayout P = param_layout(*cfg);
-  if (use_seq(*cfg)) {
-    // sequence-resident path: the update also writes the NEXT step's fragment-ordered weights (its caller may then pass
-    // GT_STEP_PACKS_CURRENT and the packing launch at the head of the step disappears)
-    if (algo != 0 && algo != 1) return gt_fail("optimizer algo %d unknown (0 = sgd, 1 = adam)", algo);
-    if (algo == 1 && (!m || !v)) return gt_fail("gt_optimizer_step: adam needs m and v");
-    Ctx x;
-    if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
-    const SeqArgs a = mk_seq(x, pe, xin, hvo_out);
-    gt_prof_tag("optimizer", 0, (algo ? 28.0 : 12.0) * P.total + 8.0 * cfg->n_enc_layers * x.W.pack_stride);
-    gt_dispatch("update kind folded_pack algo %d n %lld", algo, (long long)P.total);
-    gt_seq_launch_update_pack(a, algo, params, grads, m, v, P.total, state, 1, (hipStream_t)stream);
-    return launch_status("gt_train_step");
+// Where a fused step's loss comes from.  gt_train_step (by_opts false): the hit penalty -- the loss may ride in the forward's last launch,
+// which may then run on into backward phase 0 (FwdStep).  gt_train_step_loss (include/groove_hip.h): the loss as a launch of its own -- none
+// is handed over, so the forward runs exactly as gt_forward's and loss_ex_kernel writes d loss / d logits into ws.dlogits.
+struct StepLoss { bool by_opts; float penalty; const gt_loss_opts* lo; float* voice_stats; float* scratch; };
+// The one body of gt_train_step / gt_train_step_loss (`who`: the entry point, for its error messages).  One context and one plan for
+// the whole call; what the forward hands to the backward travels in `fs`, on this frame.
+static int train_step_impl(const char* who, const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v,
+                           const float* pe, const float* xin, const float* y, const StepLoss& loss, float* hvo_out, float* stats,
+                           float* tgt_scratch, float* ws, gt_step_state* state, int skip_update, gt_stream_t stream) {
+  if (check_cfg(cfg)) return -1;
+  if (!y || !state) return gt_fail("%s: y / state must not be NULL", who);
+  if (skip_update < 0 || skip_update > 7) return gt_fail("%s: skip_update %d outside 0..7", who, skip_update);
+  const bool packs_current = (skip_update & GT_STEP_PACKS_CURRENT) != 0;
+  skip_update &= 3;
+  const float* tgt_in = nullptr;
+  if (cfg->n_dec_layers > 0) {
+    if (!tgt_scratch) return gt_fail("%s: encoder-decoder model needs tgt_scratch", who);
+    tgt_in = tgt_scratch;
   }
-  return optimizer_step_impl(algo, params, grads, m, v, P.total, state, 1, stream, 1, xchg_err(ws_layout(*cfg), ws), 1) ? -1 : 0;
+  Ctx x;
+  if (make_ctx(x, cfg, params, grads, ws, state, 1, stream)) return -1;
+  x.plan = seq_plan(x.c);
+  if (skip_update == 3)                             // second half of a bucketed backward (tgt_scratch still holds the shifted y)
+    return backward_impl(std::move(x), xin, tgt_in, hvo_out, nullptr, 1, 2, nullptr, false, false);
+  // everything is checked before the first launch
+  if (!stats || !hvo_out || (loss.by_opts && !loss.scratch))
+    return gt_fail("%s: hvo_out / stats%s must not be NULL", who, loss.by_opts ? " / loss_scratch" : "");
+  if (loss.by_opts && loss_opts_check(who, loss.lo)) return -1;
+  const int M = x.M;
+  if (tgt_in) gt_launch(shift_right_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, y, tgt_scratch, M * GT_TGT);
+  // the launch that runs the output layer computes the loss as well where it can (one launch less): the sequence-resident launches
+  // always, one kernel per op where the OutputLayer runs on heads_fwd_kernel -- fs.loss_done says whether it did
+  unsigned* ticket = reinterpret_cast<unsigned*>(&state->pad2[0]);
+  FwdStep fs = {nullptr, 0.f, nullptr, nullptr, packs_current, false, false};
+  if (!loss.by_opts) { fs.y = y; fs.penalty = loss.penalty; fs.stats = stats; fs.ticket = ticket; }
+  if (forward_impl(x, pe, xin, tgt_in, hvo_out, &fs)) return -1;
+  if (loss.by_opts) {
+    loss_ex_launch(x.c, hvo_out, y, *loss.lo, stats, loss.voice_stats, ws + x.W.dlogits, true, loss.scratch, x.s);
+  } else if (!fs.loss_done) {
+    // loss + head-activation backward in one kernel: d loss / d logits straight into ws.dlogits; workgroup partials are
+    // combined by the last-arriving workgroup (ticket in the step state), so there is no memset node and the stats are
+    // bitwise reproducible.  grads: zero on entry (precondition), re-zeroed by the optimizer kernel.
+    gt_prof_tag("loss", 0, 12.0 * M * GT_TGT);
+    gt_launch(loss_kernel<true, true>, dim3((M * GT_VOICES + 255) / 256), dim3(256), x.s, (const float*)hvo_out, y, loss.penalty, stats,
+              ws + x.W.dlogits, M, ws + x.W.loss_part, ticket);
+  }
+  // whole step: the last launch of backward (the LayerNorm partials reduce -- every model has LayerNorms) also advances the
+  // step counters, and the optimizer is told so: one launch less than update + step_inc
+  if (backward_impl(x, xin, tgt_in, hvo_out, nullptr, 1, skip_update == 2 ? 1 : 0, skip_update == 0 ? state : nullptr, true, fs.b0_done))
+    return -1;
+  if (skip_update) return 0;
+  // the update that ends a whole step: the last launch of backward advanced the step counters already
+  if (!x.plan.seq) return optimizer_step_impl(algo, params, grads, m, v, x.P.total, state, 1, stream, 1, xchg_err(x.W, ws), 1) ? -1 : 0;
+  if (seq_update_pack(x, algo, params, m, v, pe, xin, hvo_out, state, 1)) return -1;
+  return launch_status(who);
 }
 extern "C" int gt_train_step(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe,
                              const float* xin, const float* y, float hit_loss_penalty, float* hvo_out, float* stats,
                              float* tgt_scratch, float* ws, gt_step_state* state, int skip_update, gt_stream_t stream) {
-  if (check_cfg(cfg)) return -1;
-  if (!y || !state) return gt_fail("gt_train_step: y / state must not be NULL");
-  if (skip_update < 0 || skip_update > 7) return gt_fail("gt_train_step: skip_update %d outside 0..7", skip_update);
-  const bool packs_current = (skip_update & GT_STEP_PACKS_CURRENT) != 0;
-  skip_update &= 3;
-  // the hand-offs to the sequence-resident forward / backward travel in thread-locals: whatever path leaves this function, they are cleared
-  struct Handoffs { ~Handoffs() { g_seq_loss.y = nullptr; g_seq_packs_current = false; g_seq_b0_fused = false; g_heads_loss_done = false; } } handoffs_guard;
-  const int M = cfg->batch * 32;
-  hipStream_t s = (hipStream_t)stream;
-  const float* tgt_in = nullptr;
-  if (cfg->n_dec_layers > 0) {
-    if (!tgt_scratch) return gt_fail("gt_train_step: encoder-decoder model needs tgt_scratch");
-    tgt_in = tgt_scratch;
-  }
-  if (skip_update == 3)                             // second half of a bucketed backward (tgt_scratch still holds the shifted y)
-    return backward_impl(cfg, params, grads, xin, tgt_in, hvo_out, nullptr, ws, state, 1, 1, stream, 2);
-  if (tgt_in) gt_launch(shift_right_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), s, y, tgt_scratch, M * GT_TGT);
-  // sequence-resident path: the launch that runs the output layer computes the loss as well (one launch less)
-  // (one kernel per op: the OutputLayer launch takes the loss along where it runs on heads_fwd_kernel -- it says so through g_heads_loss_done)
-  bool fuse_loss = use_seq(*cfg) && stats != nullptr && hvo_out != nullptr;
-  g_heads_loss_done = false;
-  if (stats != nullptr && hvo_out != nullptr && y != nullptr) g_seq_loss = SeqLoss{y, hit_loss_penalty, stats, reinterpret_cast<unsigned*>(&state->pad2[0])};
-  g_seq_packs_current = packs_current && use_seq(*cfg);
-  const int frc = gt_forward(cfg, params, pe, xin, tgt_in, hvo_out, ws, state, 1, stream);
-  g_seq_loss.y = nullptr;
-  g_seq_packs_current = false;
-  fuse_loss = fuse_loss || g_heads_loss_done;
-  g_heads_loss_done = false;
-  if (frc) return -1;
-  // loss + head-activation backward in one kernel: d loss / d logits straight into ws.dlogits; workgroup partials are
-  // combined by the last-arriving workgroup (ticket in the step state), so there is no memset node and the stats are
-  // bitwise reproducible.  grads: zero on entry (precondition), re-zeroed by the optimizer kernel.
-  WLayout W = ws_layout(*cfg);
-  if (!stats || !hvo_out) return gt_fail("gt_train_step: hvo_out / stats must not be NULL");
-  if (!fuse_loss) {
-    gt_prof_tag("loss", 0, 12.0 * M * GT_TGT);
-    gt_launch(loss_kernel<true, true>, dim3((M * GT_VOICES + 255) / 256), dim3(256), s, (const float*)hvo_out, y, hit_loss_penalty, stats,
-              ws + W.dlogits, M, ws + W.loss_part, reinterpret_cast<unsigned*>(&state->pad2[0]));
-  }
-  // whole step: the last launch of backward (the LayerNorm partials reduce -- every model has LayerNorms) also advances the
-  // step counters, and the optimizer is told so: one launch less than update + step_inc
-  const int brc = backward_impl(cfg, params, grads, xin, tgt_in, hvo_out, nullptr, ws, state, 1, 1, stream, skip_update == 2 ? 1 : 0,
-                                skip_update == 0 ? state : nullptr, true);
-  g_seq_b0_fused = false;                           // (consumed by that call; cleared here too in case it left early)
-  if (brc) return -1;
-  if (!skip_update) return step_update(cfg, algo, params, grads, m, v, pe, xin, hvo_out, ws, state, stream);
-  return 0;
+  const StepLoss loss = {false, hit_loss_penalty, nullptr, nullptr, nullptr};
+  return train_step_impl("gt_train_step", cfg, algo, params, grads, m, v, pe, xin, y, loss, hvo_out, stats, tgt_scratch, ws, state,
+                         skip_update, stream);
 }
-
-// gt_train_step with the loss as a launch of its own (include/groove_hip.h): no hand-off is set, so the forward runs exactly as gt_forward's
-// (the sequence-resident one does not go on into backward phase 0), loss_ex_kernel writes d loss / d logits into ws.dlogits, and backward
-// and update are gt_train_step's own calls with its own arguments.
 extern "C" int gt_train_step_loss(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe,
                                   const float* xin, const float* y, const gt_loss_opts* lo, float* voice_stats, float* loss_scratch,
                                   float* hvo_out, float* stats, float* tgt_scratch, float* ws, gt_step_state* state, int skip_update,
                                   gt_stream_t stream) {
-  if (check_cfg(cfg)) return -1;
-  if (!y || !state) return gt_fail("gt_train_step_loss: y / state must not be NULL");
-  if (skip_update < 0 || skip_update > 7) return gt_fail("gt_train_step_loss: skip_update %d outside 0..7", skip_update);
-  const bool packs_current = (skip_update & GT_STEP_PACKS_CURRENT) != 0;
-  skip_update &= 3;
-  struct Handoffs { ~Handoffs() { g_seq_packs_current = false; g_seq_b0_fused = false; } } handoffs_guard;
-  const int M = cfg->batch * 32;
-  hipStream_t s = (hipStream_t)stream;
-  const float* tgt_in = nullptr;
-  if (cfg->n_dec_layers > 0) {
-    if (!tgt_scratch) return gt_fail("gt_train_step_loss: encoder-decoder model needs tgt_scratch");
-    tgt_in = tgt_scratch;
-  }
-  g_seq_b0_fused = false;
-  if (skip_update == 3)                             // second half of a bucketed backward (tgt_scratch still holds the shifted y)
-    return backward_impl(cfg, params, grads, xin, tgt_in, hvo_out, nullptr, ws, state, 1, 1, stream, 2);
-  if (!stats || !hvo_out || !loss_scratch) return gt_fail("gt_train_step_loss: hvo_out / stats / loss_scratch must not be NULL");
-  if (!ws) return gt_fail("gt_train_step_loss: ws must not be NULL");
-  if (loss_opts_check("gt_train_step_loss", lo)) return -1;
-  if (tgt_in) gt_launch(shift_right_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), s, y, tgt_scratch, M * GT_TGT);
-  g_seq_packs_current = packs_current && use_seq(*cfg);
-  const int frc = gt_forward(cfg, params, pe, xin, tgt_in, hvo_out, ws, state, 1, stream);
-  g_seq_packs_current = false;
-  if (frc) return -1;
-  loss_ex_launch(*cfg, hvo_out, y, *lo, stats, voice_stats, ws + ws_layout(*cfg).dlogits, true, loss_scratch, s);
-  const int brc = backward_impl(cfg, params, grads, xin, tgt_in, hvo_out, nullptr, ws, state, 1, 1, stream, skip_update == 2 ? 1 : 0,
-                                skip_update == 0 ? state : nullptr, true);
-  if (brc) return -1;
-  if (!skip_update) return step_update(cfg, algo, params, grads, m, v, pe, xin, hvo_out, ws, state, stream);
-  return 0;
+  const StepLoss loss = {true, 0.f, lo, voice_stats, loss_scratch};
+  return train_step_impl("gt_train_step_loss", cfg, algo, params, grads, m, v, pe, xin, y, loss, hvo_out, stats, tgt_scratch, ws, state,
+                         skip_update, stream);
 }
 
 // ------------------------------------------------------------------------------------ data-parallel guard element
