@@ -308,6 +308,8 @@ f32x16 mfma32_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
 }
 
 void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& body) {
+  // GT_EMU_DRY=1 (read per launch, as GT_TRACE_DISPATCH is): the host side runs, no kernel body does -- tools/dispatch_trace.py
+  { const char* e = getenv("GT_EMU_DRY"); if (e && e[0] == '1') return; }
   nthreads = block.x * block.y * block.z;
   if (nthreads > 1024 || (nthreads % 64) != 0) { fprintf(stderr, "hip_emu: bad block size %d\n", nthreads); abort(); }
   if (smem > 160 * 1024) { fprintf(stderr, "hip_emu: dynamic LDS %zu > 160 KiB\n", smem); abort(); }

@@ -429,8 +429,6 @@ extern "C" int gt_ws_find(const gt_config* cfg, const char* name, int layer, int
   return 0;
 }
 
-static thread_local int g_bf16 = 0;                  // precision of the call being enqueued (set by make_ctx / the entry points)
-
 // ------------------------------------------------------------------------------------ launch helpers
 // The sequence-resident schedule of ONE call (seq_plan(), below the rules it wraps): an entry point asks once, and the forward, the
 // backward, the bucket cut and the update of that call all read the same answers.  hc: the head-dim class of the kernels' instantiations.
@@ -449,6 +447,7 @@ struct Ctx {
   hipStream_t s;
   WgradBatch* wb;            // weight gradients queue up here and leave as grouped dispatches
   LnJobs* ln;                // LayerNorm parameter-gradient partials to be summed at the end of backward
+  mutable const char* refused;   // first bf16-only tensor that met a kernel which cannot take it (need16 writes, launch_status reports): dies with the call
 };
 // next partials block for a LayerNorm backward launched with `nwg` workgroups; registers the reduction job
 static float* ln_job(const Ctx& x, int64_t gamma_off, int nwg) {
@@ -475,8 +474,7 @@ static bool only16(const Ctx& x, const float* p) {
   return r && r->only;
 }
 // a consumer of a bf16-only tensor that could not take the bf16-source kernel would read an unwritten fp32 region: refuse loudly
-static thread_local const char* g_store_error = nullptr;
-static void need16(bool ok, const char* what) { if (!ok && g_store_error == nullptr) g_store_error = what; }
+static void need16(const Ctx& x, bool ok, const char* what) { if (!ok && x.refused == nullptr) x.refused = what; }
 // where an encoder-layer weight matrix lies in a copy that keeps [in_w | out_w | w1 | w2] per layer, `stride` elements apart (-1: not one of them)
 static int64_t enc_w_slot(const Ctx& x, const float* W, int64_t stride) {
   const int64_t off = W - x.prm, d = x.d, F = x.F;
@@ -520,33 +518,33 @@ static DropArgs mk_drop(const Ctx& x, int site) {
 }
 static DropArgs no_drop() { DropArgs da; da.st = nullptr; da.site = 0u; da.thr = 0u; da.scale = 1.0f; return da; }
 static int lsite(int gl, int kind) { return GT_SITE_LAYER0 + 8 * gl + kind; }
-static GemmArgs mk_gemm(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K) {
+static GemmArgs mk_gemm(const Ctx& x, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
   g.mask_scale = 1.0f;
   g.drop.scale = 1.0f;
-  g.bf16 = g_bf16;
+  g.bf16 = x.c.precision ? 1 : 0;
   return g;
 }
 // y = x W^T + b  (forward "NT");  out16 (precision = 2): y stored in bf16 ALONE at out16 (row stride ldout), `out` not written
 static void linear_fwd(const Ctx& x, const float* in, int ldin, const float* W, const float* b, float* out, int ldout,
                        int N, int K, uint16_t* out16 = nullptr) {
-  GemmArgs g = mk_gemm(in, ldin, W, K, out16 ? nullptr : out, ldout, x.M, N, K);
+  GemmArgs g = mk_gemm(x, in, ldin, W, K, out16 ? nullptr : out, ldout, x.M, N, K);
   g.bias = b;
   if (ldin == K) { g.A16 = sh_act(x, in); g.B16 = sh_w(x, W, false); g.lda16 = g.ldb16 = K; }
-  if (out16) { g.C16 = out16; g.ldc16 = ldout; need16(gemm_on_big_kernel<false, EPI_STORE>(g), "Linear with a bf16-only output (precision 2)"); }
-  if (only16(x, in)) need16(g.A16 && g.B16 && gemm32h_ok(g, EPI_STORE), "Linear forward of a bf16-only tensor");
+  if (out16) { g.C16 = out16; g.ldc16 = ldout; need16(x, gemm_on_big_kernel<false, EPI_STORE>(g), "Linear with a bf16-only output (precision 2)"); }
+  if (only16(x, in)) need16(x, g.A16 && g.B16 && gemm32h_ok(g, EPI_STORE), "Linear forward of a bf16-only tensor");
   gemm_launch<false, false, EPI_STORE>(g, x.s);
 }
 // dW (N_w x K_w) += dY^T X ; db += colsum(dY)       ("TN", split over tokens, fp32 atomics)
 static void wgrad(const Ctx& x, const float* dY, int ldy, const float* X, int ldx, float* dW, float* db, int Nw, int Kw) {
-  GemmArgs g = mk_gemm(dY, ldy, X, ldx, dW, Kw, Nw, Kw, x.M);
+  GemmArgs g = mk_gemm(x, dY, ldy, X, ldx, dW, Kw, Nw, Kw, x.M);
   g.dbias = db;
   if (ldy == Nw && ldx == Kw) { g.A16 = sh_act(x, dY); g.B16 = sh_act(x, X); g.lda16 = Nw; g.ldb16 = Kw; }     // bf16 shadows of dY / X (precision = 1)
   if (only16(x, dY) || only16(x, X)) {
     const long t128 = (long)(Nw / 128) * (Kw / 128);
-    need16(x.wb != nullptr && g.A16 && (g.B16 || !only16(x, X)) && wgrad32_ok(g) && t128 * ((x.M + 511) / 512) >= GT_WGRAD_T128_MIN,
+    need16(x, x.wb != nullptr && g.A16 && (g.B16 || !only16(x, X)) && wgrad32_ok(g) && t128 * ((x.M + 511) / 512) >= GT_WGRAD_T128_MIN,
            "weight gradient of a bf16-only tensor");
   }
   if (x.wb) wgrad_queue(*x.wb, g, x.s);
@@ -559,23 +557,23 @@ extern "C" int gt_set_deterministic(int on) { g_deterministic = on != 0; return 
 static void dgrad_store(const Ctx& x, const float* dY, int ldy, const float* W, int ldw, float* dX, int N, int K, int accumulate,
                         uint16_t* out16 = nullptr) {
   if (out16 != nullptr) {
-    GemmArgs g = mk_gemm(dY, ldy, W, ldw, nullptr, N, x.M, N, K);
+    GemmArgs g = mk_gemm(x, dY, ldy, W, ldw, nullptr, N, x.M, N, K);
     if (ldy == K && ldw == N) { g.A16 = sh_act(x, dY); g.B16 = sh_w(x, W, true); g.lda16 = g.ldb16 = K; }
     g.C16 = out16; g.ldc16 = N;
-    need16(!accumulate && gemm_on_big_kernel<true, EPI_STORE>(g) && (!only16(x, dY) || (g.A16 && g.B16)), "dgrad with a bf16-only output (precision 2)");
+    need16(x, !accumulate && gemm_on_big_kernel<true, EPI_STORE>(g) && (!only16(x, dY) || (g.A16 && g.B16)), "dgrad with a bf16-only output (precision 2)");
     gemm_launch<false, true, EPI_STORE>(g, x.s);
     return;
   }
   if (const float* wt = (ldw == N) ? wT_of(x, W) : nullptr) {      // dX = dY (W^T)^T: the NT form over the transposed copy
-    GemmArgs g = mk_gemm(dY, ldy, wt, K, dX, N, x.M, N, K);
+    GemmArgs g = mk_gemm(x, dY, ldy, wt, K, dX, N, x.M, N, K);
     g.accumulate = accumulate; g.as_dgrad = 1;
     gemm_launch<false, false, EPI_STORE>(g, x.s);
     return;
   }
-  GemmArgs g = mk_gemm(dY, ldy, W, ldw, dX, N, x.M, N, K);
+  GemmArgs g = mk_gemm(x, dY, ldy, W, ldw, dX, N, x.M, N, K);
   g.accumulate = accumulate;
   if (ldy == K && ldw == N) { g.A16 = sh_act(x, dY); g.B16 = sh_w(x, W, true); g.lda16 = g.ldb16 = K; }      // (W^T: [N][K], k contiguous)
-  if (only16(x, dY)) need16(g.A16 && g.B16 && gemm32h_ok(g, EPI_STORE), "dgrad of a bf16-only tensor");
+  if (only16(x, dY)) need16(x, g.A16 && g.B16 && gemm32h_ok(g, EPI_STORE), "dgrad of a bf16-only tensor");
   gemm_launch<false, true, EPI_STORE>(g, x.s);
 }
 // dz = LNbwd(dY W + res) with the LayerNorm whose (xhat, rstd, gamma) are given; dzm = dz * dropout mask
@@ -607,6 +605,8 @@ extern "C" int gt_set_ln_exchange(int on) { g_ln_xchg = on < 0 ? -1 : on != 0; r
 static int seq_cu_count();
 static int xchg_cus();
 static int g_xchg_spin_max = 0;
+// polling bound of an in-launch exchange: gt_set_xchg_spin_max's while positive, else the exchange's compiled default
+static int xchg_spin_max(int dflt) { return g_xchg_spin_max > 0 ? g_xchg_spin_max : dflt; }
 // 0 = off, 1 = on where it applies (the default), 2 = forced (gt_set_ln_exchange(1) / GT_LN_XCHG=1: no lower bound on the tile count -- tests)
 static int ln_xchg_mode() {
   if (g_ln_xchg >= 0) return g_ln_xchg ? 2 : 0;
@@ -616,9 +616,8 @@ static int ln_xchg_mode() {
 static bool ln_xchg(const Ctx& x) { return ln_xchg_mode() != 0 && !(x.c.flags & GT_CFG_NO_LN_XCHG) && x.W.rowx >= 0; }
 static void ln_xchg_args(const Ctx& x, GemmArgs& g) {
   g.rowx = reinterpret_cast<unsigned*>(x.ws + x.W.rowx);
-  g.spin_max = g_xchg_spin_max > 0 ? g_xchg_spin_max : GT_ROWX_SPIN_MAX;
+  g.spin_max = xchg_spin_max(GT_ROWX_SPIN_MAX);
 }
-// the fused launch on whichever 64x64 kernel the operands allow (both bf16 shadows -> gemm64h; a bf16-ONLY input needs that one); false: not taken
 // which geometry the row exchange runs on for this (M, N): 64 = the 64x64 kernels of gt_gemm64.h, 128 = the big tile (round 6), 0 = none
 static int ln_xchg_tile(const GemmArgs& g) {
   if (gemm64_ln_shape(g, xchg_cus(), ln_xchg_mode() == 2)) return 64;
@@ -627,35 +626,42 @@ static int ln_xchg_tile(const GemmArgs& g) {
   if (!off128 && gemm32_ln_shape(g, xchg_cus())) return 128;
   return (!off32 && gemm_xln32_shape(g, xchg_cus())) ? 32 : 0;
 }
-template <bool BKM, int EPI>
-static bool ln_xchg_launch(const Ctx& x, const GemmArgs& g, bool in_only16) {
+// Which kernel takes the Linear / dgrad g with the LayerNorm (EPI_RES_LN) / its backward (EPI_RES_LNBWD) in its epilogue: the ONE statement of that rule
+// (linear_res_ln and dgrad_lnbwd pick, then run).  H: bf16-source, both operand shadows; else fp32-source -- not for a bf16-ONLY input (in_only16).
+enum LnXchgKind { LX_NONE, LX_128H, LX_128, LX_32, LX_64H, LX_64 };
+static int ln_xchg_rows(LnXchgKind k) { return k == LX_NONE ? 0 : k == LX_32 ? 32 : k <= LX_128 ? 128 : 64; }
+static LnXchgKind ln_xchg_pick(const GemmArgs& g, int epi, bool bkm, bool in_only16) {
   const int tile = ln_xchg_tile(g);
+  const bool both16 = g.bf16 && g.A16 && g.B16;
   if (tile == 128) {
-    if (!gemm32_ln_ok(g, EPI)) return false;
-    if (g.bf16 && g.A16 && g.B16 && gemm32h_ok(g, EPI)) { gemm64_trace("ln128 bf16-source", g, false, EPI); gemm32h_launch<false, EPI>(g, x.s); return true; }
-    if (in_only16 || (g.bf16 && g.A16 && g.B16)) return false;
-    if (!gemm32_ok(g, EPI, BKM)) return false;
-    gemm64_trace("ln128 fp32-source", g, BKM, EPI);
-    gemm32_launch<BKM, EPI>(g, x.s);
-    return true;
+    if (!gemm32_ln_ok(g, epi)) return LX_NONE;
+    if (both16 && gemm32h_ok(g, epi)) return LX_128H;
+    return (!in_only16 && !both16 && gemm32_ok(g, epi, bkm)) ? LX_128 : LX_NONE;
   }
-  if (tile == 32) {
-    // the generic kernel's 32x32 tiles (the d_model-256 YAMLs at 512 ... 2048 tokens): fp32 sources; precision 1 rounds them on their way into LDS
-    constexpr int EPIX = EPI == EPI_RES_LN ? EPI_RES_LN_X : EPI_RES_LNBWD_X;
-    if (in_only16 || !gemm_xln32_ok(g, EPIX)) return false;
-    GemmArgs f = g;
-    f.k_chunk = (f.K + 63) / 64 * 64;
-    gemm64_trace("ln32 fp32-source", f, BKM, EPI);
-    if (f.bf16) gemm_launch_cfg<2, 2, 1, 1, 64, false, BKM, EPIX, 1>(f, 1, x.s);
-    else        gemm_launch_cfg<2, 2, 1, 1, 64, false, BKM, EPIX>(f, 1, x.s);
-    return true;
+  if (tile == 32) return (!in_only16 && gemm_xln32_ok(g, epi == EPI_RES_LN ? EPI_RES_LN_X : EPI_RES_LNBWD_X)) ? LX_32 : LX_NONE;
+  if (tile != 64) return LX_NONE;
+  if (both16 && gemm64h_ok(g, epi)) return LX_64H;
+  return (!in_only16 && !both16 && gemm64_ok(g, epi)) ? LX_64 : LX_NONE;
+}
+template <bool BKM, int EPI>
+static void ln_xchg_run(const Ctx& x, const GemmArgs& g, LnXchgKind k) {
+  switch (k) {
+    case LX_128H: gemm64_trace("ln128 bf16-source", g, false, EPI); gemm32h_launch<false, EPI>(g, x.s); break;
+    case LX_128:  gemm64_trace("ln128 fp32-source", g, BKM, EPI); gemm32_launch<BKM, EPI>(g, x.s); break;
+    case LX_32: {
+      // the generic kernel's 32x32 tiles (the d_model-256 YAMLs at 512 ... 2048 tokens): fp32 sources; precision 1 rounds them on their way into LDS
+      constexpr int EPIX = EPI == EPI_RES_LN ? EPI_RES_LN_X : EPI_RES_LNBWD_X;
+      GemmArgs f = g;
+      f.k_chunk = (f.K + 63) / 64 * 64;
+      gemm64_trace("ln32 fp32-source", f, BKM, EPI);
+      if (f.bf16) gemm_launch_cfg<2, 2, 1, 1, 64, false, BKM, EPIX, 1>(f, 1, x.s);
+      else        gemm_launch_cfg<2, 2, 1, 1, 64, false, BKM, EPIX>(f, 1, x.s);
+      break;
+    }
+    case LX_64H:  gemm64h_launch<false, EPI>(g, x.s); break;
+    case LX_64:   gemm64_launch<BKM, EPI>(g, x.s); break;
+    case LX_NONE: break;
   }
-  if (tile != 64) return false;
-  if (g.bf16 && g.A16 && g.B16 && gemm64h_ok(g, EPI)) { gemm64h_launch<false, EPI>(g, x.s); return true; }
-  if (in_only16 || (g.bf16 && g.A16 && g.B16)) return false;
-  if (!gemm64_ok(g, EPI)) return false;
-  gemm64_launch<BKM, EPI>(g, x.s);
-  return true;
 }
 // does the row exchange take this shape's d_model-wide Linears?  (the shape rule of gemm64_ln_shape for N = d_model)
 static bool ln_xchg_rows(const Ctx& x) {
@@ -680,26 +686,21 @@ static int dgrad_lnbwd(const Ctx& x, const float* dY, int ldy, const float* W, i
     if (ln_xchg(x) && x.ln && x.ln->n < GT_LN_JOBS_MAX) {
       // ONE launch: the dgrad on 64x64 tiles, the LayerNorm backward in its epilogue (row sums through the in-launch exchange)
       const float* wt = wT_of(x, W);                            // (precision 1 without shadows: the NT form over the fp32 transpose)
-      GemmArgs g = wt ? mk_gemm(dY, ldy, wt, K, dz, x.d, x.M, x.d, K) : mk_gemm(dY, ldy, W, x.d, dz, x.d, x.M, x.d, K);
+      GemmArgs g = wt ? mk_gemm(x, dY, ldy, wt, K, dz, x.d, x.M, x.d, K) : mk_gemm(x, dY, ldy, W, x.d, dz, x.d, x.M, x.d, K);
       if (!wt && ldy == K) { g.A16 = sh_act(x, dY); g.B16 = sh_w(x, W, true); g.lda16 = g.ldb16 = K; }
       g.as_dgrad = 1;
       g.res = res; g.ldres = x.d; g.xhat = xhat; g.rstd = rstd; g.gamma = x.prm + gamma_off;
       g.C2 = (x.drop && !only16(x, dzm)) ? dzm : nullptr;
       g.C16 = sh_act(x, x.drop ? dzm : dz); g.ldc16 = x.d;
       g.drop = mk_drop(x, site);
-      float dummy; g.ln_part = &dummy;                          // (eligibility first: a registered job cannot be taken back)
+      float dummy; g.ln_part = &dummy;                          // (pick first: a registered job cannot be taken back)
       ln_xchg_args(x, g);
-      const int tile = ln_xchg_tile(g);
-      const bool both16 = g.bf16 && g.A16 && g.B16;
-      const bool h16 = tile != 32 && both16 && (tile == 128 ? gemm32_ln_ok(g, EPI_RES_LNBWD) && gemm32h_ok(g, EPI_RES_LNBWD) : gemm64h_ok(g, EPI_RES_LNBWD));
-      const bool f32 = tile == 32 ? (!only16(x, dY) && gemm_xln32_ok(g, EPI_RES_LNBWD_X))
-                     : !only16(x, dY) && !both16 &&
-                       (tile == 128 ? gemm32_ln_ok(g, EPI_RES_LNBWD) && gemm32_ok(g, EPI_RES_LNBWD, wt == nullptr) : gemm64_ok(g, EPI_RES_LNBWD));
-      if (tile != 0 && (h16 || f32)) {
-        g.ln_part = ln_job(x, gamma_off, x.M / tile);
-        if (wt) { if (ln_xchg_launch<false, EPI_RES_LNBWD>(x, g, only16(x, dY))) return 0; }
-        else if (ln_xchg_launch<true, EPI_RES_LNBWD>(x, g, only16(x, dY))) return 0;
-        return gt_fail("dgrad + LayerNorm backward: the fused launch was refused after its job was registered");
+      const LnXchgKind k = ln_xchg_pick(g, EPI_RES_LNBWD, wt == nullptr, only16(x, dY));
+      if (k != LX_NONE) {
+        g.ln_part = ln_job(x, gamma_off, x.M / ln_xchg_rows(k));
+        if (wt) ln_xchg_run<false, EPI_RES_LNBWD>(x, g, k);
+        else    ln_xchg_run<true, EPI_RES_LNBWD>(x, g, k);
+        return 0;
       }
     }
     // precision = 2: the dgrad output lives in bf16 alone -- in the region that receives the bf16 copy of the norm's result (in place)
@@ -708,7 +709,7 @@ static int dgrad_lnbwd(const Ctx& x, const float* dY, int ldy, const float* W, i
     ln_bwd(x, dz, res, xhat, rstd, gamma_off, dz, dzm, site, t16);
     return 0;
   }
-  GemmArgs g = mk_gemm(dY, ldy, W, x.d, dz, x.d, x.M, x.d, K);
+  GemmArgs g = mk_gemm(x, dY, ldy, W, x.d, dz, x.d, x.M, x.d, K);
   g.res = res; g.ldres = x.d;
   g.xhat = xhat; g.rstd = rstd; g.gamma = x.prm + gamma_off;
   g.dgamma = x.grd + gamma_off; g.dbeta = x.grd + gamma_off + (x.d + 63) / 64 * 64;   // bias tensor follows the weight
@@ -738,7 +739,7 @@ static void ln_bwd(const Ctx& x, const float* dy, const float* res, const float*
                    dzm32, mk_drop(x, site), part, x.M, rpw, dzm16, dy16);
     return;
   }
-  need16(dy16 == nullptr, "LayerNorm backward of a bf16-only gradient (precision 2)");
+  need16(x, dy16 == nullptr, "LayerNorm backward of a bf16-only gradient (precision 2)");
   gt_dispatch("ln_bwd variant generic M %d d %d rpw %d in16 0", x.M, x.d, rpw);
   gt_launch(ln_bwd_kernel, dim3(nblk), dim3(256), x.s, dy, res, xhat, rstd,
             x.prm + gamma_off, dz, (x.drop && !only16(x, dzm)) ? dzm : (float*)nullptr, mk_drop(x, site), x.grd + gamma_off,
@@ -765,79 +766,66 @@ static void ln_bwd2(const Ctx& x, const float* dy, const float* xhat_o, const fl
 }
 // second norm applied right after linear_res_ln's (the final encoder / decoder norm after the last layer)
 struct SecondNorm { int64_t gamma_off; float* y; float* xhat; float* rstd; };
+// The LayerNorm-forward row pass behind a Linear: n.y = LN_n(drop(in) + res) [; second->y = LN_second(n.y)]; in16 (precision 2): where the rows
+// live in bf16 alone.  res == nullptr: a plain norm (the one after a row-fused first).  y16: bf16 copy of n.y (one norm only).
+static void ln_fwd_rows(const Ctx& x, const float* in, const uint16_t* in16, const float* res, const DropArgs& da, const SecondNorm& n,
+                        uint16_t* y16, const SecondNorm* second) {
+  const int64_t bo = (x.d + 63) / 64 * 64;          // a norm's bias tensor follows its weight
+  const float* gm = x.prm + n.gamma_off;
+  gt_prof_tag("ln_fwd", 0, ((second ? 24.0 : res ? 16.0 : 12.0) - (in16 ? 2.0 : 0.0)) * x.M * x.d);
+  gt_dispatch("ln_fwd variant %s M %d d %d in16 %d", second ? "two_norms" : "one_norm", x.M, x.d, in16 != nullptr);
+  if (second) {
+    const float* gm2 = x.prm + second->gamma_off;
+    gt_launch(ln_fwd2_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, in, res, da, gm, gm + bo, n.y, n.xhat, n.rstd, gm2, gm2 + bo,
+              second->y, second->xhat, second->rstd, x.M, x.d, in16);
+  } else {
+    gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, in, res, da, gm, gm + bo, n.y, n.xhat, n.rstd, x.M, x.d, x.d, x.d, x.d,
+              y16, in16);
+  }
+}
 // x_out = LN(drop(in W^T + b) + res)   [; second->y = LN_second(x_out)]
 static int linear_res_ln(const Ctx& x, const float* in, int K, int64_t w_off, int64_t b_off, const float* res, int64_t gamma_off,
                          float* out, float* xhat, float* rstd, int site, const SecondNorm* second = nullptr) {
-  GemmArgs g = mk_gemm(in, K, x.prm + w_off, K, out, x.d, x.M, x.d, K);
+  GemmArgs g = mk_gemm(x, in, K, x.prm + w_off, K, out, x.d, x.M, x.d, K);
   g.bias = x.prm + b_off;
   const int64_t bo = (x.d + 63) / 64 * 64;          // a norm's bias tensor follows its weight
   if (!row_fused(x)) {
     g.A16 = sh_act(x, in); g.B16 = sh_w(x, x.prm + w_off, false); g.lda16 = g.ldb16 = K;
-    if (only16(x, in)) need16(g.A16 && g.B16 && gemm32h_ok(g, EPI_STORE), "Linear (+ LayerNorm) of a bf16-only tensor");
+    if (only16(x, in)) need16(x, g.A16 && g.B16 && gemm32h_ok(g, EPI_STORE), "Linear (+ LayerNorm) of a bf16-only tensor");
     // precision = 2: the Linear output ahead of the norm lives in bf16 alone -- in the region that then receives the bf16 copy of the norm's
     // result (the row pass reads a row into registers before it writes any of it)
     uint16_t* t16 = p2(x.c) ? sh_act(x, out) : nullptr;
     // ONE launch: the Linear with dropout + residual + LayerNorm in its epilogue (row statistics through the in-launch exchange: 64x64 tiles at
     // a GPU's share of a data-parallel batch, the big tile from 8192 tokens at d_model 512 -- round 6)
-    auto try_fused = [&]() -> bool {
-      if (second || !ln_xchg(x)) return false;
+    // (precision 2 fuses on the big tile only: the pre-norm output never leaves the registers -- rounded to bf16 there, round16: the numbers of
+    //  the bf16-stored form without its round trip.  At 2048 tokens the stored form + row pass stays: measured 0.866 / 0.867 ms against
+    //  0.870 / 0.870 fused (profiles/r06_ab_p2_fused_forward.txt))
+    if ((t16 == nullptr || ln_xchg_tile(g) == 128) && !second && ln_xchg(x)) {
       GemmArgs f = g;
       f.res = res; f.ldres = x.d; f.gamma = x.prm + gamma_off; f.beta = x.prm + gamma_off + bo;
       f.aux = xhat; f.aux2 = rstd; f.drop = mk_drop(x, site);
       f.C16 = sh_act(x, out); f.ldc16 = x.d;
       f.round16 = t16 != nullptr;
       ln_xchg_args(x, f);
-      return ln_xchg_launch<false, EPI_RES_LN>(x, f, only16(x, in));
-    };
+      const LnXchgKind k = ln_xchg_pick(f, EPI_RES_LN, false, only16(x, in));
+      if (k != LX_NONE) { ln_xchg_run<false, EPI_RES_LN>(x, f, k); return 0; }
+    }
     if (t16 != nullptr) {
-      // (precision 2 on the big tile: the pre-norm output never leaves the registers -- rounded to bf16 there, round16: the numbers of the
-      //  bf16-stored form without its round trip.  At 2048 tokens the stored form + row pass stays: measured 0.866 / 0.867 ms against
-      //  0.870 / 0.870 fused (profiles/r06_ab_p2_fused_forward.txt))
-      if (ln_xchg_tile(g) == 128 && try_fused()) return 0;
       g.C = nullptr; g.C16 = t16; g.ldc16 = x.d;
-      need16(gemm_on_big_kernel<false, EPI_STORE>(g), "Linear (+ LayerNorm) with a bf16-only output (precision 2)");
-      gemm_launch<false, false, EPI_STORE>(g, x.s);
-      if (second) {
-        gt_prof_tag("ln_fwd", 0, 22.0 * x.M * x.d);
-        gt_dispatch("ln_fwd variant two_norms M %d d %d in16 1", x.M, x.d);
-        gt_launch(ln_fwd2_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
-                  x.prm + gamma_off + bo, out, xhat, rstd, (const float*)(x.prm + second->gamma_off),
-                  (const float*)(x.prm + second->gamma_off + bo), second->y, second->xhat, second->rstd, x.M, x.d, (const uint16_t*)t16);
-        return 0;
-      }
-      gt_prof_tag("ln_fwd", 0, 14.0 * x.M * x.d);
-      gt_dispatch("ln_fwd variant one_norm M %d d %d in16 1", x.M, x.d);
-      gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
-                x.prm + gamma_off + bo, out, xhat, rstd, x.M, x.d, x.d, x.d, x.d, t16, (const uint16_t*)t16);
-      return 0;
+      need16(x, gemm_on_big_kernel<false, EPI_STORE>(g), "Linear (+ LayerNorm) with a bf16-only output (precision 2)");
     }
-    if (try_fused()) return 0;
     gemm_launch<false, false, EPI_STORE>(g, x.s);
-    if (second) {
-      gt_prof_tag("ln_fwd", 0, 24.0 * x.M * x.d);
-      gt_dispatch("ln_fwd variant two_norms M %d d %d in16 0", x.M, x.d);
-      gt_launch(ln_fwd2_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
-                x.prm + gamma_off + bo, out, xhat, rstd, (const float*)(x.prm + second->gamma_off),
-                (const float*)(x.prm + second->gamma_off + bo), second->y, second->xhat, second->rstd, x.M, x.d, (const uint16_t*)nullptr);
-      return 0;
-    }
-    gt_prof_tag("ln_fwd", 0, 16.0 * x.M * x.d);
-    gt_dispatch("ln_fwd variant one_norm M %d d %d in16 0", x.M, x.d);
-    gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, res, mk_drop(x, site), x.prm + gamma_off,
-              x.prm + gamma_off + bo, out, xhat, rstd, x.M, x.d, x.d, x.d, x.d, sh_act(x, out), (const uint16_t*)nullptr);
+    const SecondNorm first = {gamma_off, out, xhat, rstd};
+    ln_fwd_rows(x, out, t16, res, mk_drop(x, site), first, sh_act(x, out), second);
     return 0;
   }
   g.res = res; g.ldres = x.d;
-  g.gamma = x.prm + gamma_off; g.beta = x.prm + gamma_off + (x.d + 63) / 64 * 64;
+  g.gamma = x.prm + gamma_off; g.beta = x.prm + gamma_off + bo;
   g.aux = xhat; g.aux2 = rstd;
   g.drop = mk_drop(x, site);
   if (gemm_launch_row<false, false, EPI_RES_LN>(g, x.s)) return -1;
-  if (second) {                                     // fused row tile for the first norm: the second one is its own pass
-    gt_prof_tag("ln_fwd", 0, 12.0 * x.M * x.d);
-    gt_dispatch("ln_fwd variant one_norm M %d d %d in16 0", x.M, x.d);
-    gt_launch(ln_fwd_kernel, dim3((x.M + 3) / 4), dim3(256), x.s, (const float*)out, (const float*)nullptr, no_drop(),
-              x.prm + second->gamma_off, x.prm + second->gamma_off + bo, second->y, second->xhat, second->rstd, x.M, x.d, x.d, x.d, x.d, (uint16_t*)nullptr, (const uint16_t*)nullptr);
-  }
+  // fused row tile for the first norm: the second one is its own pass
+  if (second) ln_fwd_rows(x, out, nullptr, nullptr, no_drop(), *second, nullptr, nullptr);
   return 0;
 }
 // head dims served by the MFMA attention kernels (0: use the generic LDS/VALU kernels)
@@ -866,13 +854,13 @@ static void attention_fwd(const Ctx& x, const float* q, int ldq, const float* k,
   a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.P = P; a.ctx = ctx; a.ldc = x.d;
   a.H = x.H; a.hd = x.hd; a.scale = 1.0f / sqrtf((float)x.hd); a.causal = causal; a.drop = mk_drop(x, site);
   a.ctx16 = attn_mfma_hd(x) > 0 ? sh_act(x, ctx) : nullptr;
-  if (only16(x, ctx)) { need16(a.ctx16 != nullptr, "attention output stored in bf16 alone"); if (a.ctx16) a.ctx = nullptr; }
+  if (only16(x, ctx)) { need16(x, a.ctx16 != nullptr, "attention output stored in bf16 alone"); if (a.ctx16) a.ctx = nullptr; }
   gt_prof_tag("attn_fwd", 4.0 * x.M * 32 * x.d, 4.0 * (4.0 * x.M * x.d + 1024.0 * x.c.batch * x.H));
   const dim3 grid(x.c.batch * x.H);
   if (in16) {
     a.q16 = reinterpret_cast<const uint16_t*>(q); a.k16 = a.q16 + (k - q); a.v16 = a.q16 + (v - q);
     a.q = a.k = a.v = nullptr;
-    need16(((ldq | ldkv) & 3) == 0 && (attn_mfma_hd(x) == 64 || attn_mfma_hd(x) == 128), "attention over bf16-stored q / k / v (precision 2)");
+    need16(x, ((ldq | ldkv) & 3) == 0 && (attn_mfma_hd(x) == 64 || attn_mfma_hd(x) == 128), "attention over bf16-stored q / k / v (precision 2)");
     gt_dispatch("attn_fwd kernel lds%d-bf16 pairs %u", attn_mfma_hd(x), grid.x);
     if (attn_mfma_hd(x) == 128) gt_launch(attn_fwd_lds_kernel<128, true>, grid, dim3(128), x.s, a);
     else gt_launch(attn_fwd_lds_kernel<64, true>, grid, dim3(128), x.s, a);
@@ -900,7 +888,7 @@ static void attention_bwd(const Ctx& x, const float* q, int ldq, const float* k,
   a.H = x.H; a.hd = x.hd; a.scale = 1.0f / sqrtf((float)x.hd); a.drop = mk_drop(x, site);
   a.dctx = dctx; a.lddc = x.d; a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddkv; a.lddv = lddkv;
   if (attn_mfma_hd(x) > 0 && dk == dq + x.d && dv == dq + 2 * x.d && lddq == 3 * x.d && lddkv == 3 * x.d) a.dqkv16 = sh_act(x, dq);
-  if (only16(x, dq)) { need16(a.dqkv16 != nullptr, "attention gradients stored in bf16 alone"); if (a.dqkv16) { a.dq = nullptr; a.dk = nullptr; a.dv = nullptr; } }
+  if (only16(x, dq)) { need16(x, a.dqkv16 != nullptr, "attention gradients stored in bf16 alone"); if (a.dqkv16) { a.dq = nullptr; a.dk = nullptr; a.dv = nullptr; } }
   gt_prof_tag("attn_bwd", 10.0 * x.M * 32 * x.d, 4.0 * (7.0 * x.M * x.d + 1024.0 * x.c.batch * x.H));
   const dim3 grid(x.c.batch * x.H);
   // head_dim 64 with the chip full: the LDS-staged form (every operand byte requested once, 16 bytes at a time)
@@ -909,7 +897,7 @@ static void attention_bwd(const Ctx& x, const float* q, int ldq, const float* k,
   if (in16) {                                        // precision = 2: q / k / v / dctx stored in bf16 alone, widened on their way into LDS
     a.q16 = reinterpret_cast<const uint16_t*>(q); a.k16 = a.q16 + (k - q); a.v16 = a.q16 + (v - q); a.dctx16 = reinterpret_cast<const uint16_t*>(dctx);
     a.q = a.k = a.v = nullptr; a.dctx = nullptr;
-    need16(((ldq | ldkv | lddq | lddkv | x.d) & 3) == 0 && (attn_mfma_hd(x) == 64 || attn_mfma_hd(x) == 128), "attention backward over bf16-stored operands (precision 2)");
+    need16(x, ((ldq | ldkv | lddq | lddkv | x.d) & 3) == 0 && (attn_mfma_hd(x) == 64 || attn_mfma_hd(x) == 128), "attention backward over bf16-stored operands (precision 2)");
     gt_dispatch("attn_bwd kernel lds%dx%d-bf16 pairs %u", attn_mfma_hd(x), (attn_mfma_hd(x) == 128 || (int)grid.x < GT_ATTN_CS_MAX_PAIRS) ? 4 : 1, grid.x);
     if (attn_mfma_hd(x) == 128) gt_launch(attn_bwd_lds_kernel<128, 4, true>, grid, dim3(512), x.s, a);
     else if ((int)grid.x < GT_ATTN_CS_MAX_PAIRS) gt_launch(attn_bwd_lds_kernel<64, 4, true>, grid, dim3(512), x.s, a);
@@ -944,7 +932,6 @@ static int make_ctx(Ctx& x, const gt_config* cfg, const float* params, float* gr
                     int train, gt_stream_t stream) {
   if (check_cfg(cfg)) return -1;
   if (!params || !ws) return gt_fail("params / ws must not be NULL");
-  g_bf16 = cfg->precision ? 1 : 0;
   x.c = *cfg;
   x.plan = SeqPlan{};
   x.P = param_layout(*cfg);
@@ -955,20 +942,24 @@ static int make_ctx(Ctx& x, const gt_config* cfg, const float* params, float* gr
   x.s = (hipStream_t)stream;
   x.wb = nullptr;
   x.ln = nullptr;
+  x.refused = nullptr;
   return 0;
 }
 static int launch_status(const char* what) {
-  if (g_store_error != nullptr) { const char* m = g_store_error; g_store_error = nullptr; return gt_fail("%s: %s has no bf16-source kernel for this shape (gt_set_operand_shadows(1) keeps the fp32 copies)", what, m); }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return gt_fail("%s: HIP launch error: %s", what, hipGetErrorString(e));
   return 0;
+}
+static int launch_status(const Ctx& x, const char* what) {      // ... of a call with a context: what need16 recorded comes first
+  if (x.refused != nullptr) return gt_fail("%s: %s has no bf16-source kernel for this shape (gt_set_operand_shadows(1) keeps the fp32 copies)", what, x.refused);
+  return launch_status(what);
 }
 
 // ------------------------------------------------------------------------------------ forward
 // InputLayer: Linear -> ReLU -> + pe[t] -> dropout        
 static void input_layer_fwd(const Ctx& x, const float* in, int S, int64_t w, int64_t b, const float* pe, float* a0, float* out,
                             int site) {
-  GemmArgs g = mk_gemm(in, S, x.prm + w, S, out, x.d, x.M, x.d, S);
+  GemmArgs g = mk_gemm(x, in, S, x.prm + w, S, out, x.d, x.M, x.d, S);
   g.bias = x.prm + b; g.aux = a0; g.pe = pe; g.drop = mk_drop(x, site);
   g.C16 = sh_act(x, out); g.ldc16 = x.d;           // (bf16 shadow of x0 where the encoder's operands have them: written by the generic kernel's EPI_RELU_PE epilogue)
   gemm_launch<false, false, EPI_RELU_PE>(g, x.s);
@@ -978,7 +969,7 @@ static void input_layer_fwd(const Ctx& x, const float* in, int S, int64_t w, int
 // (dhid = (dzm W2) * [hact != 0] / (1 - p)).  `ok`: false when a tensor stored in bf16 alone meets a kernel that cannot take it (need16).
 static GemmArgs ffn1_args(const Ctx& x, const LayerP& p, const LayerW& w, const float* xin, int gl, bool* ok) {
   float* ws = x.ws;
-  GemmArgs g = mk_gemm(xin, x.d, x.prm + p.w1, x.d, ws + w.hact, x.F, x.M, x.F, x.d);
+  GemmArgs g = mk_gemm(x, xin, x.d, x.prm + p.w1, x.d, ws + w.hact, x.F, x.M, x.F, x.d);
   g.bias = x.prm + p.b1; g.drop = mk_drop(x, lsite(gl, GT_SITE_FFN));
   g.A16 = sh_act(x, xin); g.B16 = sh_w(x, x.prm + p.w1, false); g.lda16 = g.ldb16 = x.d;
   if (g.A16 && g.B16) { g.C16 = sh_act(x, ws + w.hact); g.ldc16 = x.F; }      // (written by the bf16-source kernel's epilogue only)
@@ -990,7 +981,7 @@ static GemmArgs ffn1_args(const Ctx& x, const LayerP& p, const LayerW& w, const 
 static GemmArgs ffn2d_args(const Ctx& x, const LayerP& p, const LayerW& w, const Tmp& t, const float* dzm, bool* nt, bool* ok) {
   float* ws = x.ws;
   const float* w2t = wT_of(x, x.prm + p.w2);
-  GemmArgs g = w2t ? mk_gemm(dzm, x.d, w2t, x.d, t.dhid, x.F, x.M, x.F, x.d) : mk_gemm(dzm, x.d, x.prm + p.w2, x.F, t.dhid, x.F, x.M, x.F, x.d);
+  GemmArgs g = w2t ? mk_gemm(x, dzm, x.d, w2t, x.d, t.dhid, x.F, x.M, x.F, x.d) : mk_gemm(x, dzm, x.d, x.prm + p.w2, x.F, t.dhid, x.F, x.M, x.F, x.d);
   g.res = ws + w.hact; g.ldres = x.F;
   g.mask_scale = x.drop ? 1.0f / (1.0f - x.c.dropout) : 1.0f;
   *nt = w2t != nullptr; *ok = true;
@@ -1024,7 +1015,7 @@ static int ffn_fwd(const Ctx& x, const LayerP& p, const LayerW& w, const float* 
   float* ws = x.ws;
   bool ok;
   GemmArgs g = ffn1_args(x, p, w, xin, gl, &ok);
-  need16(ok, "FFN activation stored in bf16 alone");
+  need16(x, ok, "FFN activation stored in bf16 alone");
   g.kbits = ffn_kbits(x, p, w, xin, gl);
   if (g.kbits) gemm64_trace("kbits write", g, false, EPI_RELU_DROP);
   gemm_launch<false, false, EPI_RELU_DROP>(g, x.s);
@@ -1054,6 +1045,12 @@ extern "C" int gt_set_seq(int on) { g_seq = on != 0; return 0; }
 // the MFMA rate idle.
 static int g_seq_split = -1;
 extern "C" int gt_set_seq_split(int on) { g_seq_split = on < 0 ? -1 : on != 0; return 0; }
+// a three-state schedule switch (g_seq_split / g_seq_ride / g_seq_quad): its setter's value, else the environment's -- read while the switch
+// is unset and then kept in it -- else -1: by shape
+static int seq_switch(int& sw, const char* env) {
+  if (sw < 0) { const char* e = getenv(env); if (e) sw = e[0] != '0'; }
+  return sw;
+}
 // CUs of the CURRENT device (the caller's torch device; cached per device ordinal: a process may drive several GPUs)
 static int seq_cu_count() {
 #ifdef GT_EMU
@@ -1083,8 +1080,7 @@ static int xchg_cus() {
 }
 static bool seq_split(const gt_config& c) {
   if (c.d_model != 128 && c.d_model != 32 && c.d_model != 64) return false;
-  if (g_seq_split < 0) { const char* e = getenv("GT_SEQ_SPLIT"); if (e) g_seq_split = e[0] != '0'; }
-  if (g_seq_split >= 0) return g_seq_split != 0;
+  if (seq_switch(g_seq_split, "GT_SEQ_SPLIT") >= 0) return g_seq_split != 0;
   // d_model 32 / 64 by shape.  With 16 heads (head_dim 2 / 4) ALWAYS: these kernels alone have the vector-ALU attention, which the zero-padded MFMA
   // form of the whole-sequence kernels loses to at every F (round 6: d32 / H16 / F 64 0.222 -> 0.162 ms, F 128 0.232 -> 0.169; the ClosedHH YAML
   // and the reference CLI's default shape -- d64 / H16 / F 256: 0.370 -> 0.260 -- are the wide end of the same family).  Otherwise only where a
@@ -1107,9 +1103,8 @@ extern "C" int gt_set_seq_ride(int on) { g_seq_ride = on < 0 ? -1 : on != 0; ret
 #endif
 static bool seq_ride(const gt_config& c) {
   if (c.d_model != 128 || c.dim_ff % 16 != 0) return false;     // (seq_plan asks for a SPLIT schedule only)
-  if (g_seq_ride < 0) { const char* e = getenv("GT_SEQ_RIDE"); if (e) g_seq_ride = e[0] != '0'; }
-  const int idle = seq_cu_count() - 2 * c.batch;
-  if (g_seq_ride >= 0) return g_seq_ride != 0 && idle >= 1;
+  const int ride = seq_switch(g_seq_ride, "GT_SEQ_RIDE"), idle = seq_cu_count() - 2 * c.batch;
+  if (ride >= 0) return ride != 0 && idle >= 1;
   return idle >= GT_SEQ_RIDE_MIN_IDLE;
 }
 // QUAD forward (gt_seq.h): four workgroups per sequence -- row halves x column partners that share the FFN through one pair exchange per
@@ -1119,8 +1114,7 @@ static int g_seq_quad = -1;
 extern "C" int gt_set_seq_quad(int on) { g_seq_quad = on < 0 ? -1 : on != 0; return 0; }
 static bool seq_quad(const gt_config& c) {
   if (c.d_model != 128 || c.dim_ff % 32 != 0 || 4 * c.batch > xchg_cus() || (c.flags & GT_CFG_NO_QUAD)) return false;     // (of a SPLIT schedule: seq_plan)
-  if (g_seq_quad < 0) { const char* e = getenv("GT_SEQ_QUAD"); if (e) g_seq_quad = e[0] != '0'; }
-  return g_seq_quad != 0;
+  return seq_switch(g_seq_quad, "GT_SEQ_QUAD") != 0;
 }
 // bound of the pair exchange's polling loop (0 / negative: the compiled default).  A test lowers it to see the time-out path -- error
 // word, skipped update, host recovery -- without waiting seconds.
@@ -1195,7 +1189,7 @@ static SeqArgs mk_seq(const Ctx& x, const float* pe, const float* src, float* hv
   a.dlogits = x.W.dlogits; a.da0 = x.W.dctx; a.ln_part = x.W.ln_part; a.ln_part_stride = x.W.ln_part_stride;
   a.stamps = x.W.stamps;
   a.pack_f = x.W.pack_f; a.pack_b = x.W.pack_b; a.kstride = x.W.pack_stride;
-  a.dctx = x.W.seq_dctx; a.xchg = x.W.seq_xchg; a.xchg_b = x.W.seq_xchg >= 0 ? x.W.seq_xchg + gt_seq_xchg_floats(x.c.batch) : -1; a.fuse_b0 = 0; a.spin_max = g_xchg_spin_max > 0 ? g_xchg_spin_max : GT_XCHG_SPIN_MAX; a.amask = x.W.seq_amask; a.amask_stride = x.W.seq_amask_stride; a.phase = 0;
+  a.dctx = x.W.seq_dctx; a.xchg = x.W.seq_xchg; a.xchg_b = x.W.seq_xchg >= 0 ? x.W.seq_xchg + gt_seq_xchg_floats(x.c.batch) : -1; a.fuse_b0 = 0; a.spin_max = xchg_spin_max(GT_XCHG_SPIN_MAX); a.amask = x.W.seq_amask; a.amask_stride = x.W.seq_amask_stride; a.phase = 0;
   a.loss_y = nullptr; a.loss_penalty = 0.f; a.loss_stats = nullptr; a.loss_part = nullptr; a.loss_ticket = nullptr;
   a.grd = nullptr; a.nseq = 0; a.wg_accumulate = 0; a.ride_last_k = x.M; a.out_early = 0; a.tail_phase = 0; a.tail_ksplit = 1; a.ln_nwg = 0; a.bump = nullptr;
   return a;
@@ -1399,7 +1393,7 @@ static int decoder_fwd(const Ctx& x, const float* pe, const float* tgt_in) {
 // M = B and leading dimensions x 32 over the SAME workspace buffers decoder_fwd uses).  The K/V rows self-attention wrote
 // at steps < t are the KV cache; cross-attention K/V (ws.kvx) is computed once per layer before the loop.
 static void step_linear(const Ctx& x, int B, const float* in, int ldin, const float* W, const float* b, float* out, int ldout, int N, int K) {
-  GemmArgs g = mk_gemm(in, 32 * ldin, W, K, out, 32 * ldout, B, N, K);
+  GemmArgs g = mk_gemm(x, in, 32 * ldin, W, K, out, 32 * ldout, B, N, K);
   g.bias = b;
   gemm_launch<false, false, EPI_STORE>(g, x.s);
 }
@@ -1422,7 +1416,7 @@ static void decoder_step(const Ctx& x, const float* pe, const float* tgt, int t,
   const int d = x.d, F = x.F, L = x.c.n_enc_layers, B = x.c.batch;
   const size_t r = (size_t)t;                       // row offset multiplier: buffer + r * ld
   {   // InputLayerDecoder on tgt row t with pe[t]
-    GemmArgs g = mk_gemm(tgt + r * GT_TGT, 32 * GT_TGT, x.prm + x.P.din_w, GT_TGT, ws + x.W.y0 + r * d, 32 * d, B, d, GT_TGT);
+    GemmArgs g = mk_gemm(x, tgt + r * GT_TGT, 32 * GT_TGT, x.prm + x.P.din_w, GT_TGT, ws + x.W.y0 + r * d, 32 * d, B, d, GT_TGT);
     g.bias = x.prm + x.P.din_b; g.aux = ws + x.W.b0; g.pe = pe + r * d; g.pe_fixed = 1; g.drop = no_drop();
     gemm_launch<false, false, EPI_RELU_PE>(g, x.s);
   }
@@ -1439,7 +1433,7 @@ static void decoder_step(const Ctx& x, const float* pe, const float* tgt, int t,
     step_attention(x, B, ws + w.qx + r * d, d, ws + w.kvx, ws + w.kvx + d, 2 * d, ws + w.ctxx + r * d, 32);
     step_linear_res_ln(x, B, ws + w.ctxx + r * d, d, d, p.xa.out_w, p.xa.out_b, ws + w.x1 + r * d, p.n2w, ws + w.x2 + r * d, ws + w.xhatx, ws + w.rstdx);
     {   // FFN
-      GemmArgs g = mk_gemm(ws + w.x2 + r * d, 32 * d, x.prm + p.w1, d, ws + w.hact + r * F, 32 * F, B, F, d);
+      GemmArgs g = mk_gemm(x, ws + w.x2 + r * d, 32 * d, x.prm + p.w1, d, ws + w.hact + r * F, 32 * F, B, F, d);
       g.bias = x.prm + p.b1; g.drop = no_drop();
       gemm_launch<false, false, EPI_RELU_DROP>(g, x.s);
     }
@@ -1448,7 +1442,7 @@ static void decoder_step(const Ctx& x, const float* pe, const float* tgt, int t,
   }
   gt_launch(ln_fwd_kernel, dim3((B + 3) / 4), dim3(256), x.s, cur + r * d, (const float*)nullptr, no_drop(), x.prm + x.P.decn_w,
             x.prm + x.P.decn_b, ws + x.W.dec_final + r * d, ws + x.W.dec_xhat, ws + x.W.dec_rstd, B, d, 32 * d, 32 * d, 32 * d, (uint16_t*)nullptr, (const uint16_t*)nullptr);
-  GemmArgs g = mk_gemm(ws + x.W.dec_final + r * d, 32 * d, x.prm + x.P.out_w, d, hvo_tmp + r * GT_TGT, 32 * GT_TGT, B, GT_TGT, d);
+  GemmArgs g = mk_gemm(x, ws + x.W.dec_final + r * d, 32 * d, x.prm + x.P.out_w, d, hvo_tmp + r * GT_TGT, 32 * GT_TGT, B, GT_TGT, d);
   g.bias = x.prm + x.P.out_b;
   gemm_launch<false, false, EPI_HEADS>(g, x.s);
 }
@@ -1469,7 +1463,7 @@ static void output_layer_fwd(const Ctx& x, float* hvo_out, FwdStep* st = nullptr
     else               gt_launch(heads_fwd_kernel<0>, dim3(x.M / 16), dim3(256), x.s, fin, (const float*)(x.prm + x.P.out_w), (const float*)(x.prm + x.P.out_b), hvo_out, x.M, x.d, hl);
     return;
   }
-  GemmArgs g = mk_gemm(fin, x.d, x.prm + x.P.out_w, x.d, hvo_out, GT_TGT, x.M, GT_TGT, x.d);
+  GemmArgs g = mk_gemm(x, fin, x.d, x.prm + x.P.out_w, x.d, hvo_out, GT_TGT, x.M, GT_TGT, x.d);
   g.bias = x.prm + x.P.out_b;
   gemm_launch<false, false, EPI_HEADS>(g, x.s);
 }
@@ -1480,12 +1474,12 @@ static int forward_impl(const Ctx& x, const float* pe, const float* xin, const f
   if (x.c.n_dec_layers > 0 && !tgt_in) return gt_fail("gt_forward: encoder-decoder model needs tgt_in");
   if (x.plan.seq) {
     seq_forward(x, pe, xin, hvo_out, st);
-    return launch_status("gt_forward");
+    return launch_status(x, "gt_forward");
   }
   if (encoder_fwd(x, pe, xin)) return -1;
   if (x.c.n_dec_layers > 0 && decoder_fwd(x, pe, tgt_in)) return -1;
   output_layer_fwd(x, hvo_out, st);
-  return launch_status("gt_forward");
+  return launch_status(x, "gt_forward");
 }
 extern "C" int gt_forward(const gt_config* cfg, const float* params, const float* pe, const float* xin, const float* tgt_in,
                           float* hvo_out, float* ws, const gt_step_state* state, int train, gt_stream_t stream) {
@@ -1555,7 +1549,7 @@ static int ffn_bwd(const Ctx& x, const LayerP& p, const LayerW& w, const Tmp& t,
   wgrad(x, dzm, x.d, ws + w.hact, x.F, x.grd + p.w2, x.grd + p.b2, x.d, x.F);
   bool nt, ok;
   GemmArgs g = ffn2d_args(x, p, w, t, dzm, &nt, &ok);
-  need16(ok, "FFN2 dgrad over bf16-only tensors");
+  need16(x, ok, "FFN2 dgrad over bf16-only tensors");
   int gl = 0;                                                  // (the layer's index in the workspace: the keep bits are per layer)
   while (gl + 1 < (int)x.W.layers.size() && x.W.layers[gl].hact != w.hact) ++gl;
   if (dzm == tmp_set(x, gl).dzAm) g.kbits = ffn_kbits(x, p, w, xin, gl);       // (the set the forward's decision looked at -- always, today)
@@ -1580,16 +1574,16 @@ static void self_attn_bwd(const Ctx& x, const LayerP& p, const LayerW& w, const 
 static void input_layer_bwd(const Ctx& x, const LayerP& first, const Tmp& t, const float* dz1, const float* a0, const float* in, int S,
                             int64_t w, int64_t b, int site, float* da_out) {
   if (const float* wt = wT_of(x, x.prm + first.sa.in_w)) {
-    GemmArgs g = mk_gemm(t.dqkv, 3 * x.d, wt, 3 * x.d, da_out, x.d, x.M, x.d, 3 * x.d);
+    GemmArgs g = mk_gemm(x, t.dqkv, 3 * x.d, wt, 3 * x.d, da_out, x.d, x.M, x.d, 3 * x.d);
     g.res = dz1; g.ldres = x.d; g.aux_in = a0; g.drop = mk_drop(x, site);
     gemm_launch<false, false, EPI_ADD_RELUMASK_DROP>(g, x.s);
     wgrad(x, da_out, x.d, in, S, x.grd + w, x.grd + b, x.d, S);
     return;
   }
-  GemmArgs g = mk_gemm(t.dqkv, 3 * x.d, x.prm + first.sa.in_w, x.d, da_out, x.d, x.M, x.d, 3 * x.d);
+  GemmArgs g = mk_gemm(x, t.dqkv, 3 * x.d, x.prm + first.sa.in_w, x.d, da_out, x.d, x.M, x.d, 3 * x.d);
   g.res = dz1; g.ldres = x.d; g.aux_in = a0; g.drop = mk_drop(x, site);
   g.A16 = sh_act(x, t.dqkv); g.B16 = sh_w(x, x.prm + first.sa.in_w, true); g.lda16 = g.ldb16 = 3 * x.d;
-  if (only16(x, t.dqkv)) need16(g.A16 && g.B16 && gemm32h_ok(g, EPI_ADD_RELUMASK_DROP), "InputLayer dgrad of a bf16-only tensor");
+  if (only16(x, t.dqkv)) need16(x, g.A16 && g.B16 && gemm32h_ok(g, EPI_ADD_RELUMASK_DROP), "InputLayer dgrad of a bf16-only tensor");
   gemm_launch<false, true, EPI_ADD_RELUMASK_DROP>(g, x.s);
   wgrad(x, da_out, x.d, in, S, x.grd + w, x.grd + b, x.d, S);
 }
@@ -1634,29 +1628,122 @@ static void heads_bwd(const Ctx& x, const float* hvo, const float* d_hvo) {
   gt_prof_tag("heads_bwd", 0, 12.0 * x.M * GT_TGT);
   gt_launch(heads_bwd_kernel, dim3((x.M * GT_TGT + 255) / 256), dim3(256), x.s, d_hvo, hvo, x.ws + x.W.dlogits, x.M * GT_TGT);
 }
+// The one-kernel-per-op backward.  phase: backward_impl's, of a two-bucket cut (else 0); cut_layer: first encoder layer of the upper bucket
+// (grad_split).  Bucket 0 is the output layer with the decoder half (encoder-decoder) or with the encoder layers from cut_layer up; bucket 1
+// the encoder layers below.  Weight gradients and LayerNorm partials queue up on x.wb / x.ln: the caller's finish() sends them.
+static int op_backward(const Ctx& x, const float* xin, const float* tgt_in, const float* hvo, const float* d_hvo, int phase, int cut_layer) {
+  const float* params = x.prm; float* grads = x.grd; float* ws = x.ws;
+  const int L = x.c.n_enc_layers, Ld = x.c.n_dec_layers, d = x.d, M = x.M;
+  const WLayout& W = x.W; const PLayout& P = x.P;
+  if (phase != 2) {                                 // bucket 0 opens with the output layer, the final norm and the decoder half
+    // OutputLayer: dlogits, dW_out, then d(final) fused with the final norm's backward
+    heads_bwd(x, hvo, d_hvo);
+    const float* fin = ws + (Ld > 0 ? W.dec_final : W.memory);
+    wgrad(x, ws + W.dlogits, GT_TGT, fin, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);
+    // the final norm's backward and the top layer's closing norm's backward sit back to back: when the output-layer dgrad is
+    // an ordinary tiled GEMM (row_fused false) both run as ONE row pass (ln_bwd2); with fused row tiles the first one is the
+    // GEMM's epilogue and the second its own pass.  Either way (dzA, dzAm) of the top layer come out.
+    const float* xh = ws + (Ld > 0 ? W.dec_xhat : W.enc_xhat);
+    const float* rs = ws + (Ld > 0 ? W.dec_rstd : W.enc_rstd);
+    const int64_t gfin = Ld > 0 ? P.decn_w : P.encn_w, gtop = Ld > 0 ? P.dec[Ld - 1].n3w : P.enc[L - 1].n2w;
+    const int top = L + Ld - 1;                     // global index of the last layer
+    const LayerW& wtop = W.layers[top];
+    const Tmp ttop = tmp_set(x, top);
+    if (!row_fused(x)) {
+      dgrad_store(x, ws + W.dlogits, GT_TGT, params + P.out_w, d, ws + W.dctx, d, GT_TGT, 0);
+      ln_bwd2(x, ws + W.dctx, xh, rs, gfin, ws + W.dctx, ws + wtop.xhat2, ws + wtop.rstd2, gtop, ttop.dzA, ttop.dzAm, lsite(top, GT_SITE_DROPF));
+    } else {
+      if (dgrad_lnbwd(x, ws + W.dlogits, GT_TGT, params + P.out_w, GT_TGT, nullptr, xh, rs, gfin, ws + W.dctx, nullptr, 0))
+        return gt_fail("d_model %d unsupported by the row-LayerNorm kernels", d);
+      ln_bwd(x, ws + W.dctx, nullptr, ws + wtop.xhat2, ws + wtop.rstd2, gtop, ttop.dzA, ttop.dzAm, lsite(top, GT_SITE_DROPF));
+    }
+    if (Ld > 0) {
+      // (ws.dmem, the memory gradient, is the SUM of the decoder layers' cross-attention k / v dgrads: the first one processed stores, the
+      //  others add.  Round 5: it used to be zeroed by a hipMemsetAsync here -- a memset NODE inside the step's captured graph -- and the
+      //  encoder-decoder step then went non-finite intermittently when replays were separated by a host synchronisation (C3, and already
+      //  the L1+1 model: 2 of 3 processes; never eagerly, never without the decoder): the only memset node of the fused step is gone.)
+      for (int l = Ld - 1; l >= 0; --l) {
+        const LayerP& p = P.dec[l];
+        const int gl = L + l;
+        const LayerW& w = W.layers[gl];
+        const Tmp t = tmp_set(x, gl);
+        const float* yin = (l == 0) ? ws + W.y0 : ws + W.layers[gl - 1].xout;
+        // FFN (norm3's backward was done by the producer of dzA) -> dz2 = LNbwd_norm2(...) in (dzB, dzBm)
+        if (ffn_bwd(x, p, w, t, ws + w.x2, t.dzA, t.dzAm, ws + w.xhatx, ws + w.rstdx, p.n2w, t.dzB, t.dzBm, lsite(gl, GT_SITE_DROP2))) return -1;
+        // cross attention: q from the decoder stream, k/v from the encoder memory
+        wgrad(x, t.dzBm, d, ws + w.ctxx, d, grads + p.xa.out_w, grads + p.xa.out_b, d, d);
+        dgrad_store(x, t.dzBm, d, params + p.xa.out_w, d, ws + W.dctx, d, d, 0);
+        float* dqx = t.dqkvx; float* dkvx = t.dqkvx + (int64_t)M * d;            // dq (M,d) then dkv (M,2d), both dense
+        attention_bwd(x, ws + w.qx, d, ws + w.kvx, ws + w.kvx + d, 2 * d, ws + w.Px, ws + W.dctx, dqx, d, dkvx, dkvx + d, 2 * d,
+                      lsite(gl, GT_SITE_XATTN));
+        wgrad(x, dqx, d, ws + w.x1, d, grads + p.xa.in_w, grads + p.xa.in_b, d, d);
+        wgrad(x, dkvx, 2 * d, ws + W.memory, d, grads + p.xa.in_w + (int64_t)d * d, grads + p.xa.in_b + d, 2 * d, d);
+        dgrad_store(x, dkvx, 2 * d, params + p.xa.in_w + (int64_t)d * d, d, ws + W.dmem, d, 2 * d, l == Ld - 1 ? 0 : 1);
+        // dz1 = LNbwd_norm1(dqx Wq + dz2) -> (dzC, dzCm) masked for the self-attn out-proj
+        if (dgrad_lnbwd(x, dqx, d, params + p.xa.in_w, d, t.dzB, ws + w.xhat1, ws + w.rstd1, p.n1w, t.dzC, t.dzCm, lsite(gl, GT_SITE_DROP1)))
+          return -1;
+        self_attn_bwd(x, p, w, t, yin, t.dzCm, gl);
+        if (l > 0) {
+          const LayerW& wp = W.layers[gl - 1];
+          const Tmp tn = tmp_set(x, gl - 1);
+          if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzC, ws + wp.xhat2, ws + wp.rstd2, P.dec[l - 1].n3w, tn.dzA,
+                          tn.dzAm, lsite(gl - 1, GT_SITE_DROPF)))
+            return -1;
+        } else {
+          input_layer_bwd(x, p, t, t.dzC, ws + W.b0, tgt_in, GT_TGT, P.din_w, P.din_b, GT_SITE_PE_DEC, ws + W.da0_dec);
+        }
+      }
+    }
+  }
+  if (Ld > 0) {
+    if (phase == 1) return 0;                       // decoder half (bucket 0) done; ws.dmem holds the memory gradient
+    // encoder final norm backward (input: accumulated dmem) and the last encoder layer's closing norm: one row pass
+    const LayerW& w = W.layers[L - 1];
+    const Tmp t = tmp_set(x, L - 1);
+    ln_bwd2(x, ws + W.dmem, ws + W.enc_xhat, ws + W.enc_rstd, P.encn_w, ws + W.dctx, ws + w.xhat2, ws + w.rstd2, P.enc[L - 1].n2w,
+            t.dzA, t.dzAm, lsite(L - 1, GT_SITE_DROPF));
+  }
+  // encoder layers hi .. lo: all of them, or (encoder-only, two buckets) those from cut_layer up, then those below.  The layers from the
+  // cut up are final when the first half ends; (dzA, dzAm) of layer cut_layer - 1 are what it hands to the second
+  const int hi = (Ld == 0 && phase == 2) ? cut_layer - 1 : L - 1, lo = (Ld == 0 && phase == 1) ? cut_layer : 0;
+  for (int l = hi; l >= lo; --l) {
+    const LayerP& p = P.enc[l];
+    const LayerW& w = W.layers[l];
+    const Tmp t = tmp_set(x, l);
+    const float* lin = (l == 0) ? ws + W.x0 : ws + W.layers[l - 1].xout;
+    if (ffn_bwd(x, p, w, t, ws + w.x1, t.dzA, t.dzAm, ws + w.xhat1, ws + w.rstd1, p.n1w, t.dzB, t.dzBm, lsite(l, GT_SITE_DROP1))) return -1;
+    self_attn_bwd(x, p, w, t, lin, t.dzBm, l);
+    if (l > 0) {
+      const LayerW& wp = W.layers[l - 1];
+      const Tmp tn = tmp_set(x, l - 1);
+      if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzB, ws + wp.xhat2, ws + wp.rstd2, P.enc[l - 1].n2w, tn.dzA, tn.dzAm,
+                      lsite(l - 1, GT_SITE_DROPF)))
+        return -1;
+    } else {
+      input_layer_bwd(x, p, t, t.dzB, ws + W.a0, xin, x.c.src_dim, P.in_w, P.in_b, GT_SITE_PE_ENC, ws + W.dctx);
+    }
+  }
+  return 0;
+}
 // phase 0: the whole backward; 1: only until bucket 0 of grad_split() is final; 2: the rest (after a phase-1 call on the
 // same workspace -- the hand-over temporaries live there).  b0_done: the caller's forward ran backward phase 0 already (FwdStep).
 // x: the caller's context with its plan, by value -- the queues of this call hang off the copy.
 static int backward_impl(Ctx x, const float* xin, const float* tgt_in, const float* hvo, const float* d_hvo, int accumulate, int phase,
                          gt_step_state* bump_state, bool grads_zero, bool b0_done) {
-  const gt_config* cfg = &x.c;
-  const float* params = x.prm; float* grads = x.grd; float* ws = x.ws;
-  if (!grads || !xin) return gt_fail("gt_backward: grads / x must not be NULL");
-  const int L = cfg->n_enc_layers, Ld = cfg->n_dec_layers, d = x.d, M = x.M;
-  if (Ld > 0 && !tgt_in) return gt_fail("gt_backward: encoder-decoder model needs tgt_in");
-  const WLayout& W = x.W;
-  const PLayout& P = x.P;
-  if (!accumulate) (void)hipMemsetAsync(grads, 0, (size_t)P.total * sizeof(float), x.s);
+  if (!x.grd || !xin) return gt_fail("gt_backward: grads / x must not be NULL");
+  const int d = x.d;
+  if (x.c.n_dec_layers > 0 && !tgt_in) return gt_fail("gt_backward: encoder-decoder model needs tgt_in");
+  const WLayout& W = x.W; const PLayout& P = x.P;
+  if (!accumulate) (void)hipMemsetAsync(x.grd, 0, (size_t)P.total * sizeof(float), x.s);
   // Weight gradients are queued and leave as ONE grouped dispatch per tile class at the end of the (phase of) backward
   // (finish()); every layer keeps its own temporaries (W.set) for that.
   WgradBatch wbatch;
   x.wb = &wbatch;
   LnJobs lnjobs;
   lnjobs.n = 0; lnjobs.N = d; lnjobs.bump = nullptr;
-  lnjobs.err = xchg_err(x.W, ws);
+  lnjobs.err = xchg_err(x.W, x.ws);
   x.ln = &lnjobs;
-  const int top = L + Ld - 1;                       // global index of the last layer
-  const GradSplit cut = grad_split(*cfg, P, x.plan);
+  const GradSplit cut = grad_split(x.c, P, x.plan);
   if (cut.nb < 2) {                                 // nothing to split: phase 1 does everything, phase 2 nothing
     if (phase == 2) return 0;
     phase = 0;
@@ -1670,7 +1757,7 @@ static int backward_impl(Ctx x, const float* xin, const float* tgt_in, const flo
       gt_dispatch("ln_param_reduce jobs %d d %d", lnjobs.n, d);
       gt_launch(ln_param_reduce_kernel, dim3((2 * d + 63) / 64, lnjobs.n), dim3(1024), x.s, lnjobs);
     }
-    return launch_status("gt_backward");
+    return launch_status(x, "gt_backward");
   };
 
   if (x.plan.seq) {
@@ -1679,106 +1766,10 @@ static int backward_impl(Ctx x, const float* xin, const float* tgt_in, const flo
     // with riders, have left in the phases and the tail launch
     heads_bwd(x, hvo, d_hvo);
     if (seq_backward(x, xin, accumulate, phase, cut.split_layer, bump_state, grads_zero, b0_done)) return -1;
-    return x.plan.ride ? launch_status("gt_backward") : finish();
+    return x.plan.ride ? launch_status(x, "gt_backward") : finish();
   }
-  bool top_norm_done = false;                       // the top layer's closing norm was folded into the final norm's pass
-  if (phase != 2) {
-  // OutputLayer: dlogits, dW_out, then d(final) fused with the final norm's backward
-  heads_bwd(x, hvo, d_hvo);
-  const float* fin = ws + (Ld > 0 ? W.dec_final : W.memory);
-  wgrad(x, ws + W.dlogits, GT_TGT, fin, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);
-  // the final norm's backward and the top layer's closing norm's backward sit back to back: when the output-layer dgrad is
-  // an ordinary tiled GEMM (row_fused false) both run as ONE row pass (ln_bwd2); with fused row tiles the first one is the
-  // GEMM's epilogue and the second its own pass
-  {
-    const float* xh = ws + (Ld > 0 ? W.dec_xhat : W.enc_xhat);
-    const float* rs = ws + (Ld > 0 ? W.dec_rstd : W.enc_rstd);
-    const int64_t gfin = Ld > 0 ? P.decn_w : P.encn_w;
-    if (!row_fused(x)) {
-      const LayerW& w = W.layers[top];
-      Tmp t = tmp_set(x, top);
-      dgrad_store(x, ws + W.dlogits, GT_TGT, params + P.out_w, d, ws + W.dctx, d, GT_TGT, 0);
-      ln_bwd2(x, ws + W.dctx, xh, rs, gfin, ws + W.dctx, ws + w.xhat2, ws + w.rstd2, Ld > 0 ? P.dec[Ld - 1].n3w : P.enc[L - 1].n2w,
-              t.dzA, t.dzAm, lsite(top, GT_SITE_DROPF));
-      top_norm_done = true;
-    } else if (dgrad_lnbwd(x, ws + W.dlogits, GT_TGT, params + P.out_w, GT_TGT, nullptr, xh, rs, gfin, ws + W.dctx, nullptr, 0)) {
-      return gt_fail("d_model %d unsupported by the row-LayerNorm kernels", d);
-    }
-  }
-  // ws.dctx now holds the grad w.r.t. the last layer's output (the input of the final norm) unless top_norm_done
-  if (Ld > 0) {
-    // (ws.dmem, the memory gradient, is the SUM of the decoder layers' cross-attention k / v dgrads: the first one processed stores, the
-    //  others add.  Round 5: it used to be zeroed by a hipMemsetAsync here -- a memset NODE inside the step's captured graph -- and the
-    //  encoder-decoder step then went non-finite intermittently when replays were separated by a host synchronisation (C3, and already
-    //  the L1+1 model: 2 of 3 processes; never eagerly, never without the decoder): the only memset node of the fused step is gone.)
-    if (!top_norm_done) {
-      const LayerW& w = W.layers[top];
-      Tmp t = tmp_set(x, top);
-      ln_bwd(x, ws + W.dctx, nullptr, ws + w.xhat2, ws + w.rstd2, P.dec[Ld - 1].n3w, t.dzA, t.dzAm, lsite(top, GT_SITE_DROPF));
-    }
-    for (int l = Ld - 1; l >= 0; --l) {
-      const LayerP& p = P.dec[l];
-      const int gl = L + l;
-      const LayerW& w = W.layers[gl];
-      const Tmp t = tmp_set(x, gl);
-      const float* yin = (l == 0) ? ws + W.y0 : ws + W.layers[gl - 1].xout;
-      // FFN (norm3's backward was done by the producer of dzA) -> dz2 = LNbwd_norm2(...) in (dzB, dzBm)
-      if (ffn_bwd(x, p, w, t, ws + w.x2, t.dzA, t.dzAm, ws + w.xhatx, ws + w.rstdx, p.n2w, t.dzB, t.dzBm, lsite(gl, GT_SITE_DROP2))) return -1;
-      // cross attention: q from the decoder stream, k/v from the encoder memory
-      wgrad(x, t.dzBm, d, ws + w.ctxx, d, grads + p.xa.out_w, grads + p.xa.out_b, d, d);
-      dgrad_store(x, t.dzBm, d, params + p.xa.out_w, d, ws + W.dctx, d, d, 0);
-      float* dqx = t.dqkvx; float* dkvx = t.dqkvx + (int64_t)M * d;            // dq (M,d) then dkv (M,2d), both dense
-      attention_bwd(x, ws + w.qx, d, ws + w.kvx, ws + w.kvx + d, 2 * d, ws + w.Px, ws + W.dctx, dqx, d, dkvx, dkvx + d, 2 * d,
-                    lsite(gl, GT_SITE_XATTN));
-      wgrad(x, dqx, d, ws + w.x1, d, grads + p.xa.in_w, grads + p.xa.in_b, d, d);
-      wgrad(x, dkvx, 2 * d, ws + W.memory, d, grads + p.xa.in_w + (int64_t)d * d, grads + p.xa.in_b + d, 2 * d, d);
-      dgrad_store(x, dkvx, 2 * d, params + p.xa.in_w + (int64_t)d * d, d, ws + W.dmem, d, 2 * d, l == Ld - 1 ? 0 : 1);
-      // dz1 = LNbwd_norm1(dqx Wq + dz2) -> (dzC, dzCm) masked for the self-attn out-proj
-      if (dgrad_lnbwd(x, dqx, d, params + p.xa.in_w, d, t.dzB, ws + w.xhat1, ws + w.rstd1, p.n1w, t.dzC, t.dzCm, lsite(gl, GT_SITE_DROP1)))
-        return -1;
-      self_attn_bwd(x, p, w, t, yin, t.dzCm, gl);
-      if (l > 0) {
-        const LayerW& wp = W.layers[gl - 1];
-        const Tmp tn = tmp_set(x, gl - 1);
-        if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzC, ws + wp.xhat2, ws + wp.rstd2, P.dec[l - 1].n3w, tn.dzA,
-                        tn.dzAm, lsite(gl - 1, GT_SITE_DROPF)))
-          return -1;
-      } else {
-        input_layer_bwd(x, p, t, t.dzC, ws + W.b0, tgt_in, GT_TGT, P.din_w, P.din_b, GT_SITE_PE_DEC, ws + W.da0_dec);
-      }
-    }
-  }
-  }                                                 // phase != 2
-  if (Ld > 0) {
-    if (phase == 1) return finish();                // decoder half (bucket 0) done; ws.dmem holds the memory gradient
-    // encoder final norm backward (input: accumulated dmem) and the last encoder layer's closing norm: one row pass
-    const LayerW& w = W.layers[L - 1];
-    const Tmp t = tmp_set(x, L - 1);
-    ln_bwd2(x, ws + W.dmem, ws + W.enc_xhat, ws + W.enc_rstd, P.encn_w, ws + W.dctx, ws + w.xhat2, ws + w.rstd2, P.enc[L - 1].n2w,
-            t.dzA, t.dzAm, lsite(L - 1, GT_SITE_DROPF));
-  } else if (phase != 2 && !top_norm_done) {
-    const LayerW& w = W.layers[L - 1];
-    const Tmp t = tmp_set(x, L - 1);
-    ln_bwd(x, ws + W.dctx, nullptr, ws + w.xhat2, ws + w.rstd2, P.enc[L - 1].n2w, t.dzA, t.dzAm, lsite(L - 1, GT_SITE_DROPF));
-  }
-  for (int l = (phase == 2 && Ld == 0) ? cut.split_layer - 1 : L - 1; l >= 0; --l) {
-    const LayerP& p = P.enc[l];
-    const LayerW& w = W.layers[l];
-    const Tmp t = tmp_set(x, l);
-    const float* lin = (l == 0) ? ws + W.x0 : ws + W.layers[l - 1].xout;
-    if (ffn_bwd(x, p, w, t, ws + w.x1, t.dzA, t.dzAm, ws + w.xhat1, ws + w.rstd1, p.n1w, t.dzB, t.dzBm, lsite(l, GT_SITE_DROP1))) return -1;
-    self_attn_bwd(x, p, w, t, lin, t.dzBm, l);
-    if (l > 0) {
-      const LayerW& wp = W.layers[l - 1];
-      const Tmp tn = tmp_set(x, l - 1);
-      if (dgrad_lnbwd(x, t.dqkv, 3 * d, params + p.sa.in_w, 3 * d, t.dzB, ws + wp.xhat2, ws + wp.rstd2, P.enc[l - 1].n2w, tn.dzA, tn.dzAm,
-                      lsite(l - 1, GT_SITE_DROPF)))
-        return -1;
-      if (phase == 1 && Ld == 0 && l == cut.split_layer) return finish();     // layers >= the cut are final; (dzA, dzAm) of l-1 handed over
-    } else {
-      input_layer_bwd(x, p, t, t.dzB, ws + W.a0, xin, cfg->src_dim, P.in_w, P.in_b, GT_SITE_PE_ENC, ws + W.dctx);
-    }
-  }
+  // ---- one kernel per op
+  if (op_backward(x, xin, tgt_in, hvo, d_hvo, phase, cut.split_layer)) return -1;
   return finish();
 }
 
@@ -1798,7 +1789,7 @@ extern "C" int gt_debug_seq_wg_phase(const gt_config* cfg, const float* params, 
   const int tiles = per_layer + (phase >= 2 ? win : 0);
   gt_prof_tag("seq_tail", 0.0, 0.0);
   gt_seq_launch_tail(a, (unsigned)(tiles * ksplit), x.s);
-  return launch_status("gt_debug_seq_wg_phase");
+  return launch_status(x, "gt_debug_seq_wg_phase");
 }
 
 extern "C" int gt_backward(const gt_config* cfg, const float* params, float* grads, const float* xin, const float* tgt_in,
@@ -1870,7 +1861,7 @@ extern "C" int gt_optimizer_step_ws(const gt_config* cfg, int algo, float* param
   if (seq_update_pack(x, algo, params, m, v, nullptr, nullptr, nullptr, state, 0)) return -1;
   gt_launch(step_inc_kernel, dim3(1), dim3(64), (hipStream_t)stream, state, xchg_err(x.W, ws),
             (const float*)(grads + P.total - 1));
-  return launch_status("gt_optimizer_step_ws");
+  return launch_status(x, "gt_optimizer_step_ws");
 }
 // ------------------------------------------------------------------------------------ fused train step
 // Where a fused step's loss comes from.  gt_train_step (by_opts false): the hit penalty -- the loss may ride in the forward's last launch,
@@ -1927,7 +1918,7 @@ static int train_step_impl(const char* who, const gt_config* cfg, int algo, floa
   // the update that ends a whole step: the last launch of backward advanced the step counters already
   if (!x.plan.seq) return optimizer_step_impl(algo, params, grads, m, v, x.P.total, state, 1, stream, 1, xchg_err(x.W, ws), 1) ? -1 : 0;
   if (seq_update_pack(x, algo, params, m, v, pe, xin, hvo_out, state, 1)) return -1;
-  return launch_status(who);
+  return launch_status(x, who);
 }
 extern "C" int gt_train_step(const gt_config* cfg, int algo, float* params, float* grads, float* m, float* v, const float* pe,
                              const float* xin, const float* y, float hit_loss_penalty, float* hvo_out, float* stats,
@@ -2132,7 +2123,7 @@ static int predict_impl(const gt_config* cfg, const float* params, const float* 
     else
       gt_launch(predict_head_kernel, dim3((M * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)hvo_out, hvo_out, (float*)nullptr,
                 thres, use_thres, -1, B, seed, idx0);
-    return launch_status(vs ? "gt_predict_voices" : "gt_predict");
+    return launch_status(x, vs ? "gt_predict_voices" : "gt_predict");
   }
   if (!tgt_scratch) return gt_fail("gt_predict: encoder-decoder model needs tgt_scratch");
   // greedy decode: tgt row 0 = zeros, row t+1 = thresholded step t.  The encoder memory and every layer's cross-attention
@@ -2155,7 +2146,7 @@ static int predict_impl(const gt_config* cfg, const float* params, const float* 
       gt_launch(predict_head_kernel, dim3((B * GT_TGT + 255) / 256), dim3(256), x.s, (const float*)tmp, hvo_out, tgt_scratch, thres,
                 use_thres, t, B, seed, idx0);
   }
-  return launch_status(vs ? "gt_predict_voices" : "gt_predict");
+  return launch_status(x, vs ? "gt_predict_voices" : "gt_predict");
 }
 
 // ---- per-voice controls: thresholds, temperature, hit caps, velocity / offset mask (include/groove_hip.h, gt_voice_sampling) ----

@@ -985,54 +985,58 @@ static inline bool gemm64_range(long t64, bool h) {
   static const long lo = gt_env_long("GT_T64R_MIN", GT_T64R_MIN), hi = gt_env_long("GT_T64R_MAX", GT_T64R_MAX), hih = gt_env_long("GT_T64H_MAX", GT_T64H_MAX);
   return t64 >= lo && t64 <= (h ? hih : hi);
 }
-// will gemm_launch put this problem on a kernel with the shared store epilogue of gt_gemm32.h (the only ones that write a bf16 output, C16,
-// and can leave the fp32 one out)?  Mirrors the rules below.
-template <bool BKM, int EPI>
-static inline bool gemm_on_big_kernel(const GemmArgs& g) {
-  const long b64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64), b128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-  if (g.bf16 && gemm64_range(b64, true) && gemm64h_ok(g, EPI)) return true;
-  if (!(g.bf16 && g.A16 && g.B16) && gemm64_range(b64, false) && gemm64_ok(g, EPI)) return true;
-  if (g.bf16 && b128 >= GT_T128H_MIN && gemm32h_ok(g, EPI)) return true;
-  return b128 >= GT_T128_BIG_MIN && gemm32_ok(g, EPI, BKM);
+// Which kernel class takes a problem with a standard (non-row) epilogue, and its k_chunk: the ONE statement of the tile rules (gemm_launch
+// switches on it, gemm_on_big_kernel asks it).  The ring tiles of gt_gemm32.h / gt_gemm64.h first -- interior problems of the store-class
+// epilogues; H: both operands as bf16 shadows, their *_ok say so -- then the generic kernel's tile by how many workgroups the problem yields.
+enum GemmKind { GK_RING64H, GK_RING64, GK_RING128H, GK_RING128, GK_T128, GK_T64, GK_T32 };
+struct GemmPick { GemmKind kind; int k_chunk; };
+static inline GemmPick gemm_pick(const GemmArgs& g, bool akm, bool bkm, int epi) {
+  const long t64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64), t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
+  const int kc64 = (g.K + 63) / 64 * 64;
+  if (!akm && (epi == EPI_STORE || epi == EPI_RELU_DROP || epi == EPI_MASK_NZ || epi == EPI_ADD_RELUMASK_DROP)) {
+    if (g.bf16 && gemm64_range(t64, true) && gemm64h_ok(g, epi)) return {GK_RING64H, kc64};
+    if (!(g.bf16 && g.A16 && g.B16) && gemm64_range(t64, false) && gemm64_ok(g, epi)) return {GK_RING64, kc64};
+    if (g.bf16 && t128 >= GT_T128H_MIN && gemm32h_ok(g, epi)) return {GK_RING128H, kc64};
+    if (t128 >= GT_T128_BIG_MIN && gemm32_ok(g, epi, bkm)) return {GK_RING128, kc64};
+  }
+  // 128x128 tiles once they still fill the chip twice over: a 64x64x64 slab needs ~38 GB/s of L2->LDS staging per
+  // workgroup to keep its MFMAs fed, two resident workgroups ask a CU for more than it delivers (46-70 GB/s measured);
+  // 128x128x32 slabs need half of that per flop.  bf16 operands: 32 keeps two 128x128 workgroups per CU resident (49 KB of LDS each); the
+  // smaller tiles take slabs of 64 k (two MFMA k-steps per barrier)
+  if (t128 >= GT_T128_MIN) return {GK_T128, (g.K + 31) / 32 * 32};
+  if (t64 >= GT_T64_MIN) return {GK_T64, g.bf16 ? kc64 : (g.K + GT_T64_BK - 1) / GT_T64_BK * GT_T64_BK};
+  return {GK_T32, g.bf16 ? kc64 : (g.K + GT_T32_BK - 1) / GT_T32_BK * GT_T32_BK};
 }
-// standard (non-row) epilogues: pick the tile by how many workgroups the problem yields
+// will gemm_launch put this problem on a kernel with the shared store epilogue of gt_gemm32.h (the only ones that write a bf16 output, C16,
+// and can leave the fp32 one out)?
+template <bool BKM, int EPI>
+static inline bool gemm_on_big_kernel(const GemmArgs& g) { return gemm_pick(g, false, BKM, EPI).kind <= GK_RING128; }
+// standard (non-row) epilogues
 template <bool AKM, bool BKM, int EPI>
 static inline void gemm_launch(GemmArgs g, hipStream_t s) {
-  g.k_chunk = (g.K + 63) / 64 * 64;
   if (EPI == EPI_ATOMIC) {
-    const int splitk = wgrad_split(g, 1024);
+    const int splitk = wgrad_split(g, 1024);          // (sets g.k_chunk)
     if (g.bf16) gemm_launch_cfg<2, 2, 1, 1, 64, AKM, BKM, EPI, 1>(g, splitk, s);
     else        gemm_launch_cfg<2, 2, 1, 1, 64, AKM, BKM, EPI>(g, splitk, s);
     return;
   }
+  const GemmPick pk = gemm_pick(g, AKM, BKM, EPI);
+  g.k_chunk = pk.k_chunk;
   if constexpr (!AKM && (EPI == EPI_STORE || EPI == EPI_RELU_DROP || EPI == EPI_MASK_NZ || EPI == EPI_ADD_RELUMASK_DROP)) {
-    const long b64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-    if (g.bf16 && gemm64_range(b64, true) && gemm64h_ok(g, EPI)) { gemm64h_launch<BKM, EPI>(g, s); return; }       // both operands as bf16 shadows
-    if (!(g.bf16 && g.A16 && g.B16) && gemm64_range(b64, false) && gemm64_ok(g, EPI)) { gemm64_launch<BKM, EPI>(g, s); return; }
-    const long b128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    if (g.bf16 && b128 >= GT_T128H_MIN && gemm32h_ok(g, EPI)) { gemm32h_launch<BKM, EPI>(g, s); return; }     // both operands as bf16 shadows
-    if (g.bf16 && b128 >= GT_T128_BIG_MIN && gemm32_ok(g, EPI, BKM)) { gemm32_launch<BKM, EPI>(g, s); return; }
+    if (pk.kind == GK_RING64H)  { gemm64h_launch<BKM, EPI>(g, s); return; }       // both operands as bf16 shadows
+    if (pk.kind == GK_RING64)   { gemm64_launch<BKM, EPI>(g, s); return; }
+    if (pk.kind == GK_RING128H) { gemm32h_launch<BKM, EPI>(g, s); return; }       // both operands as bf16 shadows
+    if (pk.kind == GK_RING128)  { gemm32_launch<BKM, EPI>(g, s); return; }
   }
   if (g.bf16) {
-    // bf16 operands: the same three tile classes; slabs of 64 k (two MFMA k-steps per barrier) except on the 128x128 tile,
-    // where 32 keeps two workgroups per CU resident (49 KB of LDS each)
-    const long u64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64), u128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-    if (u128 >= GT_T128_MIN) { g.k_chunk = (g.K + 31) / 32 * 32; gemm_launch_cfg<2, 2, 4, 4, 32, AKM, BKM, EPI, 1>(g, 1, s); }
-    else if (u64 >= GT_T64_MIN) { g.k_chunk = (g.K + 63) / 64 * 64; gemm_launch_cfg<2, 2, 2, 2, 64, AKM, BKM, EPI, 1>(g, 1, s); }
-    else { g.k_chunk = (g.K + 63) / 64 * 64; gemm_launch_cfg<2, 2, 1, 1, 64, AKM, BKM, EPI, 1>(g, 1, s); }
+    if (pk.kind == GK_T128)     gemm_launch_cfg<2, 2, 4, 4, 32, AKM, BKM, EPI, 1>(g, 1, s);
+    else if (pk.kind == GK_T64) gemm_launch_cfg<2, 2, 2, 2, 64, AKM, BKM, EPI, 1>(g, 1, s);
+    else                        gemm_launch_cfg<2, 2, 1, 1, 64, AKM, BKM, EPI, 1>(g, 1, s);
     return;
   }
-  const long t64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-  const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-  if constexpr (!AKM && (EPI == EPI_STORE || EPI == EPI_RELU_DROP || EPI == EPI_MASK_NZ || EPI == EPI_ADD_RELUMASK_DROP)) {
-    if (t128 >= GT_T128_BIG_MIN && gemm32_ok(g, EPI, BKM)) { gemm32_launch<BKM, EPI>(g, s); return; }
-  }
-  // 128x128 tiles once they still fill the chip twice over: a 64x64x64 slab needs ~38 GB/s of L2->LDS staging per
-  // workgroup to keep its MFMAs fed, two resident workgroups ask a CU for more than it delivers (46-70 GB/s measured);
-  // 128x128x32 slabs need half of that per flop
-  if (t128 >= GT_T128_MIN) { g.k_chunk = (g.K + 31) / 32 * 32; gemm_launch_cfg<2, 2, 4, 4, 32, AKM, BKM, EPI>(g, 1, s); }
-  else if (t64 >= GT_T64_MIN) { g.k_chunk = (g.K + GT_T64_BK - 1) / GT_T64_BK * GT_T64_BK; gemm_launch_cfg<2, 2, 2, 2, GT_T64_BK, AKM, BKM, EPI>(g, 1, s); }
-  else { g.k_chunk = (g.K + GT_T32_BK - 1) / GT_T32_BK * GT_T32_BK; gemm_launch_cfg<2, 2, 1, 1, GT_T32_BK, AKM, BKM, EPI>(g, 1, s); }
+  if (pk.kind == GK_T128)     gemm_launch_cfg<2, 2, 4, 4, 32, AKM, BKM, EPI>(g, 1, s);
+  else if (pk.kind == GK_T64) gemm_launch_cfg<2, 2, 2, 2, GT_T64_BK, AKM, BKM, EPI>(g, 1, s);
+  else                        gemm_launch_cfg<2, 2, 1, 1, GT_T32_BK, AKM, BKM, EPI>(g, 1, s);
 }
 
 // row epilogues: BN = padded d_model.  16-row tiles while the problem is small (M = 2048 gives only 128 of them); 32-row
@@ -1047,22 +1051,27 @@ static inline void gemm_launch(GemmArgs g, hipStream_t s) {
 static inline int gemm_row_bm(int M, int N) { return M < GT_ROW_BM32_MIN ? 16 : (N > 128 && M >= GT_ROW_BM64_MIN) ? 64 : 32; }
 static inline bool gemm32row_ok(const GemmArgs& g, bool bkm);
 template <bool BKM, int EPI>
-static inline void gemm32row_launch(const GemmArgs& g, hipStream_t s);
+static inline void gemm32row_launch(const GemmArgs& g, int rows, hipStream_t s);
 #ifndef GT_ROW32_BM64_MIN_WG
 #define GT_ROW32_BM64_MIN_WG 256   /* d_model 256: 64-row tiles from this many workgroups of them, 32-row tiles below */
 #endif
 #ifndef GT_ROW32_MIN_M
 #define GT_ROW32_MIN_M 8192     /* the ring-body row tiles (gt_gemm32.h) from this many tokens: 256 / 128 workgroups of 32 / 64 rows */
 #endif
-// rows per workgroup of the row-fused launch of g (the LayerNorm-backward partials table has one row per workgroup)
-static inline int gemm_row_rows(const GemmArgs& g, bool bkm) {
-  if (g.M >= GT_ROW32_MIN_M && gemm32row_ok(g, bkm)) return (g.N == 512 || g.M / 64 >= GT_ROW32_BM64_MIN_WG) ? 64 : 32;
-  return gemm_row_bm(g.M, g.N);
+// Which kernel takes a row-fused launch, and its rows per workgroup: gemm_launch_row launches it, gemm_row_rows sizes the LayerNorm-backward
+// partials table (one row per workgroup) from it.  ring: the ring-body row tiles of gt_gemm32.h -- 64 rows once they fill the chip (one
+// workgroup per CU at d_model 512: 132 KB of LDS), 32 below that at 256 -- else the generic kernel's.
+struct RowPick { bool ring; int rows; };
+static inline RowPick gemm_row_pick(const GemmArgs& g, bool akm, bool bkm) {
+  if (!akm && g.M >= GT_ROW32_MIN_M && gemm32row_ok(g, bkm)) return {true, (g.N == 512 || g.M / 64 >= GT_ROW32_BM64_MIN_WG) ? 64 : 32};
+  return {false, gemm_row_bm(g.M, g.N)};
 }
+static inline int gemm_row_rows(const GemmArgs& g, bool bkm) { return gemm_row_pick(g, false, bkm).rows; }
 template <bool AKM, bool BKM, int EPI>
 static inline int gemm_launch_row(GemmArgs g, hipStream_t s) {
-  if constexpr (!AKM) { if (g.M >= GT_ROW32_MIN_M && gemm32row_ok(g, BKM)) { gemm32row_launch<BKM, EPI>(g, s); return 0; } }
-  const int bm = gemm_row_bm(g.M, g.N);
+  const RowPick pk = gemm_row_pick(g, AKM, BKM);
+  if constexpr (!AKM) { if (pk.ring) { gemm32row_launch<BKM, EPI>(g, pk.rows, s); return 0; } }
+  const int bm = pk.rows;
   const bool small = bm == 16;
   if (g.N <= 32) {
     g.k_chunk = (g.K + 63) / 64 * 64;
@@ -1073,7 +1082,6 @@ static inline int gemm_launch_row(GemmArgs g, hipStream_t s) {
     if (small) gemm_launch_cfg<1, 4, 1, 1, 64, AKM, BKM, EPI>(g, 1, s);
     else       gemm_launch_cfg<2, 2, 1, 2, 64, AKM, BKM, EPI>(g, 1, s);
   } else if (g.N <= 128) {
-    g.k_chunk = (g.K + 63) / 64 * 64;
     g.k_chunk = (g.K + 127) / 128 * 128;
     if (small) gemm_launch_cfg<1, 4, 1, 2, 128, AKM, BKM, EPI>(g, 1, s);
     else       gemm_launch_cfg<2, 2, 1, 4, 64, AKM, BKM, EPI>(g, 1, s);

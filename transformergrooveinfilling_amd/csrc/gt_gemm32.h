@@ -591,12 +591,11 @@ static inline bool gemm32row_ok(const GemmArgs& g, bool bkm) {
   return true;
 }
 template <bool BKM, int EPI>
-static inline void gemm32row_launch(const GemmArgs& g, hipStream_t s) {
+static inline void gemm32row_launch(const GemmArgs& g, int rows, hipStream_t s) {      // rows: gemm_row_pick's
   gt_prof_tag(gemm_label<BKM, EPI>(), 2.0 * g.M * g.N * g.K, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + 3.0 * g.M * g.N));
-  // 64-row tiles once they fill the chip (one workgroup per CU at d_model 512: 132 KB of LDS); 32-row tiles below that at 256
-  gemm_ring_dispatch("gemm32row", (g.N == 512 || g.M / 64 >= GT_ROW32_BM64_MIN_WG) ? 64 : 32, g.N, g, BKM, EPI, "fp32");
+  gemm_ring_dispatch("gemm32row", rows, g.N, g, BKM, EPI, "fp32");
   if (g.N == 512) gt_launch(gemm32row_kernel<512, 2, BKM, EPI>, dim3(g.M / 64), dim3(512), s, g);
-  else if (g.M / 64 >= GT_ROW32_BM64_MIN_WG) gt_launch(gemm32row_kernel<256, 2, BKM, EPI>, dim3(g.M / 64), dim3(512), s, g);
+  else if (rows == 64) gt_launch(gemm32row_kernel<256, 2, BKM, EPI>, dim3(g.M / 64), dim3(512), s, g);
   else gt_launch(gemm32row_kernel<256, 1, BKM, EPI>, dim3(g.M / 32), dim3(512), s, g);
 }
 
