@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 import harness
+import regimes
 from harness import Runner
 from oracle import numpy_groove as ng
 
@@ -19,7 +20,9 @@ OUT_TOL, GRAD_TOL = 2e-5, 2e-4
 # the last check's largest error / bar ratios ("out": outputs against OUT_TOL, "grad": the worst gradient tensor against GRAD_TOL, "update":
 # check_update's ratio, "bf16_op": the worst per-operation ratio of check_ops_bf16, "bf16_e2e": the end-to-end sanity bound,
 # "probe": the worst tensor of the worst probe of check_grad_probes against GRAD_TOL, "accumulate": check_accumulate's worst element) -- figures for
-# reports (profiles/dispatch_edges.txt, profiles/grad_probes.txt); nothing asserts on them
+# reports (profiles/dispatch_edges.txt, profiles/grad_probes.txt); nothing asserts on them.  A regime run (check_step(regime=...)) records
+# "noise": the worst quantity's device error / max(fp32 oracle's error, floor) -- the ratio regimes.NOISE_FACTOR bounds --, "noise_at": that
+# quantity's name, "noise_rows": every quantity's (name, err, noise, scale, ratio), "regime": regimes.figures of the oracle's cache
 FIGURES = {}
 
 
@@ -82,8 +85,11 @@ def _check_forward_and_loss(r, hvo, hvo_ref, C, y, penalty, check_ws):
     return dpred
 
 
-def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=True, flags=0):
-    """forward + loss + backward (+ saved activations) against the fp64 numpy oracle."""
+def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=True, flags=0, regime=None):
+    """forward + loss + backward (+ saved activations) against the fp64 numpy oracle.  regime: a name of tests/regimes.py -- the same step
+    away from initialisation, under check_step_regime's bars."""
+    if regime is not None:
+        return check_step_regime(backend, cfg, B, regime, p, penalty, seed, seq, flags)
     cfg = dict(cfg, dropout=p)
     P = ng.init_params(cfg, seed=seed, perturb=0.05)
     x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
@@ -107,6 +113,79 @@ def check_step(backend, cfg, B, p=0.0, penalty=0.47, seed=3, check_ws=True, seq=
         err = float(np.abs(G[k] - Gr[k]).max() / max(np.abs(Gr[k]).max(), 1e-5))
         FIGURES["grad"] = max(FIGURES.get("grad", 0.0), err / GRAD_TOL)
         assert err < GRAD_TOL, (k, err)
+    return r, P, G, Gr
+
+
+# ---- the same step away from initialisation (tests/regimes.py) ------------------------------------------------------------------------------
+def check_step_regime(backend, cfg, B, regime, p=0.0, penalty=0.47, seed=3, seq=True, flags=0):
+    """check_step with the parameters moved by regimes.REGIMES[regime].  The fp32 oracle runs beside the fp64 one, and every compared
+    quantity -- outputs, every encoder layer's saved P and hact, x0, memory, d loss / d hvo, each gradient tensor -- meets two bars:
+    (1) check_step's fixed bar, with one correction: the hit-logit columns of the output are compared relative to max(1, max |h_ref|) (on
+        logits of +-48 ... +-91 stock fp32 numpy is 2.9e-5 ... 4.1e-5 off fp64 absolutely, 3e-7 ... 6e-7 relative to the largest); the v and
+        o columns stay absolute.  The saved P's fixed 1e-5 gives way to (2) (shift: the fp32 oracle's own P is 3.5e-6 ... 8.9e-6 off);
+    (2) error <= regimes.NOISE_FACTOR x max(the fp32 oracle's error on that quantity, 4 ulp of its scale), asserted for all quantities
+        together at the end (regimes.Noise.check), after the fixed bars.
+    The regime's own condition is asserted on the fp64 cache first.  Records FIGURES (see above); returns (r, P, G, Gr)."""
+    cfg = dict(cfg, dropout=p)
+    P = regimes.apply(ng.init_params(cfg, seed=seed, perturb=0.05), cfg, regime, seed)
+    x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
+    Ld = cfg.get("num_decoder_layers", 0)
+    tgt = shift_right(y) if Ld else None
+    rng = (1234, 99, 7)
+    orng = rng if p > 0 else None
+    (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=orng, dtype=np.float64)
+    FIGURES.clear()
+    FIGURES["regime"] = regimes.assert_condition(regime, C, h)
+    (h32, v32, o32), C32 = ng.forward(P, cfg, x, tgt=tgt, rng=orng, dtype=np.float32)
+    noise = regimes.Noise()
+    FIGURES["noise_rows"] = noise.rows
+
+    def done():
+        name, _, _, _, ratio = noise.worst()
+        FIGURES["noise"], FIGURES["noise_at"] = ratio, name
+
+    try:
+        r = Runner(cfg, B, backend, rng=rng, seq=seq, flags=flags)
+        r.set_params(P)
+        hvo = r.forward(x, tgt, train=p > 0)
+        hs = max(1.0, float(np.abs(h).max()))
+        e = noise.add("out.h", hvo[..., :9], h32, h, scale=hs)
+        FIGURES["out"] = e / OUT_TOL
+        assert e < OUT_TOL, "forward hit logits: max-abs %g of max |h| %g" % (e * hs, hs)
+        vo, vo32 = np.concatenate([v, o], -1), np.concatenate([v32, o32], -1)
+        e = noise.add("out.vo", hvo[..., 9:], vo32, vo, scale=hs) * hs
+        FIGURES["out"] = max(FIGURES["out"], e / OUT_TOL)
+        assert e < OUT_TOL, "forward v / o max-abs %g" % e
+        saved = [("x0", 0, C["enc"][0]["x_in"], C32["enc"][0]["x_in"])]
+        for l, (c, c32) in enumerate(zip(C["enc"], C32["enc"])):
+            saved += [("P", l, c["attn"]["P"], c32["attn"]["P"]), ("hact", l, c["hact"], c32["hact"])]
+        saved.append(("memory", 0, C["memory"], C32["memory"]))
+        for name, l, ref, ref32 in saved:
+            e = noise.add("%s[%d]" % (name, l), r.ws_get(name, l), ref32.reshape(-1), ref.reshape(-1))
+            assert name == "P" or e < 1e-5, (name, l, e)
+        stats, d_hvo = r.loss(y, penalty)
+        rstats, dpred = ng.calculate_loss((h, v, o), y.astype(np.float64), penalty)
+        for i in (0, 3, 4, 5):
+            assert abs(stats[i] - rstats[i]) < 1e-5 * max(1.0, abs(rstats[i])), (i, stats[i], rstats[i])
+        near = int((np.abs(h) < 1e-4).sum())
+        assert abs(stats[1] - rstats[1]) <= (near + 0.01) / h.size + 1e-6, (stats[1], rstats[1], near)
+        _, dpred32 = ng.calculate_loss((h32, v32, o32), y.astype(np.float32), np.float32(penalty))
+        e = noise.add("d_hvo", d_hvo, np.concatenate(dpred32, -1), np.concatenate(dpred, -1))
+        assert e < 1e-5, ("d_hvo", e)
+        G = r.backward(train=p > 0)
+        adopted = adopt_device_kinks(r, C, cfg)
+        assert adopted <= kink_bound(r, cfg), adopted
+        regimes.same_kinks(C32, C)
+        Gr = ng.backward(P, cfg, C, dpred, dtype=np.float64)
+        G32 = ng.backward(P, cfg, C32, dpred32, dtype=np.float32)
+        assert set(G) == set(Gr)
+        for k in Gr:
+            err = noise.add(k, G[k], G32[k], Gr[k], scale=max(float(np.abs(Gr[k]).max()), 1e-5))
+            FIGURES["grad"] = max(FIGURES.get("grad", 0.0), err / GRAD_TOL)
+            assert err < GRAD_TOL, (k, err)
+    finally:
+        done()
+    noise.check()
     return r, P, G, Gr
 
 
@@ -871,23 +950,22 @@ def check_decisions_current(r, C):
     return len(todo)
 
 
-def check_train_step(backend, cfg, B, p, algo=0, seq=True, flags=0):
+def check_train_step(backend, cfg, B, p, algo=0, seq=True, flags=0, regime=None, lr=0.05, steps=3):
     """gt_train_step == forward+loss+backward+update with the oracle's masks, three steps; later steps use step+1.  Each step is checked
     twice: teacher-forced (the fp64 oracle's step from the device's own parameters and moments before it, per element: check_update) and
-    along the free-running fp64 trajectory from the initial parameters.  Both oracle caches adopt the device's ReLU decisions at the kink."""
+    along the free-running fp64 trajectory from the initial parameters.  Both oracle caches adopt the device's ReLU decisions at the kink.
+    regime: the initial parameters moved by tests/regimes.py, the regime's condition asserted on the first step's oracle cache."""
     cfg = dict(cfg, dropout=p)
-    P = ng.init_params(cfg, seed=9, perturb=0.05)
+    P = regimes.apply(ng.init_params(cfg, seed=9, perturb=0.05), cfg, regime, 9)
     x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=4)
     Ld = cfg.get("num_decoder_layers", 0)
     tgt = shift_right(y) if Ld else None
-    lr = 0.05
     r = Runner(cfg, B, backend, rng=(77, 5, 0), lr=lr, seq=seq, flags=flags)
     r.set_params(P)
     cur = {k: v.astype(np.float64) for k, v in P.items()}
     folded = r.lib.cdll.gt_step_launches(ctypes.byref(r.c)) > 0     # sequence-resident path: the update writes the next step's weight packs
     bound = kink_bound(r, cfg)
     f64 = lambda D: {k: np.asarray(v, np.float64) for k, v in D.items()}
-    steps = 3
     FIGURES.clear()
     for step in range(steps):
         before = r.unflatten(r.params.numpy())
@@ -901,6 +979,8 @@ def check_train_step(backend, cfg, B, p, algo=0, seq=True, flags=0):
         # teacher-forced: the oracle's step from where the device started it
         (h, v, o), Ct = ng.forward(f64(before), cfg, x, tgt=tgt, rng=rng, dtype=np.float64)
         tstats, dpt = ng.calculate_loss((h, v, o), y.astype(np.float64), 0.38)
+        if regime is not None and step == 0:
+            FIGURES["regime"] = regimes.assert_condition(regime, Ct, h)
         assert abs(stats[0] - tstats[0]) < 2e-5 * max(1, abs(tstats[0])), (step, "teacher-forced loss", stats[0], tstats[0])
         assert check_decisions_current(r, Ct) >= len(Ct["enc"]) + 1
         adopted = adopt_device_kinks(r, Ct, cfg)
@@ -947,16 +1027,23 @@ def check_train_step(backend, cfg, B, p, algo=0, seq=True, flags=0):
         assert "seq_xchg" in str(e) or "absent" in str(e) or "unknown" in str(e), e
 
 
-def check_predict(backend, cfg, B, use_thres=True, thres=0.5, out_tol=OUT_TOL, margin_tol=1e-4, pd_seed=None):
+def check_predict(backend, cfg, B, use_thres=True, thres=0.5, out_tol=OUT_TOL, margin_tol=1e-4, pd_seed=None, regime=None, seed=21):
     """out_tol / margin_tol: the fp32 bars by default; the bf16 operand path passes its own (hits compared where the decision
-    margin exceeds what a bf16 rounding flip can move a probability by)."""
+    margin exceeds what a bf16 rounding flip can move a probability by).
+    regime: the parameters (of seed `seed`) moved by tests/regimes.py; the regime's condition is asserted on the oracle's cache of the
+    decoded sequence, and the encoder-decoder comparison must reach 90 % of all decode steps."""
     cfg = dict(cfg, dropout=0.3)      # predict is eval mode: dropout must be ignored
-    P = ng.init_params(cfg, seed=21, perturb=0.05)
+    P = regimes.apply(ng.init_params(cfg, seed=seed, perturb=0.05), cfg, regime, seed)
     x, _ = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=8)
     r = Runner(cfg, B, backend)
     r.set_params(P)
     hvo = r.predict(x, thres=thres, use_thres=use_thres, pd_seed=pd_seed)         # pd_seed: the reference's use_pd (sampled hits)
     (h, v, o), margin = ng.predict(P, cfg, x, use_thres=use_thres, thres=thres, dtype=np.float64, pd_seed=pd_seed)
+    if regime is not None:            # (greedy decoding is causal: the teacher-forced forward over the decoded sequence is its last step's)
+        tgt = shift_right(np.concatenate([h, v, o], -1)) if cfg.get("num_decoder_layers", 0) else None
+        (hl, _, _), C = ng.forward(P, dict(cfg, dropout=0.0), x, tgt=tgt, dtype=np.float64)
+        FIGURES.clear()
+        FIGURES["regime"] = regimes.assert_condition(regime, C, hl)
     if pd_seed is not None:
         frac = float(hvo[..., :9].mean())
         assert 0.02 < frac < 0.98, frac                                            # really sampled: neither all hits nor none
@@ -976,6 +1063,9 @@ def check_predict(backend, cfg, B, use_thres=True, thres=0.5, out_tol=OUT_TOL, m
                 if t_end:
                     assert np.abs(hvo[b, :t_end, 9:] - vo[b, :t_end]).max() < out_tol, (b, t_end)
             assert compared > 0, "no comparable decode step: every sequence has a low-margin decision at step 0"
+            if regime is not None:
+                FIGURES["decode_steps"] = compared / (32.0 * B)
+                assert compared >= 0.9 * 32 * B, "only %d of %d decode steps lie before a low-margin decision" % (compared, 32 * B)
             return
         assert np.array_equal(hvo[..., :9][sure], h[sure])                      # bit-exact hit mask
         assert set(np.unique(hvo[..., :9])) <= {0.0, 1.0}

@@ -131,6 +131,43 @@ def test_kernel_against_fp64_restatement(B, variant, wrt_logits):
     check_kernel(emu_lib(), "cpu", B, variant, wrt_logits)
 
 
+def check_kernel_saturated(lib, device, B, wrt_logits):
+    """gt_loss_ex where trained heads live: hit logits drawn as N(0, 20) (|h| up to 80: exp(|h|) overflows fp32 beyond 88, sigmoid(-|h|) and
+    the focal factor q^gamma underflow towards 0), pos_weight set and focal_gamma = 2 -- DESIGN "loss options" claims that nothing overflows
+    for finite logits.  Every output finite; statistics, voice statistics and d_out under check_kernel's fixed bars AND within
+    regimes.NOISE_FACTOR x the error of the same restatement evaluated in fp32 (4-ulp floor): tests/regimes.py."""
+    import regimes
+    kw = dict(penalty_h=0.47, pos_weight=PW, focal_gamma=2.0)
+    opts, lo = ref.opts_f32(**kw), _lib.make_loss_opts(**kw)
+    hvo_np, y_np = ref.make_inputs(B, seed=B)
+    hvo_np[:, :9] = (np.random.default_rng(B + 1000).standard_normal((B * 32, 9)) * 20.0).astype(np.float32)
+    assert (np.abs(hvo_np[:, :9]) > 10).mean() > 0.5 and np.abs(hvo_np[:, :9]).max() > 50
+    want = ref.restate(hvo_np, y_np, opts, wrt_logits)
+    want32 = ref.restate(hvo_np, y_np, opts, wrt_logits, dtype=torch.float32)
+    call = LossCall(lib, device, B)
+    stats, voice, d_out = call(torch.from_numpy(hvo_np).to(call.device), torch.from_numpy(y_np).to(call.device), lo, wrt_logits)
+    assert np.isfinite(d_out).all() and np.isfinite(stats).all() and np.isfinite(voice).all()
+    noise = regimes.Noise()
+    for i in (0, 3, 4, 5):
+        e = noise.add("stats[%d]" % i, stats[i], want32[0][i], want[0][i], scale=max(1.0, abs(want[0][i])))
+        assert e <= STAT_TOL, (i, stats[i], want[0][i])
+    for k in range(27):
+        e = noise.add("voice[%d]" % k, voice[k], want32[1][k], want[1][k], scale=max(1.0, abs(want[1][k])))
+        assert e <= STAT_TOL, (k, voice[k], want[1][k])
+    e = noise.add("d_out", d_out, want32[2], want[2])
+    print("saturated B %d wrt_logits %d: d_out rel_err %.3g, worst noise ratio %.2f at %s" % (B, wrt_logits, e, noise.worst()[4], noise.worst()[0]))
+    assert e < GRAD_TOL, e
+    noise.check()
+    counts = ref.hit_counts(hvo_np, y_np)
+    assert np.array_equal(np.rint(voice[27:].astype(np.float64) * B * 32), counts)
+    return noise
+
+
+@pytest.mark.parametrize("wrt_logits", [0, 1])
+def test_kernel_against_fp64_restatement_saturated(wrt_logits):
+    check_kernel_saturated(emu_lib(), "cpu", 3, wrt_logits)
+
+
 def check_defaults_match_gt_loss(lib, device, B):
     """every option neutral, penalty_vo = penalty_h: d_out bit for bit gt_loss's, stats within the bar"""
     call = LossCall(lib, device, B)

@@ -34,6 +34,11 @@ def test_kernel_against_fp64_restatement_hip(B, variant, wrt_logits):
     T.check_kernel(_lib.get_lib(), "cuda", B, variant, wrt_logits)
 
 
+@pytest.mark.parametrize("wrt_logits", [0, 1])
+def test_kernel_against_fp64_restatement_saturated_hip(wrt_logits):
+    T.check_kernel_saturated(_lib.get_lib(), "cuda", 3, wrt_logits)
+
+
 @pytest.mark.parametrize("B", T.BATCHES)
 def test_defaults_are_gt_loss_hip(B):
     T.check_defaults_match_gt_loss(_lib.get_lib(), "cuda", B)
