@@ -94,6 +94,7 @@ class Runner:
         self.state = self.Buf(np.frombuffer(bytes(st), dtype=np.uint8).copy())
         self.stream = ctypes.c_void_p(0)
         self.params = None
+        self.d_hvo_from = None                       # whose self.d_hvo is: "loss" (gt_loss wrote it: self.y, self.loss_penalty) or "caller" (backward(d_hvo))
 
     # ---- parameters -------------------------------------------------------------------------
     def flatten(self, P):
@@ -121,12 +122,15 @@ class Runner:
         self.y = self.Buf(np.asarray(y, np.float32).reshape(self.M, 27))
         self.lib.call("gt_loss", ctypes.byref(self.c), self.hvo.ptr, self.y.ptr, ctypes.c_float(penalty), self.stats.ptr,
                       self.d_hvo.ptr if want_grad else None, self.stream)
+        if want_grad:
+            self.d_hvo_from, self.loss_penalty = "loss", penalty
         return self.stats.numpy().copy(), self.d_hvo.numpy().reshape(self.B, 32, 27).copy()
 
     def backward(self, d_hvo=None, train=False, accumulate=0):
         """accumulate: gt_backward's argument -- 1 adds onto what self.grads holds (the nn.Module path), 0 overwrites it"""
         if d_hvo is not None:
             self.d_hvo = self.Buf(np.asarray(d_hvo, np.float32).reshape(self.M, 27))
+            self.d_hvo_from = "caller"
         self.lib.call("gt_backward", ctypes.byref(self.c), self.params.ptr, self.grads.ptr, self.x.ptr,
                       self.tgt_in.ptr if self.tgt_in else None, self.hvo.ptr, self.d_hvo.ptr, self.ws.ptr, self.state.ptr,
                       int(train), int(accumulate), self.stream)

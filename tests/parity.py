@@ -24,6 +24,10 @@ OUT_TOL, GRAD_TOL = 2e-5, 2e-4
 # "noise": the worst quantity's device error / max(fp32 oracle's error, floor) -- the ratio regimes.NOISE_FACTOR bounds --, "noise_at": that
 # quantity's name, "noise_rows": every quantity's (name, err, noise, scale, ratio), "regime": regimes.figures of the oracle's cache
 FIGURES = {}
+# what goes with FIGURES["bf16_op"] and is no number: "op_at" (the comparison with the worst ratio), "ops" (bar class -> (worst ratio, its comparison)),
+# "widened" ((comparison, class bar, the np.float32 restatement's error, the device's error), all relative to the tensor's largest entry, for every
+# bar _close's np.float32 rule widened), "ledger" (the last walk's Ledger).  Cleared with FIGURES["bf16_op"]
+BF16_FIGURES = {}
 
 
 def shift_right(y):
@@ -370,6 +374,7 @@ def _check_grad_probes(backend, cfg, B, p, probes, seq, flags, penalty, seed, pr
             ratio = probe_compare(G, Gr, place)
         else:
             FIGURES.pop("bf16_op", None)
+            BF16_FIGURES.clear()
             try:
                 check_ops_bf16(r, P, cfg, x, tgt, rng, p, G, forward_checks=(i == 0))
             except AssertionError as e:
@@ -451,6 +456,9 @@ def check_accumulate(backend, cfg, B, p, seq=True, flags=0, penalty=0.47, seed=3
 #     exactly the points the device rounds them (oracle.numpy_groove.round_bf16), and compared with the device's output of
 #     that one operation.  Nothing propagates, so the bar is the fp32 one: 5e-5 of the tensor's largest entry (fp32
 #     accumulation over up to 16384 terms), LayerNorm / activation epilogues included.  This is the parity proof.
+#     The other operations -- attention cores, LayerNorm passes, dropout masks on gradients, d loss / d logits -- are restated the same way
+#     under the bar of their class (_bar_class), and the walk asserts its own CLOSURE (Ledger): no gradient tensor left uncompared, no device
+#     tensor read as an input that an earlier operation of the walk did not compare.
 # (2) END TO END against the bf16-operand oracle (oracle "bf16 operand mode").  Here differences DO propagate: an operand the
 #     device computed 6e-8 (relative) away from the oracle's value rounds to the neighbouring bf16 now and then, that moves
 #     its row by ~1e-3, and from there on the rest of the sequence rounds differently too -- two legitimate realisations of
@@ -464,10 +472,23 @@ def _rms(a):
     return float(np.sqrt((np.asarray(a, np.float64) ** 2).mean()))
 
 
-def _close(dev, ref, what, tol=BF16_OP_TOL, where=None, stored16=False, rms_tol=None):
+def _bar_class(tol, rms_tol):
+    """the name BF16_FIGURES["ops"] files a comparison under: the walk's bar classes"""
+    if rms_tol is not None:
+        return "behind a hidden bf16 rounding (max %.3g, rms %.3g)" % (tol, rms_tol)
+    return {BF16_OP_TOL: "matmul-like, fp32 accumulation (5e-5)", 2e-5: "probabilities / LayerNorm forward (2e-5)",
+            1e-4: "dgrad + LayerNorm backward, LayerNorm parameter gradients (1e-4)", 1e-6: "dropout mask on a gradient (1e-6)"}.get(tol, "%g" % tol)
+
+
+def _close(dev, ref, what, tol=BF16_OP_TOL, where=None, stored16=False, rms_tol=None, ref32=None):
     """stored16: the device keeps this tensor in bf16 alone (operand-only tensors, gt_set_operand_shadows level 2) -- what is read back
     is the RNE rounding of the value the bar applies to, so each element may additionally be off by half a bf16 ulp of itself (2^-9;
-    2^-8 allowed: the fp32 value may sit a hair on the other side of a rounding boundary)."""
+    2^-8 allowed: the fp32 value may sit a hair on the other side of a rounding boundary).
+    ref32: () -> the same restatement evaluated in np.float32 from the same inputs.  Consulted only when the comparison misses its class
+    bar: if that fp32 restatement is itself more than 1 / 8 of the bar away from the fp64 one, the bar of this one comparison becomes
+    regimes.NOISE_FACTOR x the restatement's own error (recorded in BF16_FIGURES["widened"]); otherwise the miss stands.
+    Records FIGURES["bf16_op"] (the worst error / bar ratio) and, in BF16_FIGURES, "op_at" (that comparison's name) and "ops" (bar class ->
+    (worst ratio, its comparison's name))."""
     dev, ref = np.asarray(dev, np.float64).reshape(ref.shape), np.asarray(ref, np.float64)
     err = np.abs(dev - ref)
     if stored16:
@@ -475,16 +496,97 @@ def _close(dev, ref, what, tol=BF16_OP_TOL, where=None, stored16=False, rms_tol=
     if where is not None:
         err = err * where
     scale = max(float(np.abs(ref).max()), 1e-6)
-    FIGURES["bf16_op"] = max(FIGURES.get("bf16_op", 0.0), float(err.max() / (tol * scale)))
-    assert err.max() <= tol * scale, "%s: max |err| %.3g of max |ref| %.3g (ratio %.3g)" % (what, err.max(), scale, err.max() / scale)
+    bar = tol * scale
+    if not err.max() <= bar and ref32 is not None:
+        noise = float(np.abs(np.asarray(ref32(), np.float64).reshape(ref.shape) - ref).max())
+        if noise > bar / 8:
+            BF16_FIGURES.setdefault("widened", []).append((what, bar / scale, noise / scale, float(err.max()) / scale))
+            bar = regimes.NOISE_FACTOR * noise
+            import warnings
+            warnings.warn("%s: class bar %.3g widened to %.3g (the np.float32 restatement is %.3g off; device %.3g)"
+                          % (what, tol, bar / scale, noise / scale, float(err.max()) / scale))
+    ratio = float(err.max() / bar)
+    if ratio >= FIGURES.get("bf16_op", 0.0):
+        FIGURES["bf16_op"], BF16_FIGURES["op_at"] = ratio, what
+    rows = BF16_FIGURES.setdefault("ops", {})
+    cls = _bar_class(tol, rms_tol)
+    if ratio >= rows.get(cls, (0.0, None))[0]:
+        rows[cls] = (ratio, what)
+    assert err.max() <= bar, "%s: max |err| %.3g of max |ref| %.3g (ratio %.3g, bar %.3g)" % (what, err.max(), scale, err.max() / scale, bar / scale)
     if rms_tol is not None:      # behind a HIDDEN bf16 rounding single elements may sit one ulp off (max bar 2^-8-ish); on average nothing may
         assert _rms(err) <= rms_tol * scale, "%s: rms err %.3g of max |ref| %.3g (ratio %.3g)" % (what, _rms(err), scale, _rms(err) / scale)
+
+
+class Ledger:
+    """What one walk of check_ops_bf16 has proved, kept so that the walk can assert its own closure.  A tensor is named "<region>[<layer>]"
+    (workspace regions, as gt_ws_find names them), "hvo" or "d_hvo".
+    compared: tensor -> the first comparison that covered it.  consumed: tensor -> why the walk may read it as a teacher-forcing input
+    ("compared: ..." by an EARLIER operation of the same walk, or the probe's d_hvo the test itself supplied), None if nothing admits it.
+    cover: gradient key -> which of its rows some comparison covered (the packed in-proj tensors are compared slice by slice).
+    The true inputs of the step -- x, tgt, the parameters, y -- come from the caller, not from the device, and are not recorded.
+    forward_checks=False (check_grad_probes' probes after the first: another backward from the SAME forward): the forward's comparisons are
+    not repeated; the ledger enters them as "by the first walk of this forward" and the closure assertion runs all the same."""
+
+    def __init__(self, G, forward_checks, d_hvo_supplied):
+        self.compared, self.consumed = {}, {}
+        self.forward_by_first_walk = not forward_checks
+        self.d_hvo_supplied = d_hvo_supplied
+        self.cover = None if G is None else {k: np.zeros(np.shape(v)[0], bool) for k, v in G.items()}
+
+    @staticmethod
+    def key(name, layer=None):
+        return name if layer is None else "%s[%d]" % (name, layer)
+
+    def did_compare(self, key, what):
+        if isinstance(key, tuple):                   # ("grad", the gradient's key, which of its rows)
+            self.cover[key[1]][key[2]] = True
+        else:
+            self.compared.setdefault(key, what)
+
+    def consume(self, key):
+        if key in self.consumed:
+            return
+        if key in self.compared:
+            self.consumed[key] = "compared: " + self.compared[key]
+        elif key == "d_hvo" and self.d_hvo_supplied:
+            self.consumed[key] = "supplied by the test (probe)"
+        else:
+            self.consumed[key] = None
+
+    def verdict(self):
+        """(gradient keys -- or row ranges of them -- no comparison covered, consumed tensors nothing admits), both in the walk's order"""
+        grads = []
+        for k, c in (self.cover or {}).items():
+            if not c.any():
+                grads.append(k)
+            elif not c.all():
+                miss = np.flatnonzero(~c)
+                grads.append("%s rows %d..%d" % (k, miss[0], miss[-1]))
+        return grads, [k for k, how in self.consumed.items() if how is None]
+
+    def assert_closed(self):
+        grads, tensors = self.verdict()
+        assert not grads and not tensors, ("the per-operation walk is not closed -- gradient tensors no operation compared: %s; device tensors consumed "
+                                           "as inputs that no earlier operation compared: %s" % (grads or "none", tensors or "none"))
+
+
+def _ledger_compare(led, key, dev, ref, what, **kw):
+    """One comparison of the walk: dev() reads the device's tensor, ref is the fp64 restatement -- an array, or dt -> array for the operations
+    that can also be restated in np.float32 (_close's ref32).  Only a comparison that held enters the ledger."""
+    if callable(ref):
+        _close(dev(), ref(np.float64), what, ref32=lambda: ref(np.float32), **kw)
+    else:
+        _close(dev(), ref, what, **kw)
+    led.did_compare(key, what)
 
 
 def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     """Teacher-forced per-operation parity of the bf16 path (bar (1) above).  r: Runner after forward (and, with G = the device's
     gradients, after loss + backward).  forward_checks=False: only the backward half is compared (a second backward from the same forward:
-    check_grad_probes) -- the forward half is still walked for its operands.  Returns the number of operations checked."""
+    check_grad_probes) -- the forward half is still walked for its operands.
+    The walk keeps a Ledger and asserts its own closure at the end: every device tensor it read as an input was the compared output of an
+    earlier operation (or the probe's d_hvo), and, with G, every gradient tensor was compared, the packed ones slice by slice.  The Ledger
+    stays in BF16_FIGURES["ledger"].  Returns the number of comparisons."""
     rb = ng.round_bf16
     f64 = lambda a: np.asarray(a, np.float64)
     P = {k: f64(v) for k, v in P.items()}
@@ -493,14 +595,47 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     M = r.M
     pe = np.tile(f64(ng.positional_encoding(d)), (M // 32, 1))
     scale = 1.0 / (1.0 - float(np.float32(p))) if p > 0 else 1.0
+    led = Ledger(G, forward_checks, getattr(r, "d_hvo_from", None) == "caller")
+    BF16_FIGURES["ledger"] = led
+    if G is not None:
+        G = {k: f64(v) for k, v in G.items()}
+    n = 0
 
     def mask(site, n, shape=None):
         m = ng.keep_mask(rng, site, n, p) if p > 0 else None
         return 1.0 if m is None else (m if shape is None else m.reshape(shape))
 
     def ws(name, layer=0, cols=None):
+        """a device tensor CONSUMED as a teacher-forcing input (the ledger wants it compared before)"""
+        led.consume(Ledger.key(name, layer))
         a = f64(r.ws_get(name, layer))
         return a.reshape(M, -1) if cols is None else a.reshape(-1, cols)
+
+    def tname(name):                                      # (without dropout the masked copies are the tensors themselves)
+        return name[:-1] if (p == 0 and name in ("dzAm", "dzBm", "dzCm")) else name
+
+    def tmp(name, gl, cols):
+        return ws(tname(name), gl, cols)
+
+    def cmp(name, layer, ref, what, fwd=False, **kw):
+        """compare region `name` of `layer` (None: r.hvo) with its restatement; fwd: a comparison of the forward half"""
+        nonlocal n
+        n += 1
+        key = Ledger.key(tname(name), layer)
+        if fwd and not forward_checks:
+            led.did_compare(key, what + " (by the first walk of this forward)")
+            return
+        _ledger_compare(led, key, (lambda: r.hvo.numpy()) if name == "hvo" else (lambda: r.ws_get(tname(name), layer)), ref, what, **kw)
+
+    def gcmp(key, ref, what, rows=slice(None), **kw):
+        """compare (rows of) gradient tensor G[key]"""
+        nonlocal n
+        n += 1
+        _ledger_compare(led, ("grad", key, rows), lambda: G[key][rows], ref, what, **kw)
+
+    def memo(fn):
+        got = {}
+        return lambda dt: got[dt] if dt in got else got.setdefault(dt, fn(dt))
 
     def lin(a, w, b=None):
         y = rb(a) @ rb(w).T
@@ -509,8 +644,9 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     def ln(z, g, b):
         mu = z.mean(-1, keepdims=True)
         var = ((z - mu) ** 2).mean(-1, keepdims=True)
-        xh = (z - mu) / np.sqrt(var + 1e-5)
-        return xh * g + b, xh
+        rstd = 1.0 / np.sqrt(var + 1e-5)
+        xh = (z - mu) * rstd
+        return xh * g + b, xh, rstd
 
     def ln_bwd(dy, xh, rstd, g):
         gdy = dy * g
@@ -523,6 +659,7 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     P2 = r.precision_in_force() == 2
     hrb = (lambda a: rb(a)) if P2 else (lambda a: a)
     HID = dict(tol=2.0 ** -7, rms_tol=2e-4) if P2 else {}
+    HIDB = dict(tol=2.0 ** -7, rms_tol=4e-4)             # ... and behind a hidden rounding in the backward
     heads, hd = cfg["n_heads"], cfg["d_model"] // cfg["n_heads"]
 
     def split_heads(a):                                   # (M, d) -> (B, H, 32, hd)
@@ -531,39 +668,97 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     def merge_heads(a):
         return a.transpose(0, 2, 1, 3).reshape(M, heads * hd)
 
-    n = 0
-    fclose = _close if forward_checks else (lambda *a, **k: None)
+    def probs(name, gl, dt):                              # the device's saved probabilities (B, H, 32, 32)
+        return ws(name, gl, 32).reshape(M // 32, heads, 32, 32).astype(dt)
+
+    # ---- the attention core, one helper per direction for the three kinds (encoder self, decoder masked self, decoder cross).  Its arithmetic
+    # is fp32 at every precision (precision 2 only STORES q / k / v / dctx in bf16: ws() widens them), so the bars are the fp32 class bars
+    # unless an operand was rounded out of sight (precision 2's dctx).  qkv_of() -> the device's saved (q, k, v), each (M, d)
+    def attn_core(pre, gl, kind, qkv_of, Pname, ctxname, site, causal):
+        enc2 = P2 and gl < L
+
+        def p_ref(dt):
+            q_, k_ = (split_heads(a.astype(dt)) for a in qkv_of()[:2])
+            sc = (q_ @ k_.transpose(0, 1, 3, 2)) * dt(1.0 / np.sqrt(hd))
+            if causal:
+                sc = sc + np.triu(np.full((32, 32), -np.inf, dt), 1)
+            e = np.exp(sc - sc.max(-1, keepdims=True))
+            return e / e.sum(-1, keepdims=True)
+
+        def ctx_ref(dt):
+            pr = probs(Pname, gl, dt)
+            return merge_heads((pr * np.asarray(mask(site, pr.size, pr.shape), dt)) @ split_heads(qkv_of()[2].astype(dt)))
+
+        cmp(Pname, gl, p_ref, pre + ("attention probabilities over bf16-stored q / k" if enc2 else kind + " attention probabilities"), fwd=True, tol=2e-5)
+        if causal and forward_checks:
+            above = r.ws_get(Pname, gl).reshape(-1, 32, 32)[:, np.triu(np.ones((32, 32), bool), 1)]
+            assert not above.any(), "%s%s attention: %d probabilities above the diagonal are not exactly 0" % (pre, kind, int((above != 0).sum()))
+        cmp(ctxname, gl, ctx_ref, pre + ("attention output over bf16-stored v" if enc2 else kind + " attention output"), fwd=True,
+            stored16=r.bf16_only(ctxname, gl))
+
+    def attn_core_bwd(pre, gl, kind, qkv_of, Pname, site, dzm_of, wo, outname, flat):
+        """dq, dk, dv from the saved q, k, v, P, the dropout mask and dctx = the out-proj dgrad of the (compared) masked dz; flat: the cross
+        attention's layout [dq (M, d) | dk, dv (M, 2d)], else one (M, 3d) tensor"""
+        enc2 = P2 and gl < L                             # attn_bwd_lds_kernel, IN16: dctx itself is stored in bf16
+
+        def ref(dt):
+            dctx = rb(dzm_of()).astype(dt) @ rb(wo).astype(dt)
+            if enc2:
+                dctx = rb(dctx)
+            q_, k_, v_ = (split_heads(a.astype(dt)) for a in qkv_of())
+            pr = probs(Pname, gl, dt)
+            mk = np.asarray(mask(site, pr.size, pr.shape), dt)
+            do = split_heads(dctx)
+            dp = (do @ v_.transpose(0, 1, 3, 2)) * mk
+            ds = pr * (dp - (dp * pr).sum(-1, keepdims=True)) * dt(1.0 / np.sqrt(hd))
+            dq, dk, dv = merge_heads(ds @ k_), merge_heads(ds.transpose(0, 1, 3, 2) @ q_), merge_heads((pr * mk).transpose(0, 1, 3, 2) @ do)
+            return np.concatenate([dq.reshape(-1), np.concatenate([dk, dv], 1).reshape(-1)]) if flat else np.concatenate([dq, dk, dv], 1)
+
+        if enc2:
+            cmp(outname, gl, ref, pre + "attention backward over bf16-stored operands", tol=2.0 ** -6, rms_tol=2e-3)
+        else:
+            cmp(outname, gl, ref, pre + kind + " attention backward", stored16=r.bf16_only(outname, gl))
+
+    def self_qkv(gl):
+        def of():
+            qkv = ws("qkv", gl)
+            return tuple(qkv[:, i * d:(i + 1) * d] for i in range(3))
+        return of
+
+    def cross_qkv(gl):
+        def of():
+            kv = ws("kvx", gl)
+            return ws("qx", gl), kv[:, :d], kv[:, d:]
+        return of
+
     # ---------------------------------------------------------------------------------------------- forward
     def input_layer(xin, pre, a0name, outname, site):
-        nonlocal n
         a = lin(f64(xin).reshape(M, -1), P[pre + "weight"], P[pre + "bias"])
         safe = np.abs(a) > 1e-4
-        fclose(ws(a0name), a, pre + "pre-activation")
-        fclose(ws(outname), (np.maximum(a, 0) + pe) * mask(site, a.size, a.shape), pre + "output", where=safe)
-        n += 2
+        cmp(a0name, 0, a, pre + "pre-activation", fwd=True)
+        cmp(outname, 0, (np.maximum(a, 0) + pe) * mask(site, a.size, a.shape), pre + "output", fwd=True, where=safe)
 
-    def attn_block(name, gl, xin, inw, qkvname, ctxname, outname, xhname, normname, site, q_rows=None):
-        nonlocal n
+    def attn_block(name, gl, xin, inw, qkvname, ctxname, outname, xhname, rstdname, normname, site, q_rows=None):
         enc = P2 and gl < L
         out = lin(ws(ctxname, gl), P[name + "out_proj.weight"], P[name + "out_proj.bias"])
         out = (hrb(out) if enc else out) * mask(site, M * d, (M, d))
-        y, xh = ln(xin + out, P[normname + ".weight"], P[normname + ".bias"])
-        fclose(ws(outname, gl), y, "%s out-proj + norm (layer %d)" % (name, gl), **(HID if enc else dict(tol=2e-5)))
-        fclose(ws(xhname, gl), xh, "%s xhat (layer %d)" % (name, gl), **(HID if enc else dict(tol=2e-5)))
-        n += 2
+        y, xh, rstd = ln(xin + out, P[normname + ".weight"], P[normname + ".bias"])
+        cmp(outname, gl, y, "%s out-proj + norm (layer %d)" % (name, gl), fwd=True, **(HID if enc else dict(tol=2e-5)))
+        cmp(xhname, gl, xh, "%s xhat (layer %d)" % (name, gl), fwd=True, **(HID if enc else dict(tol=2e-5)))
+        cmp(rstdname, gl, rstd, "%s rstd (layer %d)" % (name, gl), fwd=True, **(HID if enc else dict(tol=2e-5)))
         return ws(outname, gl)
 
     def ffn_block(pre, gl, xin, normname, outname="xout"):
-        nonlocal n
         hp = lin(xin, P[pre + "linear1.weight"], P[pre + "linear1.bias"])
-        fclose(ws("hact", gl), np.maximum(hp, 0) * mask(ng.layer_site(gl, ng.S_FFN), hp.size, hp.shape),
-               pre + "linear1", where=np.abs(hp) > 1e-4, stored16=r.bf16_only("hact", gl))
+        cmp("hact", gl, np.maximum(hp, 0) * mask(ng.layer_site(gl, ng.S_FFN), hp.size, hp.shape),
+            pre + "linear1", fwd=True, where=np.abs(hp) > 1e-4, stored16=r.bf16_only("hact", gl))
         enc = P2 and gl < L - 1          # (the top encoder layer's linear2 feeds the two-norm pass from fp32)
         f = lin(ws("hact", gl), P[pre + "linear2.weight"], P[pre + "linear2.bias"])
         f = (hrb(f) if enc else f) * mask(ng.layer_site(gl, ng.S_DROPF), M * d, (M, d))
-        y, xh = ln(xin + f, P[pre + normname + ".weight"], P[pre + normname + ".bias"])
-        fclose(ws(outname, gl), y, pre + "linear2 + norm", **(HID if enc else dict(tol=2e-5)))
-        n += 2
+        y, xh, rstd = ln(xin + f, P[pre + normname + ".weight"], P[pre + normname + ".bias"])
+        cmp(outname, gl, y, pre + "linear2 + norm", fwd=True, **(HID if enc else dict(tol=2e-5)))
+        cmp("xhat2", gl, xh, pre + normname + " xhat", fwd=True, **(HID if enc else dict(tol=2e-5)))
+        cmp("rstd2", gl, rstd, pre + normname + " rstd", fwd=True, **(HID if enc else dict(tol=2e-5)))
         return ws(outname, gl)
 
     input_layer(x, "InputLayerEncoder.Linear.", "a0", "x0", ng.SITE_PE_ENC)
@@ -572,22 +767,15 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
     for l in range(L):
         pre = "Encoder.Encoder.layers.%d." % l
         enc_in.append(cur)
-        fclose(ws("qkv", l), lin(cur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "in_proj",
-               stored16=r.bf16_only("qkv", l))
-        n += 1
-        if P2:      # the attention core on bf16-STORED q / k / v (fp32 arithmetic; attn_fwd_lds_kernel): probabilities and ctx
-            qkv = ws("qkv", l)
-            q_, k_, v_ = (split_heads(qkv[:, i * d:(i + 1) * d]) for i in range(3))
-            sc = q_ @ k_.transpose(0, 1, 3, 2) / np.sqrt(hd)
-            pr = np.exp(sc - sc.max(-1, keepdims=True)); pr /= pr.sum(-1, keepdims=True)
-            fclose(f64(r.ws_get("P", l)).reshape(pr.shape), pr, pre + "attention probabilities over bf16-stored q / k", tol=2e-5)
-            pm = pr * mask(ng.layer_site(l, ng.S_ATTN), pr.size, pr.shape)
-            fclose(ws("ctx", l), merge_heads(pm @ v_), pre + "attention output over bf16-stored v", stored16=True)
-            n += 2
-        x1 = attn_block(pre + "self_attn.", l, cur, None, "qkv", "ctx", "x1", "xhat1", pre + "norm1", ng.layer_site(l, ng.S_DROP1))
+        cmp("qkv", l, lin(cur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "in_proj", fwd=True,
+            stored16=r.bf16_only("qkv", l))
+        attn_core(pre, l, "self", self_qkv(l), "P", "ctx", ng.layer_site(l, ng.S_ATTN), False)
+        x1 = attn_block(pre + "self_attn.", l, cur, None, "qkv", "ctx", "x1", "xhat1", "rstd1", pre + "norm1", ng.layer_site(l, ng.S_DROP1))
         cur = ffn_block(pre, l, x1, "norm2")
-    mem, _ = ln(cur, P["Encoder.Encoder.norm.weight"], P["Encoder.Encoder.norm.bias"])
-    fclose(ws("memory"), mem, "final encoder norm", tol=2e-5)
+    mem, xh, rstd = ln(cur, P["Encoder.Encoder.norm.weight"], P["Encoder.Encoder.norm.bias"])
+    cmp("memory", 0, mem, "final encoder norm", fwd=True, tol=2e-5)
+    cmp("enc_xhat", 0, xh, "final encoder norm xhat", fwd=True, tol=2e-5)
+    cmp("enc_rstd", 0, rstd, "final encoder norm rstd", fwd=True, tol=2e-5)
     final = ws("memory")
     dec_in = []
     if Ld:
@@ -596,117 +784,186 @@ def check_ops_bf16(r, P, cfg, x, tgt, rng, p, G=None, forward_checks=True):
         for l in range(Ld):
             pre, gl = "Decoder.Decoder.layers.%d." % l, L + l
             dec_in.append(ycur)
-            fclose(ws("qkv", gl), lin(ycur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "self in_proj")
-            y1 = attn_block(pre + "self_attn.", gl, ycur, None, "qkv", "ctx", "x1", "xhat1", pre + "norm1", ng.layer_site(gl, ng.S_DROP1))
+            cmp("qkv", gl, lin(ycur, P[pre + "self_attn.in_proj_weight"], P[pre + "self_attn.in_proj_bias"]), pre + "self in_proj", fwd=True)
+            attn_core(pre, gl, "masked self", self_qkv(gl), "P", "ctx", ng.layer_site(gl, ng.S_ATTN), True)
+            y1 = attn_block(pre + "self_attn.", gl, ycur, None, "qkv", "ctx", "x1", "xhat1", "rstd1", pre + "norm1", ng.layer_site(gl, ng.S_DROP1))
             wx, bx = P[pre + "multihead_attn.in_proj_weight"], P[pre + "multihead_attn.in_proj_bias"]
-            fclose(ws("qx", gl), lin(y1, wx[:d], bx[:d]), pre + "cross q in_proj")
-            fclose(ws("kvx", gl), lin(final, wx[d:], bx[d:]), pre + "cross kv in_proj")
-            n += 3
-            y2 = attn_block(pre + "multihead_attn.", gl, y1, None, "qx", "ctxx", "x2", "xhatx", pre + "norm2", ng.layer_site(gl, ng.S_DROP2))
+            cmp("qx", gl, lin(y1, wx[:d], bx[:d]), pre + "cross q in_proj", fwd=True)
+            cmp("kvx", gl, lin(final, wx[d:], bx[d:]), pre + "cross kv in_proj", fwd=True)
+            attn_core(pre, gl, "cross", cross_qkv(gl), "Px", "ctxx", ng.layer_site(gl, ng.S_XATTN), False)
+            y2 = attn_block(pre + "multihead_attn.", gl, y1, None, "qx", "ctxx", "x2", "xhatx", "rstdx", pre + "norm2", ng.layer_site(gl, ng.S_DROP2))
             ycur = ffn_block(pre, gl, y2, "norm3")
-        fin, _ = ln(ycur, P["Decoder.Decoder.norm.weight"], P["Decoder.Decoder.norm.bias"])
-        fclose(ws("dec_final"), fin, "final decoder norm", tol=2e-5)
+        # (dec_xhat / dec_rstd have no public name: the backward below takes the fp64 ones of the saved, compared norm input)
+        fin, dec_xh, dec_rstd = ln(ycur, P["Decoder.Decoder.norm.weight"], P["Decoder.Decoder.norm.bias"])
+        cmp("dec_final", 0, fin, "final decoder norm", fwd=True, tol=2e-5)
         final = ws("dec_final")
     logits = lin(final, P["OutputLayer.Linear.weight"], P["OutputLayer.Linear.bias"])
     want = np.concatenate([logits[:, :9], 1 / (1 + np.exp(-logits[:, 9:18])), 0.5 * np.tanh(logits[:, 18:])], 1)
-    fclose(r.hvo.numpy().reshape(M, 27), want, "output layer + heads")
-    n += 1
+    cmp("hvo", None, want, "output layer + heads", fwd=True)
     if G is None:
+        led.assert_closed()
         return n
     # ---------------------------------------------------------------------------------------------- backward
-    G = {k: f64(v) for k, v in G.items()}
-
-    def tmp(name, gl, cols):
-        return f64(r.ws_get(name if (p > 0 or not name.endswith("m")) else name[:-1], gl)).reshape(M, cols)
-
     def wgrad(dy, xin, wname, bname):
-        nonlocal n
-        _close(G[wname], rb(dy).T @ rb(xin), "grad " + wname)
-        _close(G[bname], rb(dy).sum(0), "grad " + bname)
-        n += 2
+        gcmp(wname, rb(dy).T @ rb(xin), "grad " + wname)
+        gcmp(bname, rb(dy).sum(0), "grad " + bname)
 
+    def masked(name, gl, site, what):
+        """the dropout-masked copy of a gradient (the operand of the Linear's dgrad and weight gradient) against the mask on the gradient"""
+        if p > 0:
+            cmp(name + "m", gl, lambda dt: tmp(name, gl, d).astype(dt) * np.asarray(mask(site, M * d, (M, d)), dt), what, tol=1e-6,
+                stored16=r.bf16_only(name + "m", gl))
+
+    def dlog_ref(dt):
+        """d loss / d logits = d loss / d hvo x the heads' derivatives at the device's hvo (heads_bwd_kernel); d loss / d hvo: the probe's,
+        or the loss's derivative at the device's hvo, y and the penalty (gt_loss)"""
+        led.consume("hvo")
+        a = f64(r.hvo.numpy()).reshape(M, 27).astype(dt)
+        if led.d_hvo_supplied:
+            led.consume("d_hvo")
+            g = f64(r.d_hvo.numpy()).reshape(M, 27).astype(dt)
+        else:
+            assert getattr(r, "d_hvo_from", None) == "loss", "d_hvo is neither the loss's nor the caller's"
+            y = f64(r.y.numpy()).reshape(M // 32, 32, 27).astype(dt)
+            hvo3 = a.reshape(M // 32, 32, 27)
+            _, dpred = ng.calculate_loss((hvo3[..., :9], hvo3[..., 9:18], hvo3[..., 18:]), y, float(np.float32(r.loss_penalty)))
+            g = np.concatenate(dpred, -1).reshape(M, 27).astype(dt)
+        return np.concatenate([g[:, :9], g[:, 9:18] * a[:, 9:18] * (1 - a[:, 9:18]), g[:, 18:] * (dt(0.5) - 2 * a[:, 18:] * a[:, 18:])], 1)
+
+    cmp("dlogits", 0, dlog_ref, "d loss / d logits (loss derivative x head derivatives)")
     dlog = ws("dlogits")
     wgrad(dlog, final, "OutputLayer.Linear.weight", "OutputLayer.Linear.bias")
 
+    # the output layer's dgrad (bf16 operands: mk_gemm) through the final norm and the top layer's closing norm: one fused row pass (ln_bwd2)
+    top = L + Ld - 1
+    fin_norm = "Decoder.Decoder.norm" if Ld else "Encoder.Encoder.norm"
+    top_norm = ("Decoder.Decoder.layers.%d.norm3" % (Ld - 1)) if Ld else ("Encoder.Encoder.layers.%d.norm2" % (L - 1))
+
+    def top_chain(dt):
+        dfin = rb(ws("dlogits")).astype(dt) @ rb(P["OutputLayer.Linear.weight"]).astype(dt)
+        xh, rs = (dec_xh, dec_rstd) if Ld else (ws("enc_xhat"), ws("enc_rstd", 0, 1))
+        mid, dgo, dbo = ln_bwd(dfin, xh.astype(dt), rs.astype(dt), P[fin_norm + ".weight"].astype(dt))
+        return (mid, dgo, dbo) + ln_bwd(mid, ws("xhat2", top).astype(dt), ws("rstd2", top, 1).astype(dt), P[top_norm + ".weight"].astype(dt))
+
+    top_chain = memo(top_chain)
+    cmp("dzA", top, lambda dt: top_chain(dt)[3], "output layer dgrad + final norm + top layer's closing norm backward", tol=1e-4)
+    gcmp(fin_norm + ".weight", lambda dt: top_chain(dt)[1], "grad " + fin_norm + ".weight (behind the output layer's dgrad)", tol=1e-4)
+    gcmp(fin_norm + ".bias", lambda dt: top_chain(dt)[2], "grad " + fin_norm + ".bias (behind the output layer's dgrad)", tol=1e-4)
+    gcmp(top_norm + ".weight", lambda dt: top_chain(dt)[4], "grad " + top_norm + ".weight (two-norm row pass)", tol=1e-4)
+    gcmp(top_norm + ".bias", lambda dt: top_chain(dt)[5], "grad " + top_norm + ".bias (two-norm row pass)", tol=1e-4)
+
     def ffn_bwd(pre, gl, xin, dz_name, prev_xh, prev_rstd, prev_norm, dzprev_name):
-        nonlocal n
+        masked(dz_name, gl, ng.layer_site(gl, ng.S_DROPF), pre + "dropout mask on the gradient of linear2's output")
         dz, dzm = tmp(dz_name, gl, d), tmp(dz_name + "m", gl, d)
         wgrad(dzm, ws("hact", gl), pre + "linear2.weight", pre + "linear2.bias")
         dh = (rb(dzm) @ rb(P[pre + "linear2.weight"])) * np.where(ws("hact", gl) != 0, scale, 0.0)
-        _close(tmp("dhid", gl, F), dh, pre + "linear2 dgrad (relu / dropout mask)", stored16=r.bf16_only("dhid", gl))
+        cmp("dhid", gl, dh, pre + "linear2 dgrad (relu / dropout mask)", stored16=r.bf16_only("dhid", gl))
         dhid = tmp("dhid", gl, F)
         wgrad(dhid, xin, pre + "linear1.weight", pre + "linear1.bias")
         enc = P2 and gl < L
         pre_ln = rb(dhid) @ rb(P[pre + "linear1.weight"])
         pre_ln = (hrb(pre_ln) if enc else pre_ln) + dz
         want, dg, db = ln_bwd(pre_ln, ws(prev_xh, gl), ws(prev_rstd, gl, 1), P[pre + prev_norm + ".weight"])
-        HB = dict(tol=2.0 ** -7, rms_tol=4e-4) if enc else dict(tol=1e-4)
-        _close(tmp(dzprev_name, gl, d), want, pre + "linear1 dgrad + " + prev_norm + " backward", **HB)
-        _close(G[pre + prev_norm + ".weight"], dg, "grad " + pre + prev_norm + ".weight", **HB)
-        _close(G[pre + prev_norm + ".bias"], db, "grad " + pre + prev_norm + ".bias", **HB)
-        n += 4
+        HB = HIDB if enc else dict(tol=1e-4)
+        cmp(dzprev_name, gl, want, pre + "linear1 dgrad + " + prev_norm + " backward", **HB)
+        gcmp(pre + prev_norm + ".weight", dg, "grad " + pre + prev_norm + ".weight", **HB)
+        gcmp(pre + prev_norm + ".bias", db, "grad " + pre + prev_norm + ".bias", **HB)
 
+    for l in reversed(range(Ld)):
+        pre, gl = "Decoder.Decoder.layers.%d." % l, L + l
+        ffn_bwd(pre, gl, ws("x2", gl), "dzA", "xhatx", "rstdx", "norm2", "dzB")
+        masked("dzB", gl, ng.layer_site(gl, ng.S_DROP2), pre + "dropout2 mask on the gradient")
+        wo = P[pre + "multihead_attn.out_proj.weight"]
+        wgrad(tmp("dzBm", gl, d), ws("ctxx", gl), pre + "multihead_attn.out_proj.weight", pre + "multihead_attn.out_proj.bias")
+        attn_core_bwd(pre, gl, "cross", cross_qkv(gl), "Px", ng.layer_site(gl, ng.S_XATTN), lambda gl=gl: tmp("dzBm", gl, d), wo, "dqkvx", True)
+        dqkvx = ws("dqkvx", gl).reshape(-1)
+        dqx, dkvx = dqkvx[:M * d].reshape(M, d), dqkvx[M * d:].reshape(M, 2 * d)
+        wx = P[pre + "multihead_attn.in_proj_weight"]
+        gcmp(pre + "multihead_attn.in_proj_weight", rb(dqx).T @ rb(ws("x1", gl)), "grad " + pre + "cross q in_proj weight", rows=slice(0, d))
+        gcmp(pre + "multihead_attn.in_proj_weight", rb(dkvx).T @ rb(ws("memory")), "grad " + pre + "cross kv in_proj weight", rows=slice(d, 3 * d))
+        gcmp(pre + "multihead_attn.in_proj_bias", np.concatenate([rb(dqx).sum(0), rb(dkvx).sum(0)]), "grad " + pre + "cross in_proj bias")
+
+        def c_chain(dt, gl=gl, dqx=dqx, wx=wx, pre=pre):     # dz1 = LNbwd_norm1(dqx Wq + dz2)
+            pre_ln = rb(dqx).astype(dt) @ rb(wx[:d]).astype(dt) + tmp("dzB", gl, d).astype(dt)
+            return ln_bwd(pre_ln, ws("xhat1", gl).astype(dt), ws("rstd1", gl, 1).astype(dt), P[pre + "norm1.weight"].astype(dt))
+
+        c_chain = memo(c_chain)
+        cmp("dzC", gl, lambda dt: c_chain(dt)[0], pre + "cross q dgrad + norm1 backward", tol=1e-4)
+        gcmp(pre + "norm1.weight", lambda dt: c_chain(dt)[1], "grad " + pre + "norm1.weight", tol=1e-4)
+        gcmp(pre + "norm1.bias", lambda dt: c_chain(dt)[2], "grad " + pre + "norm1.bias", tol=1e-4)
+        masked("dzC", gl, ng.layer_site(gl, ng.S_DROP1), pre + "dropout1 mask on the gradient")
+        wgrad(tmp("dzCm", gl, d), ws("ctx", gl), pre + "self_attn.out_proj.weight", pre + "self_attn.out_proj.bias")
+        attn_core_bwd(pre, gl, "masked self", self_qkv(gl), "P", ng.layer_site(gl, ng.S_ATTN), lambda gl=gl: tmp("dzCm", gl, d),
+                      P[pre + "self_attn.out_proj.weight"], "dqkv", False)
+        wgrad(tmp("dqkv", gl, 3 * d), dec_in[l], pre + "self_attn.in_proj_weight", pre + "self_attn.in_proj_bias")
+
+        def in_chain(dt, gl=gl, pre=pre):                    # the self in-proj dgrad + the residual branch's gradient
+            return rb(tmp("dqkv", gl, 3 * d)).astype(dt) @ rb(P[pre + "self_attn.in_proj_weight"]).astype(dt) + tmp("dzC", gl, d).astype(dt)
+
+        if l > 0:
+            pp = "Decoder.Decoder.layers.%d." % (l - 1)
+
+            def below(dt, gl=gl, pp=pp, in_chain=in_chain):
+                return ln_bwd(in_chain(dt), ws("xhat2", gl - 1).astype(dt), ws("rstd2", gl - 1, 1).astype(dt), P[pp + "norm3.weight"].astype(dt))
+
+            below = memo(below)
+            cmp("dzA", gl - 1, lambda dt: below(dt)[0], pre + "self in_proj dgrad + previous layer's norm3 backward", tol=1e-4)
+            gcmp(pp + "norm3.weight", lambda dt: below(dt)[1], "grad " + pp + "norm3.weight", tol=1e-4)
+            gcmp(pp + "norm3.bias", lambda dt: below(dt)[2], "grad " + pp + "norm3.bias", tol=1e-4)
+        else:
+            # The decoder input layer's backward.  Its output (da0_dec) has no public name: it is checked through the weight and bias gradients
+            # it feeds, the dropout / ReLU mask restated from b0 and da rounded to bf16 where the weight gradient rounds it -- weight and bias
+            # gradients: the matmul-like class bar
+            def din(dt, in_chain=in_chain):
+                da = rb(in_chain(dt) * np.asarray(mask(ng.SITE_PE_DEC, M * d, (M, d)), dt) * (ws("b0") > 0))
+                return da.T @ rb(f64(tgt).reshape(M, -1)).astype(dt), da.sum(0)
+
+            din = memo(din)
+            gcmp("InputLayerDecoder.Linear.weight", lambda dt: din(dt)[0], "grad InputLayerDecoder.Linear.weight (in_proj dgrad, dropout, relu mask)")
+            gcmp("InputLayerDecoder.Linear.bias", lambda dt: din(dt)[1], "grad InputLayerDecoder.Linear.bias (in_proj dgrad, dropout, relu mask)")
     if Ld:
         # encoder half of the encoder-decoder backward: the memory gradient = the sum of the decoder layers' cross-attention k / v
         # dgrads; through the final encoder norm and the top layer's closing norm it becomes that layer's dz (one fused row pass on the device)
         dmem = np.zeros((M, d))
         for l in range(Ld):
-            dkvx = f64(r.ws_get("dqkvx", L + l))[M * d:].reshape(M, 2 * d)
+            dkvx = ws("dqkvx", L + l).reshape(-1)[M * d:].reshape(M, 2 * d)
             dmem += rb(dkvx) @ rb(P["Decoder.Decoder.layers.%d.multihead_attn.in_proj_weight" % l][d:])
-        _close(ws("dmem"), dmem, "memory gradient (sum of the cross-attention k / v dgrads)", tol=1e-4)
+        cmp("dmem", 0, dmem, "memory gradient (sum of the cross-attention k / v dgrads)", tol=1e-4)
         g_top, dg, db = ln_bwd(ws("dmem"), ws("enc_xhat"), ws("enc_rstd", 0, 1), P["Encoder.Encoder.norm.weight"])
-        _close(G["Encoder.Encoder.norm.weight"], dg, "grad Encoder.Encoder.norm.weight", tol=1e-4)
-        _close(G["Encoder.Encoder.norm.bias"], db, "grad Encoder.Encoder.norm.bias", tol=1e-4)
-        want, _, _ = ln_bwd(g_top, ws("xhat2", L - 1), ws("rstd2", L - 1, 1), P["Encoder.Encoder.layers.%d.norm2.weight" % (L - 1)])
-        _close(tmp("dzA", L - 1, d), want, "final encoder norm + top layer's norm2 backward", tol=1e-4)
-        n += 4
+        gcmp("Encoder.Encoder.norm.weight", dg, "grad Encoder.Encoder.norm.weight", tol=1e-4)
+        gcmp("Encoder.Encoder.norm.bias", db, "grad Encoder.Encoder.norm.bias", tol=1e-4)
+        pp = "Encoder.Encoder.layers.%d." % (L - 1)
+        want, dg, db = ln_bwd(g_top, ws("xhat2", L - 1), ws("rstd2", L - 1, 1), P[pp + "norm2.weight"])
+        cmp("dzA", L - 1, want, "final encoder norm + top layer's norm2 backward", tol=1e-4)
+        gcmp(pp + "norm2.weight", dg, "grad " + pp + "norm2.weight (two-norm row pass)", tol=1e-4)
+        gcmp(pp + "norm2.bias", db, "grad " + pp + "norm2.bias (two-norm row pass)", tol=1e-4)
     for l in reversed(range(L)):
         pre = "Encoder.Encoder.layers.%d." % l
         ffn_bwd(pre, l, ws("x1", l), "dzA", "xhat1", "rstd1", "norm1", "dzB")
-        dz1, dz1m = tmp("dzB", l, d), tmp("dzBm", l, d)
+        dz1 = tmp("dzB", l, d)
         if p > 0:
-            _close(dz1m, dz1 * mask(ng.layer_site(l, ng.S_DROP1), M * d, (M, d)), pre + "dropout1 mask on the gradient", tol=1e-6,
-                   stored16=r.bf16_only("dzBm", l))
+            cmp("dzBm", l, dz1 * mask(ng.layer_site(l, ng.S_DROP1), M * d, (M, d)), pre + "dropout1 mask on the gradient", tol=1e-6,
+                stored16=r.bf16_only("dzBm", l))
+        dz1m = tmp("dzBm", l, d)
         wgrad(dz1m, ws("ctx", l), pre + "self_attn.out_proj.weight", pre + "self_attn.out_proj.bias")
+        attn_core_bwd(pre, l, "self", self_qkv(l), "P", ng.layer_site(l, ng.S_ATTN), lambda l=l: tmp("dzBm", l, d),
+                      P[pre + "self_attn.out_proj.weight"], "dqkv", False)
         dqkv = tmp("dqkv", l, 3 * d)
-        if P2:      # attention backward over bf16-stored q / k / v / dctx (attn_bwd_lds_kernel, IN16): dctx = the out-proj dgrad, itself stored in bf16
-            dctx = hrb(rb(dz1m) @ rb(P[pre + "self_attn.out_proj.weight"]))
-            qkv = ws("qkv", l)
-            q_, k_, v_ = (split_heads(qkv[:, i * d:(i + 1) * d]) for i in range(3))
-            pr = f64(r.ws_get("P", l)).reshape(M // 32, heads, 32, 32)
-            mk = mask(ng.layer_site(l, ng.S_ATTN), pr.size, pr.shape)
-            do = split_heads(dctx)
-            dp = (do @ v_.transpose(0, 1, 3, 2)) * mk
-            ds = pr * (dp - (dp * pr).sum(-1, keepdims=True)) / np.sqrt(hd)
-            want = np.concatenate([merge_heads(ds @ k_), merge_heads(ds.transpose(0, 1, 3, 2) @ q_), merge_heads((pr * mk).transpose(0, 1, 3, 2) @ do)], 1)
-            _close(dqkv, want, pre + "attention backward over bf16-stored operands", tol=2.0 ** -6, rms_tol=2e-3)
-            n += 1
         wgrad(dqkv, enc_in[l], pre + "self_attn.in_proj_weight", pre + "self_attn.in_proj_bias")
         dx = rb(dqkv) @ rb(P[pre + "self_attn.in_proj_weight"])
         dx = (hrb(dx) if (P2 and l > 0) else dx) + dz1
         if l > 0:
             pp = "Encoder.Encoder.layers.%d." % (l - 1)
-            want, _, _ = ln_bwd(dx, ws("xhat2", l - 1), ws("rstd2", l - 1, 1), P[pp + "norm2.weight"])
-            _close(tmp("dzA", l - 1, d), want, pre + "in_proj dgrad + previous layer's norm2 backward",
-                   **(dict(tol=2.0 ** -7, rms_tol=4e-4) if P2 else dict(tol=1e-4)))
+            want, dg, db = ln_bwd(dx, ws("xhat2", l - 1), ws("rstd2", l - 1, 1), P[pp + "norm2.weight"])
+            HB = HIDB if P2 else dict(tol=1e-4)
+            cmp("dzA", l - 1, want, pre + "in_proj dgrad + previous layer's norm2 backward", **HB)
+            gcmp(pp + "norm2.weight", dg, "grad " + pp + "norm2.weight", **HB)
+            gcmp(pp + "norm2.bias", db, "grad " + pp + "norm2.bias", **HB)
         else:
             da = dx * mask(ng.SITE_PE_ENC, M * d, (M, d)) * (ws("a0") > 0)
-            _close(ws("dctx"), da, "InputLayer backward (in_proj dgrad, dropout, relu mask)", tol=1e-4)
+            cmp("dctx", 0, da, "InputLayer backward (in_proj dgrad, dropout, relu mask)", tol=1e-4)
             wgrad(ws("dctx"), f64(x).reshape(M, -1), "InputLayerEncoder.Linear.weight", "InputLayerEncoder.Linear.bias")
-        n += 1
-    for l in reversed(range(Ld)):
-        pre, gl = "Decoder.Decoder.layers.%d." % l, L + l
-        ffn_bwd(pre, gl, ws("x2", gl), "dzA", "xhatx", "rstdx", "norm2", "dzB")
-        wgrad(tmp("dzBm", gl, d), ws("ctxx", gl), pre + "multihead_attn.out_proj.weight", pre + "multihead_attn.out_proj.bias")
-        dqkvx = f64(r.ws_get("dqkvx", gl))
-        dqx, dkvx = dqkvx[:M * d].reshape(M, d), dqkvx[M * d:].reshape(M, 2 * d)
-        gw, gb = G[pre + "multihead_attn.in_proj_weight"], G[pre + "multihead_attn.in_proj_bias"]
-        _close(gw[:d], rb(dqx).T @ rb(ws("x1", gl)), "grad " + pre + "cross q in_proj weight")
-        _close(gw[d:], rb(dkvx).T @ rb(ws("memory")), "grad " + pre + "cross kv in_proj weight")
-        _close(gb, np.concatenate([rb(dqx).sum(0), rb(dkvx).sum(0)]), "grad " + pre + "cross in_proj bias")
-        wgrad(tmp("dzCm", gl, d), ws("ctx", gl), pre + "self_attn.out_proj.weight", pre + "self_attn.out_proj.bias")
-        wgrad(tmp("dqkv", gl, 3 * d), dec_in[l], pre + "self_attn.in_proj_weight", pre + "self_attn.in_proj_bias")
-        n += 3
+    led.assert_closed()
     return n
 
 
@@ -767,30 +1024,50 @@ def _check_bf16_shadows(backend, cfg, B, p, P, x, y):
     return n
 
 
-def check_step_bf16(backend, cfg, B, p=0.0, penalty=0.47, seed=3, precision=1, flags=0):
+def check_step_bf16(backend, cfg, B, p=0.0, penalty=0.47, seed=3, precision=1, flags=0, regime=None):
     """precision = 2: the same two bars; the end-to-end sanity bound is taken against the bf16-OPERAND oracle with a wider factor (the
-    storage roundings of precision 2 are additional noise of the same size: 2.5 x the bf16 effect)"""
+    storage roundings of precision 2 are additional noise of the same size: 2.5 x the bf16 effect).
+    regime: a name of tests/regimes.py -- the parameters moved away from initialisation, the regime's condition asserted on the fp64
+    (bf16-operand) oracle's cache.  The per-operation walk keeps its fixed class bars (_close's np.float32 rule included) and is the
+    assertion.  Three end-to-end assertions are not made, in two regimes (reasons below): the max-abs bound in saturated, and both the
+    max-abs and the rms bound in shift with precision 2 in force."""
     cfg = dict(cfg, dropout=p, precision=precision)
     cfg0 = dict(cfg, precision=0)
-    P = ng.init_params(cfg, seed=seed, perturb=0.05)
+    P = regimes.apply(ng.init_params(cfg, seed=seed, perturb=0.05), cfg, regime, seed)
     x, y = ng.synthetic_batch(B, cfg["embedding_size_src"], seed=seed + 2)
     Ld = cfg.get("num_decoder_layers", 0)
     tgt = shift_right(y) if Ld else None
     rng = (1234, 99, 7)
+    (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=rng if p > 0 else None, dtype=np.float64)
+    FIGURES.clear()
+    BF16_FIGURES.clear()
+    if regime is not None:
+        FIGURES["regime"] = regimes.assert_condition(regime, C, h)
     r = Runner(cfg, B, backend, rng=rng, flags=flags)
     r.set_params(P)
     hvo = r.forward(x, tgt, train=p > 0)
     # (2) end to end, sanity bound
-    (h, v, o), C = ng.forward(P, cfg, x, tgt=tgt, rng=rng if p > 0 else None, dtype=np.float64)
     (h0, v0, o0), _ = ng.forward(P, cfg0, x, tgt=tgt, rng=rng if p > 0 else None, dtype=np.float64)
     ref, ref0 = np.concatenate([h, v, o], -1), np.concatenate([h0, v0, o0], -1)
     eq = _rms(ref0 - ref)
     assert eq > 1e-5, "the bf16 rounding has no visible effect on this case: pick another"
-    assert np.abs(hvo - ref).max() < BF16_OUT_MAX, "forward max-abs %g" % np.abs(hvo - ref).max()
     frac = BF16_E2E_FRAC if r.precision_in_force() < 2 else 2.5
-    FIGURES.clear()
+    FIGURES["bf16_out_max"] = float(np.abs(hvo - ref).max() / BF16_OUT_MAX)
     FIGURES["bf16_e2e"] = _rms(hvo - ref) / (frac * eq + 1e-5)
-    assert _rms(hvo - ref) <= frac * eq + 1e-5, "forward rms %g vs bf16 effect %g" % (_rms(hvo - ref), eq)
+    # Two regimes take a forward bound away, because E_q -- the distance between the two ORACLES -- no longer measures what separates the device
+    # from them; the bound relative to the loss and the walk, which is the assertion, stay.
+    # saturated: the absolute 5e-2 was sized for hit logits within +-1.7.  With the output layer's weights x 30 they reach +-23 ... +-91, and ONE
+    # operand element that rounds to the neighbouring bf16 on the device -- the decorrelation described above -- moves such a logit by 3e-2
+    # (emulator, d_model 32: 0.63 of the bound from a single flip).  The bound relative to E_q, which scales with the logits, stays.
+    # shift with precision 2 in force: k carries a bias of N(0, 40), and STORING it in bf16 moves each element by up to 2^-9 of that -- score noise
+    # the operand-rounding oracle E_q is measured on does not have (its k is rounded inside the in-proj only, before the bias is added): the
+    # device sits 3.7 x E_q (emulator, d_model 256) and 0.078 max-abs (MI355X, d_model 512) from that oracle.  The walk restates the softmax
+    # over the STORED q / k.
+    stored_k = regime == "shift" and r.precision_in_force() == 2
+    if regime != "saturated" and not stored_k:
+        assert np.abs(hvo - ref).max() < BF16_OUT_MAX, "forward max-abs %g" % np.abs(hvo - ref).max()
+    if not stored_k:
+        assert _rms(hvo - ref) <= frac * eq + 1e-5, "forward rms %g vs bf16 effect %g" % (_rms(hvo - ref), eq)
     stats, d_hvo = r.loss(y, penalty)
     rstats, _ = ng.calculate_loss((h, v, o), y.astype(np.float64), penalty)
     assert abs(stats[0] - rstats[0]) < 1e-2 * max(1.0, abs(rstats[0]))
