@@ -1351,6 +1351,88 @@ def check_predict(backend, cfg, B, use_thres=True, thres=0.5, out_tol=OUT_TOL, m
     assert np.abs(hvo[..., 9:] - np.concatenate([v, o], -1)).max() < out_tol
 
 
+def predict_inputs(cfg, B, seed=21):
+    """check_predict's fixed inputs for one shape: (cfg with dropout 0.3 -- predict is eval mode: it must be ignored --, parameters, x)"""
+    cfg = dict(cfg, dropout=0.3)
+    return cfg, ng.init_params(cfg, seed=seed, perturb=0.05), ng.synthetic_batch(B, cfg["embedding_size_src"], seed=8)[0]
+
+
+# the largest share of hit decisions a check_predict_forced case may leave uncompared (inside the margin), per precision: a condition on the
+# case's inputs, not a tolerance.  fp32: the fp64 oracle's own share below 1e-4 is 9.1e-4 at d_model 32 and 0 at 64 (73 728 decisions each);
+# bf16 operands: its share below 1e-3 is 9.5e-3, about 5 % below the 5e-3 margin
+MAX_LEFT_OUT = {0: 0.01, 1: 0.10}
+
+
+def check_predict_forced(P, cfg, x, hvo, use_thres=True, thres=None, pd_seed=None, first_seq=0, temperature=1.0, prob=None,
+                         out_tol=OUT_TOL, margin_tol=1e-4, max_left_out=None):
+    """A finished predict -- hvo (N, 32, 27) from Runner.predict, gt_predict_voices (uncapped, unmasked) or StepEngine.predict over the set x
+    -- against ONE eval forward of the fp64 oracle, teacher-forced as check_update is: greedy decoding is causal (step t sees target rows
+    0..t only), so the oracle's forward with tgt = shift_right(hvo) restates every decode step from the device's OWN earlier decisions.
+    Nothing propagates; all 32 N rows are compared, where check_predict stops a sequence at its first decision inside the margin.
+      v, o:  |hvo[..., 9:] - ref| < out_tol on every row.
+      use_thres False (and no pd_seed):  |hvo[..., :9] - sigmoid(h_ref)| < out_tol on every row.
+      thresholded / sampled:  hits in {0, 1}, equal to sigmoid(h_ref / temperature) > cut wherever that probability is more than margin_tol
+        from cut; cut = thres (a number or one per voice; None: 0.5), or with pd_seed ng.pd_uniforms at the element's index in the whole set
+        (first_seq: the index of x[0] in it); pd_seed and a thres (gt_predict_voices' sampled mode): a hit needs p above both, the margin is
+        the smaller one.  The hit fraction lies in (0.02, 0.98), and at most max_left_out (MAX_LEFT_OUT of cfg's precision) of the decisions
+        lie inside the margin.
+      prob: the call's prob_out (N, 32, 9), held to sigmoid(h_ref / temperature) within out_tol on every row.
+    Encoder-only models: the same comparisons against the plain forward.  Records FIGURES "out" (worst error / out_tol) and "left_out" (the
+    share of decisions inside the margin); returns the oracle's (h, v, o)."""
+    cfg = dict(cfg)
+    N = x.shape[0]
+    hvo = np.asarray(hvo, np.float64).reshape(N, 32, 27)
+    if max_left_out is None:
+        max_left_out = MAX_LEFT_OUT[1 if cfg.get("precision", 0) else 0]
+    tgt = shift_right(hvo) if cfg.get("num_decoder_layers", 0) else None
+    (h, v, o), _ = ng.forward(P, cfg, x, tgt=tgt, dtype=np.float64)                  # (rng None: eval mode whatever cfg's dropout)
+    FIGURES.clear()
+    vo_err = np.abs(hvo[..., 9:] - np.concatenate([v, o], -1))
+    FIGURES["out"] = float(vo_err.max() / out_tol)
+    p_ref = 1.0 / (1.0 + np.exp(-h / float(temperature)))
+    if prob is not None:
+        perr = np.abs(np.asarray(prob, np.float64).reshape(N, 32, 9) - p_ref)
+        FIGURES["out"] = max(FIGURES["out"], float(perr.max() / out_tol))
+    decided = use_thres or pd_seed is not None
+    if not decided:
+        herr = np.abs(hvo[..., :9] - p_ref)
+        FIGURES["out"] = max(FIGURES["out"], float(herr.max() / out_tol))
+        FIGURES["left_out"] = 0.0
+    else:
+        cuts = []
+        if pd_seed is not None:
+            cuts.append(ng.pd_uniforms(pd_seed, first_seq + N)[first_seq:])
+        if thres is not None or pd_seed is None:
+            cuts.append(np.broadcast_to(np.asarray(0.5 if thres is None else thres, np.float64), (N, 32, 9)))
+        want = np.ones((N, 32, 9), bool)
+        margin = np.full((N, 32, 9), np.inf)
+        for cut in cuts:
+            want &= p_ref > cut
+            margin = np.minimum(margin, np.abs(p_ref - cut))
+        sure = margin > margin_tol
+        FIGURES["left_out"] = float((~sure).mean())
+    # ---- the assertions, after every figure is on record
+    if not vo_err.max() < out_tol:
+        i = tuple(int(j) for j in np.unravel_index(int(np.argmax(vo_err)), vo_err.shape))
+        raise AssertionError("v / o: sequence %d step %d column %d: max-abs %.3g (bar %g), %d elements over" % (i[0], i[1], 9 + i[2], vo_err.max(), out_tol, int((vo_err >= out_tol).sum())))
+    if prob is not None:
+        assert perr.max() < out_tol, "prob_out max-abs %g (bar %g)" % (perr.max(), out_tol)
+    if not decided:
+        assert herr.max() < out_tol, "hit probabilities max-abs %g (bar %g)" % (herr.max(), out_tol)
+        return h, v, o
+    hits = hvo[..., :9]
+    assert set(np.unique(hits)) <= {0.0, 1.0}, np.unique(hits)[:8]
+    wrong = sure & ((hits != 0) != want)
+    if wrong.any():
+        i = tuple(int(j) for j in np.argwhere(wrong)[0])
+        raise AssertionError("%d hits differ outside the margin, first at sequence %d step %d voice %d: device %g, oracle p %.9g, margin %.3g"
+                             % (int(wrong.sum()), i[0], i[1], i[2], hits[i], p_ref[i], margin[i]))
+    frac = float(hits.mean())
+    assert 0.02 < frac < 0.98, "hit fraction %g: the case decides nothing" % frac
+    assert FIGURES["left_out"] <= max_left_out, "%.3g of the decisions lie inside the margin %g (cap %g): pick other inputs" % (FIGURES["left_out"], margin_tol, max_left_out)
+    return h, v, o
+
+
 def check_golden(backend, path):
     """HIP/emulated path against the committed torch-generated vectors."""
     z = np.load(path)
