@@ -282,6 +282,50 @@ int64_t gt_voice_metrics_scratch_floats(int64_t n_rows);
 int gt_voice_metrics(const float* hvo_pred, const float* hvo_gt, int64_t n_rows, float* out30, float* scratch,
                      gt_stream_t stream);
 
+/* Per-voice hit threshold curves (no counterpart in ref:evaluator.py:522-525, whose only hit metric is the accuracy gt_voice_metrics
+ * computes -- dominated by the empty cells): for each voice and each of the two classes (the ground truth is a hit, or is not), how many
+ * predicted probabilities lie above each threshold of a grid.  Precision, recall and F-beta at any grid threshold follow from the counts,
+ * and so does the threshold that is best under a rule (gt_hit_thresholds): the nine numbers gt_predict_voices' thres takes.
+ * prob: device; the probability of row m, voice c is prob[m * prob_stride + c].  prob_stride 9 = the prob_out of gt_predict_voices, 27 = the
+ * hit columns of an HVO buffer written by gt_predict with use_thres 0; nothing else is accepted.  hvo_gt (n_rows,27): the class is
+ * g = (hvo_gt[m * 27 + c] == 1.0f), the loss's yh == 1 convention.  thres is HOST memory, read when the call is enqueued (a captured graph
+ * keeps the values): n_thres values, strictly ascending, each in [0,1].
+ * bin(p) = the number of k with p > thres[k] -- fp32 and strict, the comparison gt_predict_voices decides hits with; bin(NaN) = 0.
+ * counts: device, 9 * 2 * (n_thres + 1) unsigned 64-bit words; counts[(c * 2 + g) * (n_thres + 1) + bin] += 1 for every element.  The call
+ * ADDS: zero the buffer once and walk a set in chunks.  TP_k(c) = sum of counts[c][1][b] over b > k, FP_k(c) the same with g = 0,
+ * P(c) = sum of counts[c][1][b] over all b, FN_k = P - TP_k.  Integer arithmetic throughout: the result depends on neither the launch
+ * geometry nor on how a set is cut into calls or on their order.
+ * Two launches (csrc/gt_curve.h): workgroups with 32-bit LDS histograms write partials to scratch, a second kernel adds them onto counts
+ * (one writer per word: no global atomics).  scratch: gt_hit_curve_scratch_words 32-bit words, device; NO precondition (every word read was
+ * written by the same call) -- it need not be zeroed and is not left zero.  No host sync, no allocation; capturable.
+ * Rejected before any launch, counts untouched: a NULL pointer, n_rows <= 0 or >= 2^31, n_thres < 1 or > GT_CURVE_MAX_THRES, a prob_stride
+ * other than 9 or 27, a threshold that is NaN or outside [0,1], thresholds not strictly ascending. */
+#define GT_CURVE_MAX_THRES 127
+int64_t gt_hit_curve_scratch_words(int64_t n_rows, int32_t n_thres);          /* 32-bit words */
+int gt_hit_curve(const float* prob, int32_t prob_stride, const float* hvo_gt, int64_t n_rows,
+                 const float* thres, int32_t n_thres, uint64_t* counts, uint32_t* scratch, gt_stream_t stream);
+/* The choice, a pure host function (like gt_param_layout): counts_host = a HOST copy of gt_hit_curve's counts over the same grid.  Per voice,
+ * in fp64 from the integers above:
+ *   criterion 0 (F-beta): with b2 = (double)beta * beta, score_k = (1 + b2) TP_k / ((1 + b2) TP_k + b2 FN_k + FP_k), 0 where TP_k == 0; each
+ *     product is rounded on its own and the denominator summed left to right -- compiled with floating-point contraction off, so no fused
+ *     multiply-add is formed.  The candidates are the k whose score EQUALS the maximum (equal counts give equal doubles: the plateau
+ *     between two distinct probabilities is an exact tie);
+ *   criterion 1 (density): the candidates are the k that minimise |TP_k + FP_k - P|, an integer: the voice places as many hits as the
+ *     ground truth has.
+ * The chosen index is the LOWER MEDIAN of the candidates: element (n - 1) / 2 of their ascending list.  thres_out[c] = thres[index_out[c]].
+ * Fallback -- index_out[c] = -1, thres_out[c] = rule->fallback, four zero scores -- where P == 0, and under criterion 0 where the best score is 0.
+ * scores_out[4 c ..] at the chosen index: precision TP / (TP + FP) (0 for a zero denominator), recall TP / P, the F-beta score (criterion 1:
+ * with rule->beta where that is > 0 and finite, else 0), the density ratio (TP + FP) / P.
+ * Rejected: a NULL pointer, a grid gt_hit_curve would reject, a criterion other than 0 / 1, under criterion 0 a beta <= 0 or not finite,
+ * a fallback outside [0,1]. */
+typedef struct gt_threshold_rule {
+  int32_t criterion;   /* 0 = F-beta, 1 = density */
+  float beta;          /* > 0, finite; criterion 0 only */
+  float fallback;      /* in [0,1]: the threshold of a voice the rule cannot decide */
+} gt_threshold_rule;
+int gt_hit_thresholds(const uint64_t* counts_host, const float* thres, int32_t n_thres, const gt_threshold_rule* rule,
+                      float* thres_out /*9*/, int32_t* index_out /*9*/, float* scores_out /*9 x 4*/);
+
 /* Replaces GrooveMidiDatasetInfilling.__getitem__ + the DataLoader's collate for a dataset resident in HBM
  * (ref:dataset.py:263-264,355-356; ref:train.py:156-158): x[b] = xs[idx[b]], y[b] = ys[idx[b]] for b < batch, both step
  * inputs in ONE launch.  xs (n_seq,32,src_dim), ys (n_seq,32,27) fp32; idx int64 on the device (out-of-range entries are

@@ -100,6 +100,12 @@ def build_parser():
     p.add_argument("--infill_max", default=None, type=int, help="most voices removed per groove (default: infill_min)")
     p.add_argument("--infill_prob", default=None, type=str,
                    help="comma list of integer weights, one per size infill_min..infill_max: the weight of EACH combination of that size (default all 1)")
+    # per-voice hit thresholds from the threshold curves of the validation set (gt_hit_curve / gt_hit_thresholds).  Also YAML keys; off by default
+    p.add_argument("--calibrate_thresholds", default="off", choices=["off", "f_beta", "density"],
+                   help="on the evaluation epochs, rank 0 calibrates a hit threshold per voice on Validation_Set (Train_Set when that is "
+                        "disabled): f_beta = the best F-beta, density = as many hits as the ground truth; adds hit precision / recall / F1 at "
+                        "those thresholds to each set's record, writes voice_thresholds_Epoch_<n>.json, and checkpoints carry the thresholds")
+    p.add_argument("--calibrate_beta", default=1.0, type=float, help="the beta of --calibrate_thresholds f_beta (and of the reported F score)")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible weight gradients (gt_set_deterministic: no token split in the weight-gradient kernels; +9-30 %% step time)")
     return p
@@ -135,6 +141,16 @@ def load_hyperparameters(args):
     for k in ("focal_gamma", "vo_penalty"):
         v = hp.get(k, getattr(args, k))
         hp[k] = None if v is None else float(v)
+    # threshold calibration, the same way (only where set: with it off the printed / logged hyper-parameters are the reference's)
+    cal = str(hp.get("calibrate_thresholds", args.calibrate_thresholds) or "off").lower()
+    if cal not in ("off", "false", "f_beta", "density"):
+        raise SystemExit("calibrate_thresholds must be off, f_beta or density, got %r" % cal)
+    hp.pop("calibrate_thresholds", None)
+    cal_beta = float(hp.pop("calibrate_beta", args.calibrate_beta))
+    if cal in ("f_beta", "density"):
+        if not (0.0 < cal_beta < float("inf")):
+            raise SystemExit("calibrate_beta must be > 0 and finite, got %r" % cal_beta)
+        hp["calibrate_thresholds"], hp["calibrate_beta"] = cal, cal_beta
     # infilling from full grooves, the same way
     hp["infill_npz"] = hp.get("infill_npz", args.infill_npz)
     hp["infill"] = infill_setup(hp, args)
@@ -371,8 +387,22 @@ def main(argv=None):
             # the evaluation leg (ref:train.py:219-250 -> log_eval, ref:evaluator.py:516-525) on the epochs of the save schedule:
             # predict each enabled set on the device, per-voice metrics on the device, one 30-float copy per set
             if ep in part or ep in full:
+                cal = hp.get("calibrate_thresholds")
+                cal_set = next((s for s in ("Validation_Set", "Train_Set") if s in eval_sets), None)
+                if cal and cal_set:
+                    # thresholds per voice from the threshold curves of the validation set (counted on the device, one copy of the counts);
+                    # they stay on the model: the checkpoints written from here on carry them
+                    import json
+                    res = model.calibrate_thresholds(*eval_sets[cal_set], criterion=cal, beta=hp["calibrate_beta"])
+                    print("  calibrated hit thresholds (%s on %s): %s" % (cal, cal_set, " ".join("%.2f" % t for t in res["thresholds"])))
+                    with open(os.path.join(save_dir, "voice_thresholds_Epoch_%d.json" % ep), "w") as f:
+                        json.dump({"epoch": ep, "criterion": cal, "beta": hp["calibrate_beta"], "set": cal_set, "voices": list(metrics.VOICES),
+                                   "thresholds": res["thresholds"], "index": res["index"],
+                                   **{k: res[k] for k in ("precision", "recall", "f_beta", "density_ratio")}}, f)
                 for name, (xin, gt) in eval_sets.items():
                     sc = metrics.evaluate(model, xin, gt)
+                    if cal and cal_set:
+                        sc.update(metrics.hit_scores(model, xin, gt, voice_thresholds="calibrated", beta=hp["calibrate_beta"]))
                     rec = {"%s/%s" % (name, k): v for k, v in sc.items()}
                     model.eval_log.append(dict(rec, epoch=ep))
                     print("  %s: hits accuracy %.4f  velocity MSE %.5f  offset MSE %.5f" %

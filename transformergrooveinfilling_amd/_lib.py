@@ -48,6 +48,15 @@ class GtVoiceSampling(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("mask_vo", ctypes.c_int32)]
 
 
+class GtThresholdRule(ctypes.Structure):
+    """gt_threshold_rule: how gt_hit_thresholds picks a voice's threshold from its curve"""
+    _fields_ = [("criterion", ctypes.c_int32), ("beta", ctypes.c_float), ("fallback", ctypes.c_float)]
+
+
+CURVE_MAX_THRES = 127            # GT_CURVE_MAX_THRES
+CRITERIA = {"f_beta": 0, "density": 1}
+
+
 class GtLossOpts(ctypes.Structure):
     """gt_loss_opts: host memory, read when gt_loss_ex / gt_train_step_loss is enqueued"""
     _fields_ = [("penalty_h", ctypes.c_float), ("penalty_vo", ctypes.c_float), ("pos_weight", ctypes.c_float * GT_VOICES),
@@ -100,6 +109,13 @@ _SIGS = {
     "gt_voice_metrics_scratch_floats": (ctypes.c_int64, [ctypes.c_int64]),
     # hvo_pred, hvo_gt, n_rows, out30, scratch, stream
     "gt_voice_metrics": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    "gt_hit_curve_scratch_words": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    # prob, prob_stride, hvo_gt, n_rows, thres (host), n_thres, counts, scratch, stream
+    "gt_hit_curve": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_int32, _vp, _vp, _vp]),
+    # counts_host, thres, n_thres, rule, thres_out, index_out, scores_out -- all host memory
+    "gt_hit_thresholds": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float), ctypes.c_int32,
+                                         ctypes.POINTER(GtThresholdRule), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_float)]),
     # xs, ys, idx, n_seq, batch, src_dim, x, y, stream
     "gt_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     # hvo_set, idx, n_seq, batch, io, state, x, y, removed, stream
@@ -186,6 +202,20 @@ class GrooveLib:
         if n < 1:
             raise GrooveLibError("gt_grad_buckets failed: %s" % self.cdll.gt_last_error().decode())
         return [(off[i], cnt[i]) for i in range(n)]
+
+    def hit_thresholds(self, counts, grid, criterion=0, beta=1.0, fallback=0.5):
+        """gt_hit_thresholds on a HOST copy of gt_hit_curve's counts ((9, 2, K + 1) integers, any array-like) over `grid` (K floats)
+        -> (thresholds [9], index [9], scores [9][4] = precision, recall, F-beta, density ratio)."""
+        grid = [float(t) for t in grid]
+        k = len(grid)
+        flat = [int(v) for v in (counts.reshape(-1).tolist() if hasattr(counts, "reshape") else counts)]
+        if len(flat) != GT_VOICES * 2 * (k + 1):
+            raise ValueError("counts must hold 9 x 2 x %d integers, got %d" % (k + 1, len(flat)))
+        cnt = (ctypes.c_uint64 * len(flat))(*flat)
+        rule = GtThresholdRule(int(criterion), float(beta), float(fallback))
+        th, idx, sc = (ctypes.c_float * GT_VOICES)(), (ctypes.c_int32 * GT_VOICES)(), (ctypes.c_float * (4 * GT_VOICES))()
+        self.call("gt_hit_thresholds", cnt, (ctypes.c_float * max(k, 1))(*grid), k, ctypes.byref(rule), th, idx, sc)
+        return list(th), list(idx), [list(sc[4 * c:4 * c + 4]) for c in range(GT_VOICES)]
 
     def ws_find(self, cfg, name, layer=0):
         o, c = ctypes.c_int64(), ctypes.c_int64()

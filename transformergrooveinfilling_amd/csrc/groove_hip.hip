@@ -19,6 +19,7 @@
 
 #include "gt_attn.h"
 #include "gt_common.h"
+#include "gt_curve.h"
 #include "gt_gemm.h"
 #include "gt_misc.h"
 #include "gt_seq_api.h"
@@ -2033,6 +2034,58 @@ extern "C" int gt_voice_metrics(const float* hvo_pred, const float* hvo_gt, int6
   gt_launch(voice_metrics_partial_kernel, dim3(nwg), dim3(256), s, hvo_pred, hvo_gt, scratch, M);
   gt_launch(voice_metrics_final_kernel, dim3(1), dim3(64), s, (const float*)scratch, out30, nwg, M);
   return launch_status("gt_voice_metrics");
+}
+// Threshold curves (gt_curve.h): the counting pass as two launches, the choice as a pure host function.  The grid is read from the host
+// array here and baked into the launch, as gt_predict_voices' thresholds are.
+extern "C" int64_t gt_hit_curve_scratch_words(int64_t n_rows, int32_t n_thres) {
+  if (n_rows <= 0 || n_rows >= (1ll << 31) || n_thres < 1 || n_thres > GT_CURVE_MAX_THRES) return 0;
+  return (int64_t)gt_curve_wgs(n_rows) * GT_CURVE_CLASSES * (n_thres + 1);
+}
+extern "C" int gt_hit_curve(const float* prob, int32_t prob_stride, const float* hvo_gt, int64_t n_rows, const float* thres, int32_t n_thres,
+                            uint64_t* counts, uint32_t* scratch, gt_stream_t stream) {
+  if (!prob || !hvo_gt || !thres || !counts || !scratch) return gt_fail("gt_hit_curve: pointers must not be NULL");
+  if (n_rows <= 0 || n_rows >= (1ll << 31)) return gt_fail("gt_hit_curve: n_rows %lld out of range", (long long)n_rows);
+  if (prob_stride != GT_VOICES && prob_stride != GT_TGT)
+    return gt_fail("gt_hit_curve: prob_stride %d (9 = a prob_out buffer, 27 = the hit columns of an HVO buffer)", (int)prob_stride);
+  if (const char* e = gt_curve_grid_error(thres, n_thres)) return gt_fail("gt_hit_curve: %s (n_thres %d)", e, (int)n_thres);
+  CurveGrid g;
+  for (int k = 0; k <= GT_CURVE_PAD; ++k) g.t[k] = k < n_thres ? thres[k] : __builtin_inff();
+  const int nb = n_thres + 1, keys = GT_CURVE_CLASSES * nb, nwg = gt_curve_wgs(n_rows);
+  hipStream_t s = (hipStream_t)stream;
+  gt_prof_tag("hit_curve", 0.0, (double)n_rows * GT_VOICES * 8.0);
+  gt_launch(hit_curve_partial_kernel, dim3(nwg), dim3(GT_CURVE_THREADS), s, prob, (int)prob_stride, hvo_gt, n_rows, g, nb, (unsigned*)scratch);
+  gt_prof_tag("hit_curve_sum", 0.0, (double)nwg * keys * 4.0 + keys * 16.0);
+  gt_launch(hit_curve_sum_kernel, dim3((keys + GT_CURVE_THREADS - 1) / GT_CURVE_THREADS), dim3(GT_CURVE_THREADS), s, (const unsigned*)scratch, nwg,
+            keys, counts);
+  return launch_status("gt_hit_curve");
+}
+extern "C" int gt_hit_thresholds(const uint64_t* counts_host, const float* thres, int32_t n_thres, const gt_threshold_rule* rule,
+                                 float* thres_out, int32_t* index_out, float* scores_out) {
+  if (!counts_host || !thres || !rule || !thres_out || !index_out || !scores_out) return gt_fail("gt_hit_thresholds: pointers must not be NULL");
+  if (const char* e = gt_curve_grid_error(thres, n_thres)) return gt_fail("gt_hit_thresholds: %s (n_thres %d)", e, (int)n_thres);
+  if (rule->criterion != 0 && rule->criterion != 1) return gt_fail("gt_hit_thresholds: criterion %d (0 = F-beta, 1 = density)", (int)rule->criterion);
+  if (rule->criterion == 0 && (!(rule->beta > 0.f) || __builtin_isinf(rule->beta)))
+    return gt_fail("gt_hit_thresholds: beta %g must be > 0 and finite", (double)rule->beta);
+  if (!(rule->fallback >= 0.f && rule->fallback <= 1.f)) return gt_fail("gt_hit_thresholds: fallback %g outside [0, 1]", (double)rule->fallback);
+  const double b2 = (double)rule->beta * (double)rule->beta;
+  const bool beta_ok = rule->beta > 0.f && !__builtin_isinf(rule->beta);      // (criterion 1 does not need one: its F-beta column is then 0)
+  for (int c = 0; c < GT_VOICES; ++c) {
+    uint64_t tp = 0, fp = 0, P = 0;
+    const int k = gt_curve_choose(counts_host + (size_t)c * 2 * (n_thres + 1), n_thres, rule->criterion, b2, &tp, &fp, &P);
+    float* sc = scores_out + 4 * c;
+    index_out[c] = k;
+    if (k < 0) {
+      thres_out[c] = rule->fallback;
+      sc[0] = sc[1] = sc[2] = sc[3] = 0.f;
+      continue;
+    }
+    thres_out[c] = thres[k];
+    sc[0] = tp + fp ? (float)((double)tp / (double)(tp + fp)) : 0.f;
+    sc[1] = (float)((double)tp / (double)P);
+    sc[2] = beta_ok ? (float)gt_curve_fbeta(b2, tp, P - tp, fp) : 0.f;
+    sc[3] = (float)((double)(tp + fp) / (double)P);
+  }
+  return 0;
 }
 extern "C" int gt_gather_batch(const float* xs, const float* ys, const int64_t* idx, int64_t n_seq, int32_t batch, int32_t src_dim,
                                float* x, float* y, gt_stream_t stream) {

@@ -177,6 +177,8 @@ class StepEngine:
         self._predict_ws = {}          # chunk size -> (cfg, workspace, tgt scratch) of predict()
         self._predict_prob = {}        # chunk size -> (m,32,9) probabilities of gt_predict_voices; lives as long as that chunk's workspace
         self._predict_epoch = None     # gt_layout_epoch() those were sized at
+        self._curve_buf = {}           # chunk size -> (HVO output, gt_hit_curve scratch) of hit_curve(); lives as long as that chunk's workspace
+        self.voice_thresholds = None   # the nine thresholds of the last calibration (predict(voice_thresholds="calibrated"))
         # gt_config.flags of every configuration this engine hands to the library (per ENGINE, not per process: train.py's evaluation engines and
         # bench.py's second engine keep their own).  _flags_fallback: set for good once an in-launch exchange timed out (no QUAD, no row exchange);
         # _flags_recipe: what the data-parallel recipe in force asks for (bucketed overlap: no row exchange beside a collective's workgroups)
@@ -924,7 +926,9 @@ class StepEngine:
     def predict(self, x, use_thres=True, thres=0.5, chunk=None, pd_seed=None, voice_thresholds=None, voice_max_count=None, temperature=1.0,
                 mask_vo=False):
         """voice_thresholds / voice_max_count / temperature / mask_vo: the per-voice controls of gt_predict_voices (include/groove_hip.h);
-        with all four at their defaults the call sequence is that of gt_predict / gt_predict_pd_at."""
+        with all four at their defaults the call sequence is that of gt_predict / gt_predict_pd_at.  voice_thresholds="calibrated": the
+        nine thresholds the last calibrate_thresholds stored (ValueError when there are none)."""
+        voice_thresholds = self._calibrated(voice_thresholds)
         vs = self.voice_sampling(use_thres, thres, pd_seed, voice_thresholds, voice_max_count, temperature, mask_vo)
         out = self._predict(x, use_thres, thres, chunk, pd_seed, vs)
         # a timed-out exchange inside the call (its own workspaces): noticed when the call ends, the call repeated on the exchange-free schedule
@@ -948,32 +952,16 @@ class StepEngine:
         of `chunk` sequences (default: predict_chunk) over one cached workspace (sized for a chunk, not for N)."""
         x = torch.as_tensor(x, dtype=torch.float32).to(self.device).contiguous()
         n = x.shape[0]
-        d = self.dims
         if chunk is None:
             chunk = self.predict_chunk(n)
         out = torch.empty(n, 32, 27, dtype=torch.float32, device=self.device)
         for i in range(0, n, chunk):
             m = min(chunk, n - i)
-            if self._predict_epoch != self.lib.cdll.gt_layout_epoch():      # (a layout switch changed: see slot())
-                self._predict_ws.clear()
-                self._predict_epoch = self.lib.cdll.gt_layout_epoch()
-            if m not in self._predict_ws:
-                if len(self._predict_ws) >= 2:             # the full chunk + one remainder size at most
-                    self._predict_ws.pop(next(k for k in self._predict_ws if k != chunk), None)
-                cfg = _lib.make_config(m, d["embedding_size_src"], d["d_model"], d["n_heads"], d["dim_feedforward"],
-                                       d["num_encoder_layers"], d["num_decoder_layers"], d["dropout"], d["precision"], self.cfg_flags)
-                ws = torch.empty(self.lib.workspace_floats(cfg), dtype=torch.float32, device=self.device)
-                self.lib.call("gt_workspace_init", ctypes.byref(cfg), _ptr(ws), self.stream)
-                tgt = torch.empty(m, 32, 27, dtype=torch.float32, device=self.device) if not self.encoder_only else None
-                self._predict_ws[m] = (cfg, ws, tgt)
-            cfg, ws, tgt = self._predict_ws[m]
+            cfg, ws, tgt = self._chunk_ws(m, chunk)
             if vs is not None:              # per-voice controls: the chunk's probabilities go to a buffer kept beside its workspace
-                self._predict_prob = {k: v for k, v in self._predict_prob.items() if k in self._predict_ws}
-                if m not in self._predict_prob:
-                    self._predict_prob[m] = torch.empty(m, 32, 9, dtype=torch.float32, device=self.device)
                 self.lib.call("gt_predict_voices", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(out[i:i + m]),
                               ctypes.byref(vs), ctypes.c_uint32(int(pd_seed or 0) & 0xFFFFFFFF), ctypes.c_int64(i),
-                              _ptr(self._predict_prob[m]), _ptr(tgt), _ptr(ws), self.stream)
+                              _ptr(self._chunk_prob(m)), _ptr(tgt), _ptr(ws), self.stream)
                 continue
             if pd_seed is not None:         # use_pd: hits sampled from the probabilities, hashed from the element's index in the WHOLE set
                 self.lib.call("gt_predict_pd_at", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(out[i:i + m]),
@@ -982,6 +970,113 @@ class StepEngine:
             self.lib.call("gt_predict", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(out[i:i + m]),
                           ctypes.c_float(thres), int(use_thres), _ptr(tgt), _ptr(ws), self.stream)
         return out
+
+    def _chunk_ws(self, m, chunk):
+        """(cfg, workspace, tgt scratch) of a predict call over m sequences, cached in _predict_ws: the full chunk + one remainder size at most"""
+        d = self.dims
+        if self._predict_epoch != self.lib.cdll.gt_layout_epoch():      # (a layout switch changed: see slot())
+            self._predict_ws.clear()
+            self._predict_epoch = self.lib.cdll.gt_layout_epoch()
+        if m not in self._predict_ws:
+            if len(self._predict_ws) >= 2:
+                self._predict_ws.pop(next(k for k in self._predict_ws if k != chunk), None)
+            cfg = _lib.make_config(m, d["embedding_size_src"], d["d_model"], d["n_heads"], d["dim_feedforward"],
+                                   d["num_encoder_layers"], d["num_decoder_layers"], d["dropout"], d["precision"], self.cfg_flags)
+            ws = torch.empty(self.lib.workspace_floats(cfg), dtype=torch.float32, device=self.device)
+            self.lib.call("gt_workspace_init", ctypes.byref(cfg), _ptr(ws), self.stream)
+            tgt = torch.empty(m, 32, 27, dtype=torch.float32, device=self.device) if not self.encoder_only else None
+            self._predict_ws[m] = (cfg, ws, tgt)
+        return self._predict_ws[m]
+
+    def _chunk_prob(self, m):
+        """the (m,32,9) probability buffer kept beside the workspace of chunk size m"""
+        self._predict_prob = {k: v for k, v in self._predict_prob.items() if k in self._predict_ws}
+        if m not in self._predict_prob:
+            self._predict_prob[m] = torch.empty(m, 32, 9, dtype=torch.float32, device=self.device)
+        return self._predict_prob[m]
+
+    def _calibrated(self, voice_thresholds):
+        """voice_thresholds="calibrated": the nine thresholds calibrate_thresholds stored on this engine"""
+        if isinstance(voice_thresholds, str):
+            if voice_thresholds != "calibrated":
+                raise ValueError("voice_thresholds must be 9 values or \"calibrated\", got %r" % (voice_thresholds,))
+            if self.voice_thresholds is None:
+                raise ValueError("voice_thresholds=\"calibrated\" needs thresholds: run calibrate_thresholds first (or load a checkpoint that carries them)")
+            return list(self.voice_thresholds)
+        return voice_thresholds
+
+    DEFAULT_CURVE_GRID = tuple(float(np.float32(k) / np.float32(100)) for k in range(1, 100))
+
+    def hit_curve(self, x, gt_hvo, grid=None, temperature=1.0, voice_thresholds=None, chunk=None, counts=None):
+        """Per-voice threshold curves of a whole set on the device (gt_hit_curve; include/groove_hip.h): for each voice and class (the ground
+        truth is a hit / is not), how many predicted probabilities fall into each bin of `grid` (K ascending thresholds in [0,1]; default
+        float32(k) / float32(100), k = 1..99) -> device int64 tensor (9, 2, K + 1).  The set is walked in predict's chunks over predict's
+        cached workspaces; nothing is copied to the host per chunk.  counts: an earlier result over the same grid to continue (it is
+        added to in place; counts of disjoint shards add, which is all a data-parallel evaluation needs).
+        Encoder-only at temperature 1: gt_predict(use_thres = 0) per chunk, its hit columns read in place; otherwise gt_predict_voices and
+        its prob_out.  Encoder-decoder: the probabilities are those ALONG THE GREEDY DECODE at the starting thresholds (voice_thresholds,
+        default 0.5) -- the decode feeds decided hits back, so another threshold would have met other probabilities from its first
+        differing step on; the curve approximates what a changed threshold does."""
+        x = torch.as_tensor(x, dtype=torch.float32).to(self.device).contiguous()
+        gt = torch.as_tensor(gt_hvo, dtype=torch.float32).to(self.device).contiguous()
+        n = x.shape[0]
+        if n < 1 or gt.numel() != n * 32 * 27:
+            raise ValueError("hit_curve needs x (N,32,S) and gt_hvo (N,32,27) with N >= 1, got %s / %s" % (tuple(x.shape), tuple(gt.shape)))
+        grid = [float(np.float32(t)) for t in (self.DEFAULT_CURVE_GRID if grid is None else grid)]
+        k = len(grid)
+        if not 1 <= k <= _lib.CURVE_MAX_THRES or not all(0.0 <= t <= 1.0 for t in grid) or any(b <= a for a, b in zip(grid, grid[1:])):
+            raise ValueError("grid: 1..%d strictly ascending thresholds in [0, 1], got %r" % (_lib.CURVE_MAX_THRES, grid))
+        plain = self.encoder_only and float(temperature) == 1.0
+        vs = None
+        if not plain:
+            th = self._calibrated(voice_thresholds)
+            vs = self.voice_sampling(True, 0.5, None, [0.5] * 9 if th is None else th, None, temperature, False)
+        if counts is None:
+            counts = torch.zeros(9, 2, k + 1, dtype=torch.int64, device=self.device)
+        elif tuple(counts.shape) != (9, 2, k + 1) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != x.device:
+            raise ValueError("counts must be a contiguous int64 tensor (9, 2, %d) on %s" % (k + 1, self.device))
+        if chunk is None:
+            chunk = self.predict_chunk(n)
+        cgrid = (ctypes.c_float * k)(*grid)
+        before = counts.clone()
+
+        def walk():
+            for i in range(0, n, chunk):
+                m = min(chunk, n - i)
+                cfg, ws, tgt = self._chunk_ws(m, chunk)
+                if m not in self._curve_buf:
+                    self._curve_buf = {q: v for q, v in self._curve_buf.items() if q in self._predict_ws}
+                    words = int(self.lib.cdll.gt_hit_curve_scratch_words(ctypes.c_int64(m * 32), _lib.CURVE_MAX_THRES))
+                    self._curve_buf[m] = (torch.empty(m, 32, 27, dtype=torch.float32, device=self.device),
+                                          torch.empty(words, dtype=torch.int32, device=self.device))
+                hvo, scratch = self._curve_buf[m]
+                if plain:
+                    self.lib.call("gt_predict", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(hvo),
+                                  ctypes.c_float(0.5), 0, _ptr(tgt), _ptr(ws), self.stream)
+                    prob, stride = hvo, 27
+                else:
+                    prob, stride = self._chunk_prob(m), 9
+                    self.lib.call("gt_predict_voices", ctypes.byref(cfg), _ptr(self.params), _ptr(self.pe), _ptr(x[i:i + m]), _ptr(hvo),
+                                  ctypes.byref(vs), ctypes.c_uint32(0), ctypes.c_int64(i), _ptr(prob), _ptr(tgt), _ptr(ws), self.stream)
+                self.lib.call("gt_hit_curve", _ptr(prob), stride, _ptr(gt[i:i + m]), ctypes.c_int64(m * 32), cgrid, k, _ptr(counts),
+                              _ptr(scratch), self.stream)
+
+        walk()
+        # a timed-out exchange inside the walk: as in predict, noticed when the walk ends; the counts go back to what they were and the
+        # walk is repeated on the exchange-free schedule
+        bad = [(cfg, ws) for cfg, ws, _ in self._predict_ws.values()
+               if self._xchg_word(ws, cfg) is not None and int(self._xchg_word(ws, cfg)[0].item()) != 0]
+        if bad:
+            for cfg, ws in bad:
+                self.lib.call("gt_workspace_init", ctypes.byref(cfg), _ptr(ws), self.stream)
+
+            def again():
+                counts.copy_(before)
+                walk()
+            self._local_retry(None, None, "hit_curve", again)
+        self._trim_predict_ws()
+        self._curve_buf = {q: v for q, v in self._curve_buf.items() if q in self._predict_ws}
+        return counts
 
     def _trim_predict_ws(self):
         for m in [k for k, (_, ws, _) in self._predict_ws.items() if 4 * ws.numel() > PREDICT_WS_KEEP]:

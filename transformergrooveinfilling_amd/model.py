@@ -17,7 +17,7 @@ import weakref
 import torch
 from torch import nn
 
-from . import layout
+from . import _lib, layout
 from .engine import StepEngine
 
 
@@ -171,7 +171,8 @@ class _GrooveBase(nn.Module):
         Per-voice controls (gt_predict_voices): voice_thresholds -- 9 values in [0,1] that override thres (with use_pd: a floor under the
         sampled hits, 0 when not given); voice_max_count -- 9 caps in 0..32 on a voice's hits per sequence, the most probable stay and of
         equal probabilities the earlier step; temperature -- p = sigmoid(logit / temperature); mask_vo -- velocity and offset are 0
-        wherever the final hit is 0.  They need decided hits: with use_thres=False (and no use_pd) they raise ValueError."""
+        wherever the final hit is 0.  They need decided hits: with use_thres=False (and no use_pd) they raise ValueError.
+        voice_thresholds="calibrated": the thresholds calibrate_thresholds stored (ValueError before any calibration)."""
         self.eval()
         n = self.embedding_size_tgt // 3
         voices = dict(voice_thresholds=voice_thresholds, voice_max_count=voice_max_count, temperature=temperature, mask_vo=mask_vo)
@@ -192,6 +193,38 @@ class _GrooveBase(nn.Module):
             return self.engine.predict(src, use_thres=use_thres, thres=thres, voice_thresholds=voice_thresholds,
                                        voice_max_count=voice_max_count, temperature=temperature, mask_vo=mask_vo)
 
+    # the nine thresholds of the last calibration live on the engine (engine.predict(voice_thresholds="calibrated") reads them there)
+    voice_thresholds = property(lambda self: self.engine.voice_thresholds,
+                                lambda self, v: setattr(self.engine, "voice_thresholds", None if v is None else [float(t) for t in v]))
+
+    def calibrate_thresholds(self, src, gt_hvo, criterion="f_beta", beta=1.0, grid=None, temperature=1.0, fallback=0.5, rounds=1):
+        """Pick a hit threshold per voice from the threshold curves of an evaluation set: the curves are counted on the device
+        (engine.hit_curve), ONE copy of the (9, 2, K + 1) counts comes to the host, gt_hit_thresholds chooses.  criterion "f_beta": the
+        threshold of the best F-beta; "density": the threshold at which the voice places as many hits as the ground truth has.  A voice the
+        rule cannot decide (no true hit; F-beta 0 everywhere) gets `fallback`.  The nine thresholds are stored as model.voice_thresholds:
+        predict(voice_thresholds="calibrated") uses them, checkpoints carry them.
+        Encoder-decoder: the curve holds the probabilities met along the greedy decode at the starting thresholds (0.5), which feeds decided
+        hits back -- an approximation of what other thresholds would meet; rounds=2 repeats the calibration from the thresholds of round 1.
+        -> {"thresholds": [9], "index": [9], "precision" | "recall" | "f_beta" | "density_ratio": {voice: float}, "counts": numpy (9, 2, K + 1)}"""
+        from .metrics import VOICES
+        if criterion not in _lib.CRITERIA:
+            raise ValueError("criterion must be one of %s, got %r" % (sorted(_lib.CRITERIA), criterion))
+        if int(rounds) < 1:
+            raise ValueError("rounds must be >= 1, got %r" % (rounds,))
+        eng = self.engine
+        grid = [float(t) for t in (eng.DEFAULT_CURVE_GRID if grid is None else grid)]
+        self.eval()
+        start = None
+        for _ in range(int(rounds)):
+            with torch.no_grad():
+                counts = eng.hit_curve(src, gt_hvo, grid=grid, temperature=temperature, voice_thresholds=start).cpu().numpy()
+            th, idx, sc = eng.lib.hit_thresholds(counts, grid, _lib.CRITERIA[criterion], beta, fallback)
+            start = th
+        self.voice_thresholds = th
+        out = {"thresholds": list(self.voice_thresholds), "index": idx, "counts": counts}
+        for j, name in enumerate(("precision", "recall", "f_beta", "density_ratio")):
+            out[name] = {v: sc[c][j] for c, v in enumerate(VOICES)}
+        return out
 
     def infill(self, hvo_in, removed=None, mode=1, **predict_kwargs):
         """The finished groove on the device: predict on the symbolic input hvo_in (N,32,27) -- a groove with voices removed --, then put

@@ -169,6 +169,9 @@ def save_checkpoint(path, epoch, model, optimizer, loss):
     eng = getattr(model, "engine", None)
     if eng is not None and osd.get("param_groups"):
         osd["param_groups"][0]["dropout_step"] = max(int(eng.state_struct().step), int(getattr(model, "_train_forwards", 0)))
+        # calibrated hit thresholds (model.calibrate_thresholds) ride beside it; a model without them writes no such key
+        if getattr(model, "voice_thresholds", None) is not None:
+            osd["param_groups"][0]["voice_thresholds"] = [float(t) for t in model.voice_thresholds]
     torch.save({"epoch": epoch, "model_state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                 "optimizer_state_dict": osd, "loss": float(loss)}, path)
     return path
@@ -244,6 +247,8 @@ def initialize_model(params):
         step = int(groups[0].get("dropout_step", initial_epoch << 20)) & 0x7FFFFFFF
         model.engine.set_state(step=step)
         model._train_forwards = step
+        if groups[0].get("voice_thresholds") is not None:
+            model.voice_thresholds = groups[0]["voice_thresholds"]
     return model, optimizer, initial_epoch
 
 
