@@ -61,7 +61,7 @@ class Runner:
 
     def __init__(self, cfg, B, backend="emu", rng=(1234, 99, 0), lr=0.094, seq=True, flags=0):
         self.cfgd, self.B, self.backend = cfg, B, backend
-        self.lib = emu_lib() if backend == "emu" else _lib.get_lib()
+        self.lib = ledgered(emu_lib() if backend == "emu" else _lib.get_lib())
         self.lib.cdll.gt_set_seq(int(bool(seq)))  # process-global switch: sequence-resident kernels (default where supported)
         # seq = "split" / "whole": force / forbid their two-workgroups-per-sequence mode (d_model 128); True: the library's choice
         self.lib.cdll.gt_set_seq_split(1 if seq in ("split", "split-noride", "split-noquad") else 0 if seq == "whole" else -1)
@@ -283,6 +283,7 @@ def trace_dispatch(fn):
                 sys.stderr.write(rest)
     trace = parse_dispatch(text)
     assert trace, "no [dispatch] line: the trace is off"
+    ledger_append(trace)
     return out, trace
 
 
@@ -290,3 +291,69 @@ def dispatched(trace, family, **kv):
     """the trace's lines of `family` (a name or a tuple of names) whose keys have the given values"""
     fams = (family,) if isinstance(family, str) else family
     return [d for f, d in trace if f in fams and all(d.get(k) == v for k, v in kv.items())]
+
+
+# ---- GT_VARIANT_LEDGER=<file> (tests/variant_ledger.py; DESIGN.md 4a "Variant ledger"): every launch a Runner or trace_dispatch makes is
+# appended to <file> as "signature <tab> $PYTEST_CURRENT_TEST".  Unset (the default): Runner.lib is the library itself, nothing is redirected
+# and no variable is touched. ------------------------------------------------------------------------------------------------------------
+def ledger_append(trace):
+    """the distinct signatures of a parsed trace, one short O_APPEND write each (parallel workers may share the file)"""
+    path = os.environ.get("GT_VARIANT_LEDGER")
+    if not path:
+        return
+    from variant_ledger import signatures
+    test = os.environ.get("PYTEST_CURRENT_TEST", "")
+    fd = os.open(path, os.O_WRONLY | os.O_APPEND | os.O_CREAT, 0o644)
+    try:
+        for sig in sorted(set(signatures(trace))):
+            os.write(fd, ("%s\t%s\n" % (sig, test)).encode())
+    finally:
+        os.close(fd)
+
+
+def ledger_call(fn):
+    """fn() under GT_TRACE_DISPATCH=1 with file descriptor 2 in a temporary file, as trace_dispatch runs it; its launches go to the ledger.
+    What arrived on stderr is passed on to file descriptor 2 afterwards -- the [dispatch] lines only where the caller had the trace on
+    already (a capfd test, or an enclosing trace_dispatch, reads them there)."""
+    import tempfile
+    sys.stderr.flush()
+    saved = os.dup(2)
+    old = os.environ.get("GT_TRACE_DISPATCH")
+    text = ""
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        os.dup2(tmp.fileno(), 2)
+        os.environ["GT_TRACE_DISPATCH"] = "1"
+        try:
+            return fn()
+        finally:
+            if old is None:
+                del os.environ["GT_TRACE_DISPATCH"]
+            else:
+                os.environ["GT_TRACE_DISPATCH"] = old
+            sys.stderr.flush()
+            os.dup2(saved, 2)
+            os.close(saved)
+            tmp.seek(0)
+            text = tmp.read().decode(errors="replace")
+            keep = old is not None and old[:1] == "1"
+            rest = "".join(ln + "\n" for ln in text.splitlines() if keep or not ln.startswith("[dispatch] "))
+            if rest:
+                os.write(2, rest.encode())
+            ledger_append(parse_dispatch(text))
+
+
+class LedgeredLib:
+    """GrooveLib with call() -- the one place through which Runner reaches an entry point that launches -- run under ledger_call"""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+    def call(self, name, *args):
+        ledger_call(lambda: self._lib.call(name, *args))
+
+
+def ledgered(lib):
+    return LedgeredLib(lib) if os.environ.get("GT_VARIANT_LEDGER") else lib

@@ -7,6 +7,7 @@ order: a change of host code that is meant to move no launch is checked by compa
 
     python tools/dispatch_trace.py --dry [--digest] > trace.txt     # emulator build, GT_EMU_DRY=1: no kernel body runs (no GPU needed)
     python tools/dispatch_trace.py > trace.txt                      # the HIP library (GT_LIB_PATH: another build) on the current device
+    python tools/dispatch_trace.py --dry --grid > grid.txt          # the sweep grid (grid_groups) in full: tests/variant_ledger.py's universe
 
 --dry assumes the emulator's 256 CUs; the numbers left in the buffers are garbage either way (nothing here reads them).  A block that
 repeats an earlier block line for line, of whichever shape, is printed as "= <that block's marker>".  --digest prints one line per shape
@@ -75,6 +76,30 @@ def groups(cus):
     g["exchange"] = ({}, None, [case(sh, B, ln_xchg=v) for sh, B in BASELINE for v in (-1, 0, 1)] +
                      [case(sh, B, flags=FALLBACK) for sh, B in BASELINE])
     g["GT_SEQ=0"] = ({"GT_SEQ": "0"}, None, [case(sh, B) for sh, B in BASELINE + YAMLS])
+    return g
+
+
+GRID_D = (16, 32, 64, 128, 256, 512)
+GRID_H = (1, 2, 4, 8, 16)
+GRID_F = (16, 64, 256, 512, 2048)
+GRID_B = (16, 32, 64, 128, 256, 512)
+
+
+def grid_groups():
+    """The reference's sweep grid for tests/variant_ledger.py's universe(), one group per d_model (--grid runs them side by
+    side): d_model x heads x dim_feedforward x batch, encoder-only (2+0) and encoder-decoder (2+2), precision 1 / 2 at dim_feedforward >= 512
+    and batch 64 / 512, and per model (d_model, heads, dim_feedforward, layers) one point each of S 27 and of the time-out fall-back flags,
+    both at batch 64.  gt_set_seq(1), what tests/harness.py's Runner sets; "grid-seq0" is gt_set_seq(0) at batch 64 of every model.
+    Same form: name -> (environment, gt_set_seq argument, cases).  A dry run assumes 256 CUs (an MI355X's count): the batch boundaries of
+    the sequence-resident schedules are where that count puts them."""
+    g = {}
+    models = lambda d: [shape(d, H, F, 2, Ld) for H in GRID_H if d % H == 0 for F in GRID_F for Ld in (0, 2)]
+    for d in GRID_D:
+        c = [case(sh, B) for sh in models(d) for B in GRID_B]
+        c += [case(sh, B, precision=p) for sh in models(d) if sh["F"] >= 512 for B in (64, 512) for p in (1, 2)]
+        c += [case(dict(sh, S=27), 64) for sh in models(d)] + [case(sh, 64, flags=FALLBACK) for sh in models(d)]
+        g["grid-d%d" % d] = ({}, 1, c)
+    g["grid-seq0"] = ({}, 0, [case(sh, 64) for d in GRID_D for sh in models(d)])
     return g
 
 
@@ -210,7 +235,7 @@ def run_group(name, dry):
     else:
         import torch
         lib, cus = _lib.get_lib(), torch.cuda.get_device_properties(0).multi_processor_count
-    _, seq, cases = groups(cus)[name]
+    _, seq, cases = (grid_groups() if name.startswith("grid-") else groups(cus))[name]
     if seq is not None:
         lib.cdll.gt_set_seq(seq)
     print("# group %s: CUs %d%s" % (name, cus, "" if seq is None else ", gt_set_seq(%d)" % seq))
@@ -219,14 +244,36 @@ def run_group(name, dry):
         drv.run_case(c)
 
 
+def run_grid(dry):
+    """every group of grid_groups(), each in a child process; dry: all of them at once (host code only, one CPU each)"""
+    e = dict(os.environ, GT_TRACE_DISPATCH="1", GT_TRACE_GEMM64="1", **({"GT_EMU_DRY": "1"} if dry else {}))
+    cmd = lambda name: [sys.executable, os.path.abspath(__file__), "--group", name] + (["--dry"] if dry else [])
+    names = list(grid_groups())
+    if not dry:
+        for name in names:
+            sys.stdout.write(subprocess.run(cmd(name), env=e, check=True, stdout=subprocess.PIPE, universal_newlines=True).stdout)
+        return
+    outs = [tempfile.TemporaryFile(mode="w+") for _ in names]
+    procs = [subprocess.Popen(cmd(name), env=e, stdout=f) for name, f in zip(names, outs)]
+    for name, pr, f in zip(names, procs, outs):
+        if pr.wait() != 0:
+            raise SystemExit("group %s: exit status %d" % (name, pr.returncode))
+        f.seek(0)
+        sys.stdout.write(f.read())
+        f.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dry", action="store_true", help="the emulator build with GT_EMU_DRY=1")
     ap.add_argument("--digest", action="store_true", help="one line per shape: line count and head of the sha256 of each form's block")
+    ap.add_argument("--grid", action="store_true", help="the sweep grid of grid_groups() instead of the groups above, every block in full")
     ap.add_argument("--group", help="(internal) run one group in this process")
     a = ap.parse_args()
     if a.group:
         return run_group(a.group, a.dry)
+    if a.grid:
+        return run_grid(a.dry)
     seen = {}
     for name, (env, _, _) in groups(256).items():
         e = dict(os.environ, GT_TRACE_DISPATCH="1", GT_TRACE_GEMM64="1", **env)
