@@ -46,6 +46,90 @@ class CudaBuf:
         return self.t.cpu().numpy()
 
 
+def _signed32(pattern):
+    return int(np.uint32(pattern).astype(np.int32))
+
+
+def _filled(Buf, n, pattern):
+    """n floats that all hold the 32-bit pattern, as a Buf (filled on the device for a CudaBuf: a workspace can be hundreds of megabytes)"""
+    if hasattr(Buf, "_adopt"):                       # a guarded class: the data between its red zones
+        b = Buf.__new__(Buf)
+        b._adopt(None, (n,), np.dtype(np.float32))
+    elif issubclass(Buf, CudaBuf):
+        import torch
+        b = Buf.__new__(Buf)
+        b.t = torch.empty(n, dtype=torch.float32, device="cuda")
+        b.ptr = ctypes.c_void_p(b.t.data_ptr())
+    else:
+        return Buf(np.full(n, pattern, np.uint32).view(np.float32))
+    if issubclass(Buf, CudaBuf):
+        import torch
+        b.t.view(torch.int32).fill_(_signed32(pattern))
+    else:
+        b.a.view(np.uint32)[:] = pattern
+    return b
+
+
+def redzone_floats(row_width):
+    """floats of ONE red zone of a guarded buffer: 128 rows (the tallest tile the library has) of the buffer's row width, at least 4096,
+    rounded up to a multiple of 64 floats -- 256 bytes, so the inner pointer keeps the alignment the allocator gave the whole block"""
+    return (max(128 * int(row_width), 4096) + 63) // 64 * 64
+
+
+def guarded(Buf, pattern, flat_width, registry):
+    """Buf (NpBuf / CudaBuf) whose memory is the INSIDE of a larger allocation: a red zone of redzone_floats(row width) floats on each side,
+    every word the 32-bit `pattern`.  Row width: the last dimension of a 2-D array, flat_width for anything else (a flat parameter, gradient
+    or workspace buffer: the widest row of a tensor inside it).  The upper zone starts at the first byte behind the data.  Every buffer made
+    is appended to `registry` as a weak reference; intact() compares both zones bit for bit."""
+    import weakref
+    on_device = issubclass(Buf, CudaBuf)
+    word = np.frombuffer(np.uint32(pattern).tobytes(), np.uint8)
+
+    class Guarded(Buf):
+        def __init__(self, arr):
+            a = np.ascontiguousarray(arr)
+            self._adopt(a, a.shape, a.dtype)
+
+        def _adopt(self, a, shape, dtype):
+            n = int(np.prod(shape)) * dtype.itemsize
+            assert n % 4 == 0, "a guarded buffer holds whole 32-bit words"
+            rz = 4 * redzone_floats(shape[-1] if len(shape) >= 2 else flat_width)
+            self._lo, self._n, self._rz = rz, n, rz
+            if on_device:
+                import torch
+                self.full = torch.empty(2 * rz + n, dtype=torch.uint8, device="cuda")
+                for z in (self.full[:rz], self.full[rz + n:]):
+                    z.view(torch.int32).fill_(_signed32(pattern))
+                inner = self.full[rz:rz + n]
+                if a is not None:
+                    inner.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8)))
+                self.t = inner.view({np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32,
+                                     np.dtype(np.int64): torch.int64, np.dtype(np.uint32): torch.int32}[dtype]).reshape(shape)
+                self.ptr = ctypes.c_void_p(self.t.data_ptr())
+            else:
+                self.full = np.empty(2 * rz + n, np.uint8)
+                self.full[:rz] = np.tile(word, rz // 4)
+                self.full[rz + n:] = np.tile(word, rz // 4)
+                if a is not None:
+                    self.full[rz:rz + n] = a.reshape(-1).view(np.uint8)
+                self.a = self.full[rz:rz + n].view(dtype).reshape(shape)
+                self.ptr = ctypes.c_void_p(self.a.ctypes.data)
+            registry.append(weakref.ref(self))
+
+        def intact(self):
+            rz, n = self._rz, self._n
+            if on_device:
+                import torch
+                torch.cuda.synchronize()
+                want = _signed32(pattern)
+                return bool((self.full[:rz].view(torch.int32) == want).all()) and bool((self.full[rz + n:].view(torch.int32) == want).all())
+            want = np.tile(word, rz // 4)
+            return np.array_equal(self.full[:rz], want) and np.array_equal(self.full[rz + n:], want)
+
+    Guarded.__name__ = "Guarded" + Buf.__name__
+    return Guarded
+
+
 def cfg_dict(d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_layers=0, embedding_size_src=16,
              dropout=0.0, precision=0):
     d = dict(d_model=d_model, n_heads=n_heads, dim_feedforward=dim_feedforward,
@@ -59,7 +143,10 @@ def cfg_dict(d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_
 class Runner:
     """One model instance behind the C ABI.  backend = 'emu' | 'hip'."""
 
-    def __init__(self, cfg, B, backend="emu", rng=(1234, 99, 0), lr=0.094, seq=True, flags=0):
+    def __init__(self, cfg, B, backend="emu", rng=(1234, 99, 0), lr=0.094, seq=True, flags=0, ws_fill=None, guard=None):
+        """ws_fill: the 32-bit pattern the workspace holds before gt_workspace_init (None: the float 7.25).  guard: a 32-bit pattern -- every
+        buffer this Runner hands to the library (self.Buf, also for buffers a test makes later) then lies between two red zones of that
+        pattern (guarded()); redzones_intact() names the buffers whose zones changed.  None: plain allocations."""
         self.cfgd, self.B, self.backend = cfg, B, backend
         self.lib = ledgered(emu_lib() if backend == "emu" else _lib.get_lib())
         self.lib.cdll.gt_set_seq(int(bool(seq)))  # process-global switch: sequence-resident kernels (default where supported)
@@ -72,6 +159,10 @@ class Runner:
         # the grouped dispatch at the end of backward
         self.lib.cdll.gt_set_seq_ride(0 if seq == "split-noride" else -1)
         self.Buf = NpBuf if backend == "emu" else CudaBuf
+        self._guarded = []
+        if guard is not None:                        # widest row of a tensor inside a flat buffer: a Linear's weight or an activation
+            width = max(3 * cfg["d_model"], cfg["dim_feedforward"], cfg["embedding_size_src"], 27)
+            self.Buf = guarded(self.Buf, guard, width, self._guarded)
         self.c = _lib.make_config(B, cfg["embedding_size_src"], cfg["d_model"], cfg["n_heads"], cfg["dim_feedforward"],
                                   cfg["num_encoder_layers"], cfg.get("num_decoder_layers", 0), cfg.get("dropout", 0.0),
                                   cfg.get("precision", 0), flags=flags)      # flags: gt_config.flags (_lib.CFG_NO_QUAD | _lib.CFG_NO_LN_XCHG)
@@ -82,7 +173,10 @@ class Runner:
         for (n, shp), (off, size, rows, cols) in zip(self.names, self.entries):
             assert int(np.prod(shp)) == size and shp[0] == rows, (n, shp, size, rows, cols)
         self.M = B * 32
-        self.ws = self.Buf(np.full(self.lib.workspace_floats(self.c), 7.25, np.float32))     # (garbage: gt_workspace_init zeroes what must be zero)
+        if ws_fill is None:
+            self.ws = self.Buf(np.full(self.lib.workspace_floats(self.c), 7.25, np.float32))     # (garbage: gt_workspace_init zeroes what must be zero)
+        else:
+            self.ws = _filled(self.Buf, self.lib.workspace_floats(self.c), ws_fill)
         self.lib.call("gt_workspace_init", ctypes.byref(self.c), self.ws.ptr, ctypes.c_void_p(0))
         self.pe = self.Buf(layout.positional_encoding(cfg["d_model"]))
         self.hvo = self.Buf(np.zeros((self.M, 27), np.float32))
@@ -95,6 +189,13 @@ class Runner:
         self.stream = ctypes.c_void_p(0)
         self.params = None
         self.d_hvo_from = None                       # whose self.d_hvo is: "loss" (gt_loss wrote it: self.y, self.loss_penalty) or "caller" (backward(d_hvo))
+
+    def redzones_intact(self):
+        """names of the live guarded buffers (the attribute that holds one, "buf#<k>" for the k-th made otherwise) whose red zones differ
+        from the guard pattern by even one bit; [] without a guard"""
+        names = {id(b): k for k, b in vars(self).items() if hasattr(b, "intact")}
+        live = [(i, ref()) for i, ref in enumerate(self._guarded)]
+        return [names.get(id(b), "buf#%d" % i) for i, b in live if b is not None and not b.intact()]
 
     # ---- parameters -------------------------------------------------------------------------
     def flatten(self, P):
