@@ -376,6 +376,48 @@ int gt_gather_infill(const float* hvo_set, const int64_t* idx, int64_t n_seq, in
 int gt_infill_merge(const float* hvo_pred, const float* hvo_in, const int32_t* removed, int64_t n_seq,
                     int32_t mode, float* hvo_out, gt_stream_t stream);
 
+/* Event-level infilling pairs: replaces GrooveMidiDatasetInfillingRandom's pairing (ref:dataset.py:464-555,
+ * hvo_seq.remove_random_events(thres_range=(0.4, 0.6))) in its symbolic form (src_dim 27; the reference's MSO input of these experiments is
+ * out of scope).  Where gt_gather_infill removes whole voices, this gather takes a random share of the individual HITS out of a groove,
+ * across voices.  hvo_set (n_seq,32,27) FULL grooves; idx: batch int64 indices on the device, clamped like gt_gather_batch's.  Conventions
+ * as gt_gather_infill: eo is HOST memory, read when the call is enqueued (a captured graph keeps the values); state is a DEVICE pointer,
+ * required: seed_lo, seed_hi and step are read on the device, so a graph replay draws afresh once the update has advanced step; kept
+ * values are bit copies.
+ * The draw for source index src (after clamping), in unsigned 32-bit wrap-around integers throughout -- no floating point:
+ *   cell j = t * 9 + c (step t, voice c, 0 <= j < 288) is an EVENT iff hvo_set[src][t][c] != 0 and a CANDIDATE iff it is an event and bit c
+ *   of voice_mask is set; n_ev = events, n_cand = candidates; cap = min(n_cand, n_ev - 1): neither side of the pair may be empty (the
+ *   reference drops such pairs, ref:dataset.py:520-524).  cap < 1: the sequence is INELIGIBLE -- x = the groove, y = zeros, its nine cells
+ *   words = 0; hosts keep such sequences out of the index stream.
+ *   key = the dropout streams' key(site) above with site = GT_SITE_INFILL_EVENTS; base = (uint32)(src * 512);
+ *   r_i = fmix32(((base + i) * 0x9E3779B1) ^ key).
+ *   Share: q = ratio_lo + (((uint64)r_0 * (uint32)(ratio_hi - ratio_lo + 1)) >> 32).
+ *   Count: k0 = (n_cand * q + 32768) >> 16, k = min(max(k0, 1), cap).
+ *   Subset: candidate j is removed iff fewer than k candidates j' have r_{1+j'} < r_{1+j} -- the k candidates with the smallest hash.  No
+ *   tie rule is needed: fmix32, the odd multiplier and the XOR are each bijections on 32 bits and base + 1 + j is distinct for j < 288, so
+ *   the 288 values of one sequence are pairwise different.  Exactly k cells are removed; the rule depends on no visiting order.
+ * Outputs: for a removed cell (t, c), x gets 0 in its h, v and o entries (columns c, 9 + c, 18 + c of row t) and y gets the groove's three
+ * values; for every other cell x gets the groove's values and y gets 0.  cells (batch x 9 uint32, or NULL): cells[b * 9 + c] has bit t set
+ * iff cell (t, c) was removed.
+ * The draw depends on src, not on the batch position: two batch elements with the same src in one call get the SAME draw.
+ * Rejected before any launch: a NULL pointer other than cells, batch or n_seq <= 0, a zero voice_mask or one with bits >= 9, a ratio
+ * outside 0..65536, ratio_lo > ratio_hi.  One launch, no atomics on global memory, bitwise repeatable; no host sync, no allocation;
+ * capturable. */
+#define GT_SITE_INFILL_EVENTS 3          /* sites 0, 1, 2 and >= 16 are taken */
+typedef struct gt_infill_event_opts {
+  int32_t voice_mask;           /* bit c set: hits of voice c may be removed; non-zero, no bits >= 9 */
+  int32_t ratio_lo, ratio_hi;   /* share of the candidate hits to remove, in 1/65536ths: 0 <= ratio_lo <= ratio_hi <= 65536 */
+} gt_infill_event_opts;
+int gt_gather_infill_events(const float* hvo_set, const int64_t* idx, int64_t n_seq, int32_t batch,
+                            const gt_infill_event_opts* eo, const gt_step_state* state,
+                            float* x, float* y, uint32_t* cells /* batch x 9, or NULL */, gt_stream_t stream);
+/* gt_infill_merge with the mask per cell: where bit (row % 32) of cells[(row / 32) * 9 + c] is clear, the prediction's three values of cell
+ * (row, c) count as 0 -- the model may only fill the cells that were removed.  cells (n_seq x 9 uint32, or NULL): NULL behaves exactly as
+ * gt_infill_merge(removed = NULL).  The two modes, the aliasing rule (hvo_out may be hvo_pred), the n_seq range and the rejections are
+ * gt_infill_merge's.  With pred = y, in = x and the cells of one gt_gather_infill_events call, both modes give back the source groove
+ * exactly (an HVO groove: velocity and offset are +0 wherever the hit is 0).  One elementwise launch. */
+int gt_infill_merge_cells(const float* hvo_pred, const float* hvo_in, const uint32_t* cells /* n_seq x 9, or NULL */,
+                          int64_t n_seq, int32_t mode, float* hvo_out, gt_stream_t stream);
+
 /* Measurement aid (no reference counterpart): with profiling on, every kernel launch is bracketed by
  * HIP events on its own stream.  gt_profile_report synchronises and writes one text row per kernel
  * class: "label launches total_ms total_flops total_bytes".  Not graph-capturable while on. */

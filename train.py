@@ -11,7 +11,8 @@ importable (`load_processed_dataset`, ref:train.py:153-155), (b) --data-npz FILE
 `inputs (N,32,S)` / `outputs (N,32,27)` (= the dataset's processed_inputs/processed_outputs tensors,
 ref:dataset.py:263-264), (c) --synthetic N sequences from the SURVEY 8(d) generator, or (d), for the symbolic
 infilling experiments, --infill-npz FILE with ONE array `hvo (N,32,27)` of full grooves: the voices to remove are
-drawn on the device at every visit (--infill_voices / --infill_min / --infill_max / --infill_prob).  W&B is optional.
+drawn on the device at every visit (--infill_voices / --infill_min / --infill_max / --infill_prob), or, with --infill_mode events,
+a random share of the individual hits (--infill_ratio LO,HI: the reference's InfillingRandom pairing).  W&B is optional.
 Data-parallel: launch with torch.distributed.run, one process per GPU.
 """
 import argparse
@@ -106,6 +107,11 @@ def build_parser():
                         "disabled): f_beta = the best F-beta, density = as many hits as the ground truth; adds hit precision / recall / F1 at "
                         "those thresholds to each set's record, writes voice_thresholds_Epoch_<n>.json, and checkpoints carry the thresholds")
     p.add_argument("--calibrate_beta", default=1.0, type=float, help="the beta of --calibrate_thresholds f_beta (and of the reported F score)")
+    p.add_argument("--infill_mode", default=None, choices=["voices", "events"],
+                   help="what --infill-npz removes from a groove: voices (default; whole voices, gt_gather_infill) or events (a random share of the "
+                        "individual hits across the --infill_voices, default all nine: GrooveMidiDatasetInfillingRandom's pairing, gt_gather_infill_events)")
+    p.add_argument("--infill_ratio", default=None, type=str,
+                   help="events mode: LO,HI -- the share of the removable hits to take out, drawn per groove and visit (default 0.4,0.6, the reference's thres_range)")
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible weight gradients (gt_set_deterministic: no token split in the weight-gradient kernels; +9-30 %% step time)")
     return p
@@ -157,7 +163,7 @@ def load_hyperparameters(args):
     return hp
 
 
-SYMBOLIC = ("InfillingClosedHH_Symbolic",)      # the experiments whose input is an HVO groove (embedding_size_src 27, ref:train.py:129-131)
+SYMBOLIC = ("InfillingClosedHH_Symbolic", "InfillingRandom_Symbolic")      # the experiments whose input is an HVO groove (embedding_size_src 27, ref:train.py:129-131)
 
 
 def _ints(v, what):
@@ -174,9 +180,10 @@ def _ints(v, what):
 
 
 def infill_setup(hp, args):
-    """make_infill_opts keywords of the infill flags / YAML keys, or None while none is given.  SystemExit for a non-symbolic experiment:
-    only there is the input the groove itself."""
-    vals = {k: hp.get(k, getattr(args, k)) for k in ("infill_voices", "infill_min", "infill_max", "infill_prob")}
+    """make_infill_opts keywords of the infill flags / YAML keys, or None while none is given; with infill_mode events, the dict
+    infill.as_opts takes for the event options: mode="events" beside make_infill_event_opts keywords.  SystemExit for a non-symbolic
+    experiment: only there is the input the groove itself."""
+    vals = {k: hp.get(k, getattr(args, k)) for k in ("infill_voices", "infill_min", "infill_max", "infill_prob", "infill_mode", "infill_ratio")}
     if hp.get("infill_npz") is None and all(v is None for v in vals.values()):
         return None
     if hp["experiment"] not in SYMBOLIC:
@@ -185,6 +192,25 @@ def infill_setup(hp, args):
     if hp.get("infill_npz") is None:
         raise SystemExit("--infill_voices / --infill_min / --infill_max / --infill_prob need --infill-npz FILE (full grooves)")
     from transformergrooveinfilling_amd import _lib
+    mode = "voices" if vals["infill_mode"] is None else str(vals["infill_mode"])
+    if mode not in ("voices", "events"):
+        raise SystemExit("infill_mode must be voices or events, got %r" % (mode,))
+    if mode == "events":
+        given = [k for k in ("infill_min", "infill_max", "infill_prob") if vals[k] is not None]
+        if given:
+            raise SystemExit("%s select how many whole voices go: they do not apply to --infill_mode events (use --infill_ratio)" % " / ".join(given))
+        try:
+            ratio = [0.4, 0.6] if vals["infill_ratio"] is None else _floats(vals["infill_ratio"], (2,), "infill_ratio")
+        except ValueError:
+            raise SystemExit("--infill_ratio expects two comma-separated floats LO,HI, got %r" % (vals["infill_ratio"],))
+        kw = dict(mode="events", voices=_ints(vals["infill_voices"], "infill_voices") or list(range(9)), ratio=ratio)
+        try:
+            _lib.make_infill_event_opts(voices=kw["voices"], ratio=ratio)
+        except ValueError as e:
+            raise SystemExit("infill options: %s" % e)
+        return kw
+    if vals["infill_ratio"] is not None:
+        raise SystemExit("--infill_ratio is the share of hits --infill_mode events removes: it does not apply to --infill_mode voices")
     lo = 1 if vals["infill_min"] is None else int(vals["infill_min"])
     kw = dict(voices=_ints(vals["infill_voices"], "infill_voices") or [2], min_remove=lo,
               max_remove=lo if vals["infill_max"] is None else int(vals["infill_max"]), prob=_ints(vals["infill_prob"], "infill_prob"))
@@ -223,7 +249,7 @@ def model_params(hp, device):
                       "d_model": hp["d_model"], "n_heads": hp["n_heads"], "dim_feedforward": hp["dim_feedforward"],
                       "dropout": hp["dropout"], "num_encoder_layers": hp["num_encoder_decoder_layers"],
                       "num_decoder_layers": 0 if enc_only else hp["num_encoder_decoder_layers"], "max_len": 32,
-                      "embedding_size_src": 27 if hp["experiment"] == "InfillingClosedHH_Symbolic" else 16,
+                      "embedding_size_src": 27 if hp["experiment"] in SYMBOLIC else 16,
                       "embedding_size_tgt": 27, "device": device},
             "training": {"learning_rate": hp["learning_rate"], "batch_size": hp["batch_size"],
                          "hit_loss_penalty": hp["hit_loss_penalty"], **extras},
@@ -336,7 +362,9 @@ def main(argv=None):
             raise SystemExit("--infill-npz: hvo must be (N,32,27), got %s" % (tuple(hvo.shape),))
         if args.host_loader:
             raise SystemExit("--infill-npz draws the pairs on the device: it cannot be combined with --host-loader")
-        x, y, _ = (t.cpu() for t in infill.pair_once(hvo[:args.eval_size], infill_kw, seed=args.seed, device=device))
+        # (events mode: pair_once_events; its third result is the removed cells, which the evaluation merge below is confined to)
+        pair_once = infill.pair_once_events if infill_kw.get("mode") == "events" else infill.pair_once
+        x, y, _ = (t.cpu() for t in pair_once(hvo[:args.eval_size], infill_kw, seed=args.seed, device=device))
     else:
         x, y = load_data(args, hp, params["model"]["embedding_size_src"])
 
@@ -347,7 +375,7 @@ def main(argv=None):
     ds = _Triples(x, y)
     pair = None
     if infill_kw is not None:
-        pair = lambda h: tuple(t.cpu() for t in infill.pair_once(h, infill_kw, seed=args.seed, device=device)[:2])
+        pair = lambda h: tuple(t.cpu() for t in pair_once(h, infill_kw, seed=args.seed, device=device)[:2])
     eval_sets = load_eval_sets(args, x, y, params["model"]["embedding_size_src"], pair) if rank == 0 else {}
     test = eval_sets.get("Test_Set", (None, None))
     val = eval_sets.get("Validation_Set", (None, None))
@@ -401,6 +429,11 @@ def main(argv=None):
                                    **{k: res[k] for k in ("precision", "recall", "f_beta", "density_ratio")}}, f)
                 for name, (xin, gt) in eval_sets.items():
                     sc = metrics.evaluate(model, xin, gt)
+                    if infill_kw is not None and infill_kw.get("mode") == "events":
+                        # the finished groove against the source groove: the prediction merged into its input, confined to the removed
+                        # cells (gt_infill_merge_cells) -- they are the cells where the target has a hit
+                        done = model.infill(xin, cells=(gt[..., :9] != 0))
+                        sc.update({"Infill_" + k: v for k, v in metrics.voice_metrics(model, done, xin + gt).items()})
                     if cal and cal_set:
                         sc.update(metrics.hit_scores(model, xin, gt, voice_thresholds="calibrated", beta=hp["calibrate_beta"]))
                     rec = {"%s/%s" % (name, k): v for k, v in sc.items()}

@@ -5,6 +5,7 @@ substitutes another implementation.  (tests/ may call ``load(path)`` with the ho
 of the same sources, tests/emu/libgroove_emu.so, to debug kernels without a GPU.)
 """
 import ctypes
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -69,6 +70,11 @@ class GtInfillOpts(ctypes.Structure):
                 ("count_weight", ctypes.c_int32 * GT_VOICES)]
 
 
+class GtInfillEventOpts(ctypes.Structure):
+    """gt_infill_event_opts: host memory, read when gt_gather_infill_events is enqueued"""
+    _fields_ = [("voice_mask", ctypes.c_int32), ("ratio_lo", ctypes.c_int32), ("ratio_hi", ctypes.c_int32)]
+
+
 _vp, _cfgp = ctypes.c_void_p, ctypes.POINTER(GtConfig)
 _SIGS = {
     "gt_last_error": (ctypes.c_char_p, []),
@@ -122,6 +128,11 @@ _SIGS = {
     "gt_gather_infill": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(GtInfillOpts), _vp, _vp, _vp, _vp, _vp]),
     # hvo_pred, hvo_in, removed, n_seq, mode, hvo_out, stream
     "gt_infill_merge": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]),
+    # hvo_set, idx, n_seq, batch, eo, state, x, y, cells, stream
+    "gt_gather_infill_events": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(GtInfillEventOpts), _vp, _vp, _vp, _vp,
+                                               _vp]),
+    # hvo_pred, hvo_in, cells, n_seq, mode, hvo_out, stream
+    "gt_infill_merge_cells": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]),
     # cfg, algo, params, grads, m, v, ws, state, zero_grads, stream
     "gt_optimizer_step_ws": (ctypes.c_int, [_cfgp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "gt_grad_buckets": (ctypes.c_int, [_cfgp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
@@ -314,6 +325,49 @@ def infill_opts_struct(t):
     if not isinstance(t, tuple) or len(t) != 12 or any(int(a) != a for a in t):
         raise ValueError("infill options must be the 12-integer tuple infill_opts_tuple() returns, got %r" % (t,))
     return _infill_struct(int(t[0]), int(t[1]), int(t[2]), [int(a) for a in t[3:3 + max(0, int(t[2]) - int(t[1]) + 1)]])
+
+
+RATIO_ONE = 65536      # gt_infill_event_opts: ratios are integers in 1/65536ths
+
+
+def _infill_event_struct(mask, lo, hi):
+    """the validated GtInfillEventOpts of (voice_mask, ratio_lo, ratio_hi); ValueError for what the library would refuse"""
+    if not 0 < mask < (1 << GT_VOICES):
+        raise ValueError("infill voices must be a non-empty subset of 0..%d (mask 0x%x)" % (GT_VOICES - 1, mask))
+    if not 0 <= lo <= hi <= RATIO_ONE:
+        raise ValueError("need 0 <= ratio_lo <= ratio_hi <= %d (1/65536ths), got %d / %d" % (RATIO_ONE, lo, hi))
+    return GtInfillEventOpts(mask, lo, hi)
+
+
+def make_infill_event_opts(voices=range(GT_VOICES), ratio=(0.4, 0.6)):
+    """gt_infill_event_opts: voices = the voices whose hits may be removed (default: all nine), ratio = (lo, hi), the share of the candidate
+    hits to remove, drawn per groove and visit (the reference's remove_random_events(thres_range=(0.4, 0.6)), ref:dataset.py:464-555); each
+    float becomes int(round(r * 65536)).  ValueError for what the library would refuse."""
+    voices = [int(v) for v in ([voices] if not hasattr(voices, "__len__") else voices)]
+    if any(not 0 <= v < GT_VOICES for v in voices):
+        raise ValueError("infill voices must be a non-empty subset of 0..%d, got %r" % (GT_VOICES - 1, voices))
+    ratio = [ratio, ratio] if not hasattr(ratio, "__len__") else list(ratio)
+    if len(ratio) != 2 or any(not math.isfinite(float(r)) for r in ratio):
+        raise ValueError("infill ratio must be two finite numbers (lo, hi), got %r" % (ratio,))
+    lo, hi = (int(round(float(r) * RATIO_ONE)) for r in ratio)
+    return _infill_event_struct(sum(1 << v for v in set(voices)), lo, hi)
+
+
+def infill_event_opts_tuple(eo):
+    """the hashable form of a GtInfillEventOpts (StepEngine.infill_event_opts; part of a captured graph's key): ("events", voice_mask,
+    ratio_lo, ratio_hi) -- the tag keeps it apart from the 12-integer tuple of the voice options"""
+    return ("events", eo.voice_mask, eo.ratio_lo, eo.ratio_hi)
+
+
+def is_infill_event_tuple(t):
+    return isinstance(t, tuple) and len(t) == 4 and t[0] == "events"
+
+
+def infill_event_opts_struct(t):
+    """the validated GtInfillEventOpts of such a tuple"""
+    if not is_infill_event_tuple(t) or any(not isinstance(a, int) or isinstance(a, bool) for a in t[1:]):
+        raise ValueError("event infill options must be the tuple infill_event_opts_tuple() returns, got %r" % (t,))
+    return _infill_event_struct(t[1], t[2], t[3])
 
 
 def torch_like(v):

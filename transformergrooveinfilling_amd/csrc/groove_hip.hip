@@ -2131,6 +2131,37 @@ extern "C" int gt_infill_merge(const float* hvo_pred, const float* hvo_in, const
             hvo_out, cells, (int)mode);
   return launch_status("gt_infill_merge");
 }
+// The gather that draws the event-level pair (gt_misc.h gather_infill_events_kernel): options from the host struct, baked into the launch;
+// seed and step are read on the device.
+extern "C" int gt_gather_infill_events(const float* hvo_set, const int64_t* idx, int64_t n_seq, int32_t batch, const gt_infill_event_opts* eo,
+                                       const gt_step_state* state, float* x, float* y, uint32_t* cells, gt_stream_t stream) {
+  if (!hvo_set || !idx || !eo || !state || !x || !y)
+    return gt_fail("gt_gather_infill_events: hvo_set / idx / eo / state / x / y must not be NULL");
+  if (batch <= 0 || n_seq <= 0) return gt_fail("gt_gather_infill_events: batch / n_seq must be > 0");
+  if (eo->voice_mask == 0 || (eo->voice_mask & ~((1 << GT_VOICES) - 1)))
+    return gt_fail("gt_gather_infill_events: voice_mask 0x%x must name at least one of the %d voices and no other bit", (unsigned)eo->voice_mask,
+                   GT_VOICES);
+  if (eo->ratio_lo < 0 || eo->ratio_hi > 65536 || eo->ratio_lo > eo->ratio_hi)
+    return gt_fail("gt_gather_infill_events: need 0 <= ratio_lo (%d) <= ratio_hi (%d) <= 65536", (int)eo->ratio_lo, (int)eo->ratio_hi);
+  const InfillEventArgs a{eo->voice_mask, (uint32_t)eo->ratio_lo, (uint32_t)(eo->ratio_hi - eo->ratio_lo + 1)};
+  gt_prof_tag("gather_infill_events", 0.0, (double)batch * (3.0 * 32 * GT_TGT * 4.0 + 8.0 + 4.0 * GT_VOICES));
+  gt_launch(gather_infill_events_kernel, dim3((unsigned)((batch + GT_GE_SEQ - 1) / GT_GE_SEQ)), dim3(GT_GE_THREADS), (hipStream_t)stream, hvo_set,
+            idx, x, y, cells, (int)batch, n_seq, a, state);
+  return launch_status("gt_gather_infill_events");
+}
+extern "C" int gt_infill_merge_cells(const float* hvo_pred, const float* hvo_in, const uint32_t* cells, int64_t n_seq, int32_t mode,
+                                     float* hvo_out, gt_stream_t stream) {
+  if (!hvo_pred || !hvo_in || !hvo_out) return gt_fail("gt_infill_merge_cells: hvo_pred / hvo_in / hvo_out must not be NULL");
+  if (n_seq <= 0 || n_seq >= (1ll << 26)) return gt_fail("gt_infill_merge_cells: n_seq %lld out of range", (long long)n_seq);
+  if (mode != 0 && mode != 1)
+    return gt_fail("gt_infill_merge_cells: mode %d (0 = the reference's sum, 1 = the input's hits win whole)", (int)mode);
+  if (!cells) return gt_infill_merge(hvo_pred, hvo_in, nullptr, n_seq, mode, hvo_out, stream);      // (the same launch: nothing is masked)
+  const int64_t n_cells = n_seq * 32 * GT_VOICES;
+  gt_prof_tag("infill_merge_cells", 0.0, (double)n_seq * (3.0 * 32 * GT_TGT * 4.0 + 4.0 * GT_VOICES));
+  gt_launch(infill_merge_cells_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), (hipStream_t)stream, hvo_pred, hvo_in, cells, hvo_out,
+            n_cells, (int)mode);
+  return launch_status("gt_infill_merge_cells");
+}
 
 // ------------------------------------------------------------------------------------ predict
 // vs != nullptr (gt_predict_voices): the per-voice head kernel decides and writes prob_out; thres / use_thres are then unused

@@ -1158,6 +1158,134 @@ __global__ __launch_bounds__(256) void infill_merge_kernel(const float* pred, co
   out[o] = h; out[o + GT_VOICES] = v; out[o + 2 * GT_VOICES] = w;
 }
 
+// ---- event-level infilling pairs drawn in the gather (ref:dataset.py:464-555 GrooveMidiDatasetInfillingRandom: remove_random_events takes a
+// random share of the individual hits out of a groove): x[b] = groove idx[b] with the drawn CELLS' h / v / o entries zeroed, y[b] = those
+// entries alone, the draw keyed on the device-resident step state.  Spec of the draw: include/groove_hip.h (integers only;
+// tests/infill_events_ref.py restates it).  A workgroup holds GT_GE_SEQ whole sequences, 320 threads (five waves) each, one thread per cell
+// (t, c) for the first 288:
+//   1. the 864 floats of the sequence are staged in LDS with float4 loads (threads 0..215);
+//   2. every cell thread derives its event / candidate flags and its hash r_{1+j}; event threads add (1 | candidate << 16) to the sequence's
+//      count word in LDS (integer adds: any order gives the same sum), and what the add returns gives a candidate a slot of its own in
+//      0..n_cand - 1 of the hash list, where its hash goes.  Which candidate gets which slot depends on the order of arrival; the ranks
+//      below do not -- they count a set.  Slots past n_cand hold 0xFFFFFFFF (written in step 1), which is smaller than no hash;
+//   3. every thread reads the counts and works out k (uniform per sequence); a candidate counts the listed hashes below its own --
+//      ceil(n_cand / 4) 16-byte LDS reads, the same word for every lane: broadcasts -- and is removed iff that rank is < k (k = n_cand:
+//      every candidate goes, nothing is counted);
+//   4. threads 0..215 write x and y from the LDS copy with float4 stores, looking each element's cell up in the removal flags; threads
+//      256..264 (the fifth wave has no store to do) gather one voice word of `cells` each.
+// Every thread of the workgroup meets all three barriers, also those of a sequence slot past the batch's end.
+#define GT_GE_SEQ 2
+#define GT_GE_TPS 320                                          // threads per sequence
+#define GT_GE_THREADS (GT_GE_SEQ * GT_GE_TPS)
+#define GT_GE_CELLS (32 * GT_VOICES)                           // 288
+struct InfillEventArgs { int voice_mask; uint32_t ratio_lo, ratio_span; };      // ratio_span = ratio_hi - ratio_lo + 1
+struct __attribute__((aligned(16))) gt_u32x4 { uint32_t a, b, c, d; };
+__global__ __launch_bounds__(GT_GE_THREADS) void gather_infill_events_kernel(const float* __restrict__ set, const int64_t* __restrict__ idx,
+                                                                             float* __restrict__ x, float* __restrict__ y,
+                                                                             uint32_t* __restrict__ cells, const int B, const int64_t n_seq,
+                                                                             const InfillEventArgs a, const gt_step_state* __restrict__ st) {
+  __shared__ __attribute__((aligned(16))) float sg[GT_GE_SEQ][32 * GT_TGT];
+  __shared__ __attribute__((aligned(16))) uint32_t s_hash[GT_GE_SEQ][GT_GE_CELLS];      // the candidates' hashes, compacted; 0xFFFFFFFF behind them
+  __shared__ uint32_t s_rem[GT_GE_SEQ][GT_GE_CELLS];           // 1: the cell was removed
+  __shared__ unsigned s_cnt[GT_GE_SEQ];                        // n_ev | n_cand << 16
+  const int g = threadIdx.x / GT_GE_TPS, t = threadIdx.x % GT_GE_TPS;
+  const int b = blockIdx.x * GT_GE_SEQ + g;
+  const bool live = b < B;                                     // the last workgroup may hold fewer sequences (it still meets every barrier)
+  const uint32_t seed_lo = st->seed_lo, seed_hi = st->seed_hi, step = st->step;      // (uniform; in flight beside the index and the groove)
+  int64_t src = 0;
+  if (live) {
+    src = idx[b];
+    src = src < 0 ? 0 : (src >= n_seq ? n_seq - 1 : src);      // as gather_batch_kernel: a bad index must not read outside the dataset
+    const float4* in = reinterpret_cast<const float4*>(set) + (size_t)src * GT_GI_Q;
+    if (t < GT_GI_Q) reinterpret_cast<float4*>(sg[g])[t] = in[t];
+  }
+  if (t == 0) s_cnt[g] = 0u;
+  if (t < GT_GE_CELLS) s_hash[g][t] = 0xFFFFFFFFu;
+  __syncthreads();
+  const uint32_t key = gt_site_key(seed_lo, seed_hi, step, GT_SITE_INFILL_EVENTS);      // (the dropout streams' key)
+  const uint32_t base = (uint32_t)(src * 512);
+  const bool cell = live && t < GT_GE_CELLS;
+  bool cand = false;
+  uint32_t r = 0u;
+  if (cell) {
+    const int tt = t / GT_VOICES, c = t % GT_VOICES;
+    const bool ev = sg[g][tt * GT_TGT + c] != 0.0f;
+    cand = ev && ((a.voice_mask >> c) & 1);
+    if (ev) {
+      const unsigned before = atomicAdd(&s_cnt[g], 1u | (cand ? 1u << 16 : 0u));
+      if (cand) {
+        r = gt_fmix32(((base + 1u + (uint32_t)t) * 0x9E3779B1u) ^ key);
+        s_hash[g][before >> 16] = r;                            // (fewer than n_cand <= 288 candidates came before)
+      }
+    }
+  }
+  __syncthreads();
+  if (cell) {
+    const uint32_t n_ev = s_cnt[g] & 0xFFFFu, n_cand = s_cnt[g] >> 16;
+    const uint32_t cap = n_cand < n_ev - 1u ? n_cand : n_ev - 1u;      // min(n_cand, n_ev - 1); n_ev = 0: n_cand = 0 < 2^32 - 1, cap = 0
+    uint32_t rem = 0u;
+    if (cand && cap >= 1u) {
+      const uint32_t q = a.ratio_lo + (uint32_t)(((uint64_t)gt_fmix32((base * 0x9E3779B1u) ^ key) * a.ratio_span) >> 32);
+      uint32_t k = (n_cand * q + 32768u) >> 16;
+      k = k < 1u ? 1u : k;
+      k = k > cap ? cap : k;
+      uint32_t below = 0u;
+      if (k < n_cand) {
+        const gt_u32x4* h4 = reinterpret_cast<const gt_u32x4*>(s_hash[g]);
+        const int n4 = (int)((n_cand + 3u) >> 2);
+#pragma unroll 4
+        for (int i = 0; i < n4; ++i) {
+          const gt_u32x4 h = h4[i];
+          below += (h.a < r ? 1u : 0u) + (h.b < r ? 1u : 0u) + (h.c < r ? 1u : 0u) + (h.d < r ? 1u : 0u);
+        }
+      }
+      rem = below < k ? 1u : 0u;
+    }
+    s_rem[g][t] = rem;
+  }
+  __syncthreads();
+  if (!live) return;
+  if (t < GT_GI_Q) {
+    const float4 v = reinterpret_cast<const float4*>(sg[g])[t];
+    const float e[4] = {v.x, v.y, v.z, v.w};
+    float ex[4], ey[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int el = 4 * t + j;
+      const bool out = s_rem[g][(el / GT_TGT) * GT_VOICES + (el % GT_TGT) % GT_VOICES] != 0u;      // the element's cell was removed
+      ex[j] = out ? 0.0f : e[j];
+      ey[j] = out ? e[j] : 0.0f;
+    }
+    reinterpret_cast<float4*>(x)[(size_t)b * GT_GI_Q + t] = make_float4(ex[0], ex[1], ex[2], ex[3]);
+    reinterpret_cast<float4*>(y)[(size_t)b * GT_GI_Q + t] = make_float4(ey[0], ey[1], ey[2], ey[3]);
+  } else if (cells != nullptr && t >= 256 && t < 256 + GT_VOICES) {
+    const int c = t - 256;
+    uint32_t w = 0u;
+#pragma unroll 8
+    for (int tt = 0; tt < 32; ++tt) w |= s_rem[g][tt * GT_VOICES + c] << tt;
+    cells[(size_t)b * GT_VOICES + c] = w;
+  }
+}
+// ... and the way back with the mask per cell: infill_merge_kernel where pred counts only in the cells whose bit is set (cells[seq * 9 + c]
+// bit row % 32).  out may alias pred (a thread reads its three values before it writes them).
+__global__ __launch_bounds__(256) void infill_merge_cells_kernel(const float* pred, const float* __restrict__ in,
+                                                                 const uint32_t* __restrict__ cellmask, float* out, const int64_t cells,
+                                                                 const int mode) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= cells) return;
+  const int64_t row = e / GT_VOICES;
+  const int c = (int)(e % GT_VOICES);
+  const size_t o = (size_t)row * GT_TGT + c;
+  float ph = pred[o], pv = pred[o + GT_VOICES], po = pred[o + 2 * GT_VOICES];
+  const float ih = in[o], iv = in[o + GT_VOICES], io = in[o + 2 * GT_VOICES];
+  if (!((cellmask[(row >> 5) * GT_VOICES + c] >> (row & 31)) & 1u)) { ph = 0.0f; pv = 0.0f; po = 0.0f; }
+  const bool hit = ih != 0.0f;
+  float h, v, w;
+  if (mode == 0) { h = hit ? ih : ph + ih; v = pv + iv; w = po + io; }
+  else { h = hit ? ih : ph; v = hit ? iv : pv; w = hit ? io : po; }
+  out[o] = h; out[o + GT_VOICES] = v; out[o + 2 * GT_VOICES] = w;
+}
+
 // ---- bf16 shadows of the encoder layers' weight matrices (gt_config.precision = 1, GemmArgs::B16): for each of the four matrices W
 // (R x C) of every layer, W16 = bf16(W) in place order and W16T = bf16(W^T) -- the copy that turns a dgrad (dX = dY W) into the forward's
 // NT form.  One workgroup per 32 x 32 tile, transposed through LDS; both outputs leave as 64-byte row segments.  Runs at the head of

@@ -62,6 +62,7 @@ class _Slot:
         self.loss_scratch = None       # options (StepEngine._loss_ready); the scratch is zeroed once, every call leaves it zero
         self.idx = torch.zeros(B, dtype=torch.int64, device=eng.device)     # static batch indices of the indexed step
         self.removed = None            # train_step_indexed_infill: the removal bitmasks of the step's B draws (int32; made by its first step)
+        self.cells = None              # train_step_indexed_infill_events: the removed cells of the step's B draws ((B,9) int32 bit words)
         self.graphs = {}               # step recipe -> captured hipGraph
         self.keep = {}                 # step recipe -> tensors whose raw pointers its graph holds
         self.use_graph = None          # StepEngine.graph_for's decision for this slot (use_graph="auto")
@@ -95,7 +96,7 @@ class StepEngine:
     def __init__(self, d_model, n_heads, dim_feedforward, num_encoder_layers, num_decoder_layers=0,
                  dropout=0.0, embedding_size_src=16, batch_size=None, optimizer="sgd", learning_rate=0.05,
                  hit_loss_penalty=1.0, seed=0, device="cuda", world_size=1, use_graph="auto", lib=None, precision="fp32",
-                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False, loss_opts=None, infill_opts=None):
+                 max_grad_norm=None, weight_decay=0.0, momentum=0.0, nesterov=False, loss_opts=None, infill_opts=None, infill_event_opts=None):
         self.device = torch.device(device)
         # The only way onto host memory is an EXPLICITLY passed library object (tests hand in the host-emulator build of
         # the same kernel sources to cover the multi-rank step sequence over gloo); nothing in the package does that.
@@ -142,6 +143,10 @@ class StepEngine:
         # (make_infill_opts).  Settable at any time; part of that step's graph key
         self.infill_opts = infill_opts
         self._io_struct = (None, None)     # (tuple, its validated GtInfillOpts)
+        # the event removal train_step_indexed_infill_events' gather draws (gt_infill_event_opts): None, or the tuple
+        # _lib.infill_event_opts_tuple() returns (make_infill_event_opts).  Settable at any time; part of that step's graph key
+        self.infill_event_opts = infill_event_opts
+        self._eo_struct = (None, None)     # (tuple, its validated GtInfillEventOpts)
         self.mbuf = None               # SGD's momentum buffers, flat like the gradients (zeros when momentum is first non-zero: torch's first step)
         self.names = layout.param_names(d_model, dim_feedforward, embedding_size_src, num_encoder_layers, num_decoder_layers)
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -755,7 +760,7 @@ class StepEngine:
         return self._indexed_step(s, (xs.data_ptr(), ys.data_ptr(), xs.shape[0]), gather, (xs, ys), on_grads)
 
     def _indexed_step(self, s, key, gather, keep, on_grads):
-        """The step behind an indexed gather (train_step_indexed / train_step_indexed_infill): `gather` enqueues the launch that fills the
+        """The step behind an indexed gather (train_step_indexed / train_step_indexed_infill / _infill_events): `gather` enqueues the launch that fills the
         slot's static inputs, `key` is what it bakes into a captured graph, `keep` the resident tensors whose raw pointers that graph holds."""
         if on_grads is not None:
             gather()
@@ -813,6 +818,41 @@ class StepEngine:
         def gather():
             self.lib.call("gt_gather_infill", _ptr(hvo_set), _ptr(s.idx), ctypes.c_int64(hvo_set.shape[0]), int(s.B), ctypes.byref(io),
                           _ptr(self.state), _ptr(s.x), _ptr(s.y), _ptr(s.removed), self.stream)
+
+        return self._indexed_step(s, key, gather, (hvo_set,), on_grads)
+
+    def make_infill_event_opts(self, voices=range(_lib.GT_VOICES), ratio=(0.4, 0.6)):
+        """A value for self.infill_event_opts: the validated, hashable tuple of a gt_infill_event_opts (the voices whose hits may be removed,
+        the share of them to remove: the reference's remove_random_events thres_range)."""
+        return _lib.infill_event_opts_tuple(_lib.make_infill_event_opts(voices, ratio))
+
+    def train_step_indexed_infill_events(self, hvo_set, idx, on_grads=None):
+        """train_step_indexed_infill with the event-level pairing: the gather at the head of the step (gt_gather_infill_events) removes, per
+        batch element, a random share of the individual hits (self.infill_event_opts), drawn from the engine's own device step state -- every
+        replay draws afresh -- and fills both static step inputs: x = the groove without those hits, y = the removed hits.  The slot's
+        `cells` ((B,9) int32 bit words: bit t of cells[b, c] = cell (t, c) was removed) holds the draws of the last step."""
+        if self.dims["embedding_size_src"] != _lib.GT_TGT:
+            raise ValueError("train_step_indexed_infill_events needs a symbolic model (embedding_size_src 27: the input is an HVO groove), got %d"
+                             % self.dims["embedding_size_src"])
+        if self.infill_event_opts is None:
+            raise ValueError("train_step_indexed_infill_events: set infill_event_opts first (StepEngine.make_infill_event_opts)")
+        infill.check_set(hvo_set)
+        s = self.slot(idx.shape[0])
+        self._train_B = s.B
+        s.fwd_id += 1
+        if self.loss_opts is not None:
+            self._loss_ready(s)
+        if s.cells is None:
+            s.cells = torch.zeros(s.B, _lib.GT_VOICES, dtype=torch.int32, device=self.device)
+        s.idx.copy_(idx, non_blocking=True)
+        if self._eo_struct[0] != self.infill_event_opts:     # (validated once per value, like the loss's options)
+            self._eo_struct = (self.infill_event_opts, _lib.infill_event_opts_struct(self.infill_event_opts))
+        eo = self._eo_struct[1]
+        key = ("infill",) + self.infill_event_opts + (hvo_set.data_ptr(), hvo_set.shape[0])
+
+        def gather():
+            self.lib.call("gt_gather_infill_events", _ptr(hvo_set), _ptr(s.idx), ctypes.c_int64(hvo_set.shape[0]), int(s.B), ctypes.byref(eo),
+                          _ptr(self.state), _ptr(s.x), _ptr(s.y), _ptr(s.cells), self.stream)
 
         return self._indexed_step(s, key, gather, (hvo_set,), on_grads)
 

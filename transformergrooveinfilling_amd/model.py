@@ -226,17 +226,21 @@ class _GrooveBase(nn.Module):
             out[name] = {v: sc[c][j] for c, v in enumerate(VOICES)}
         return out
 
-    def infill(self, hvo_in, removed=None, mode=1, **predict_kwargs):
+    def infill(self, hvo_in, removed=None, mode=1, cells=None, **predict_kwargs):
         """The finished groove on the device: predict on the symbolic input hvo_in (N,32,27) -- a groove with voices removed --, then put
         the prediction back into it (gt_infill_merge; ref:evaluator.py:364-372 add_removed_part_to_hvo).  removed: one bitmask per sequence
         (what gt_gather_infill reported), or None -- the model may then fill any voice; mode 1: where the input has a hit its (h, v, o) win
-        whole; mode 0: the reference's arithmetic (velocities and offsets are summed).  predict_kwargs: predict_hvo's.  -> (N,32,27)"""
+        whole; mode 0: the reference's arithmetic (velocities and offsets are summed).  cells (instead of removed): the mask per cell
+        (gt_infill_merge_cells) -- (N,9) bit words as gt_gather_infill_events reported them, or (N,32,9) bool: the prediction is confined to
+        those cells.  predict_kwargs: predict_hvo's.  -> (N,32,27)"""
         from . import infill
+        if removed is not None and cells is not None:
+            raise ValueError("infill takes removed (a bitmask of voices per sequence) or cells (a mask per cell), not both")
         if self.embedding_size_src != self.embedding_size_tgt:
             raise ValueError("infill needs a symbolic model (embedding_size_src 27: the input is an HVO groove), got %d" % self.embedding_size_src)
         hvo_in = torch.as_tensor(hvo_in, dtype=torch.float32).to(self.engine.device).contiguous()
         pred = self.predict_hvo(hvo_in, **predict_kwargs)
-        return infill.merge(pred, hvo_in, removed, mode, lib=self.engine.lib, out=pred)
+        return infill.merge(pred, hvo_in, removed, mode, lib=self.engine.lib, out=pred, cells=cells)
 
 
 class GrooveTransformerEncoder(_GrooveBase):

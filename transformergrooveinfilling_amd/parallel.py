@@ -98,7 +98,9 @@ class DeviceBatchLoader:
     ``DeviceBatchLoader.infilling(hvo, infill_opts, ...)`` is the form for the symbolic infilling experiments: ONE resident tensor of full
     grooves (N,32,27); the pair is drawn on the device (gt_gather_infill).  Only the grooves that can be paired (infill.infill_eligible) are
     permuted; ``index_batches()`` is as above (train_loop hands the indices to StepEngine.train_step_indexed_infill), iteration yields
-    (x, y, idx) drawn with this loader's own step state (the loader's seed, step = batches yielded so far)."""
+    (x, y, idx) drawn with this loader's own step state (the loader's seed, step = batches yielded so far).  With event options
+    (infill.as_opts: mode="events") the pool is infill.events_eligible, iteration gathers through gt_gather_infill_events and train_loop
+    calls StepEngine.train_step_indexed_infill_events."""
 
     def __init__(self, x, y, batch_size, device, rank=0, world=1, seed=0):
         x = torch.as_tensor(x, dtype=torch.float32).to(device).contiguous()
@@ -123,9 +125,10 @@ class DeviceBatchLoader:
         from . import infill
         x = torch.as_tensor(hvo, dtype=torch.float32).to(device).contiguous()
         io = infill.as_opts(infill_opts)
-        pool = infill.infill_eligible(x, io).cpu()
+        pool = infill.eligible(x, io).cpu()
         if pool.numel() == 0:
-            raise ValueError("no groove of the set can be paired with these infill options (none has a removable voice beside another active one)")
+            raise ValueError("no groove of the set can be paired with these infill options (none has a removable %s)"
+                             % ("hit beside another hit" if infill.is_events(io) else "voice beside another active one"))
         self = cls.__new__(cls)
         self._setup(x, None, batch_size, device, rank, world, seed, io, pool, lib)
         return self
@@ -158,7 +161,8 @@ class DeviceBatchLoader:
                 step = torch.tensor([self._drawn & 0x7FFFFFFF], dtype=torch.int32).view(torch.uint8)
                 self._state[8:12].copy_(step, non_blocking=True)          # gt_step_state.step: a fresh draw per batch
                 self._drawn += 1
-                x, y, _ = infill.gather(self.x, idx, self.infill_opts, self._state, self._lib)
+                draw = infill.gather_events if infill.is_events(self.infill_opts) else infill.gather
+                x, y, _ = draw(self.x, idx, self.infill_opts, self._state, self._lib)
                 yield x, y, idx
             return
         for idx in self.index_batches():

@@ -444,7 +444,11 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
     batches = ((None, None, i) for i in dataloader.index_batches()) if indexed else dataloader
     # ... or ONE resident tensor of full grooves: the gather draws the voices to remove (gt_gather_infill) with the loader's options
     infilling = indexed and getattr(dataloader, "infill_opts", None) is not None
-    if infilling:
+    # (event options: individual hits instead, gt_gather_infill_events)
+    events = infilling and isinstance(dataloader.infill_opts, _lib.GtInfillEventOpts)
+    if events:
+        eng.infill_event_opts = _lib.infill_event_opts_tuple(dataloader.infill_opts)
+    elif infilling:
         eng.infill_opts = _lib.infill_opts_tuple(dataloader.infill_opts)
     # wandb.watch(model, log_freq=1000) (ref:train.py:150) hooks the Parameters' gradients; the fused step never materialises a .grad
     # autograd could hook (it consumes and re-zeroes the flat gradient buffer inside its last launch).  Equivalent: every
@@ -466,7 +470,9 @@ def train_loop(dataloader, groove_transformer, encoder_only, opt, epoch, loss_fn
             n_batches += 1
             model._watch_step = getattr(model, "_watch_step", 0) + 1
             on_grads = watch_cb if (watch and model._watch_step % watch == 0) else None
-            if infilling:
+            if events:
+                stats = eng.train_step_indexed_infill_events(dataloader.x, _idx, on_grads=on_grads)
+            elif infilling:
                 stats = eng.train_step_indexed_infill(dataloader.x, _idx, on_grads=on_grads)
             elif indexed:
                 stats = eng.train_step_indexed(dataloader.x, dataloader.y, _idx, on_grads=on_grads)
