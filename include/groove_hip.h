@@ -326,6 +326,43 @@ typedef struct gt_threshold_rule {
 int gt_hit_thresholds(const uint64_t* counts_host, const float* thres, int32_t n_thres, const gt_threshold_rule* rule,
                       float* thres_out /*9*/, int32_t* index_out /*9*/, float* scores_out /*9 x 4*/);
 
+/* Per-group and removed-cell evaluation counts: the device side of the reference's per-subset evaluation (ref:evaluator.py:171-196 splits a
+ * set by genre tag and reports hit, velocity and micro-timing numbers per subset), of hit metrics confined to the cells an infilling pair
+ * removed, of the velocity / offset error on the hits that came back, and of per-sequence counts a host can pick examples by -- one counting
+ * pass over the two HVO buffers.  hvo_pred / hvo_gt: (n_seq * 32, 27), device.  group (n_seq int32, device, or NULL: every sequence in
+ * group 0): a sequence with group[s] < 0 or >= n_groups is SKIPPED -- none of its cells reach acc, and the last word of acc counts it.
+ * cells (n_seq x 9 uint32, device, or NULL: every cell): the convention of gt_gather_infill_events and gt_infill_merge_cells -- cell (s, t, c) is
+ * counted iff bit t of cells[s * 9 + c] is set.
+ * Per counted cell, with m = s * 32 + t, g = group[s], in fp32: ph = (hvo_pred[m * 27 + c] == 1.0f), gh = (hvo_gt[m * 27 + c] == 1.0f) (the
+ * loss's and the curve's yh == 1 convention; a NaN is no hit); dv = pred - gt of column 9 + c, ev = dv * dv; eo the same from column 18 + c.
+ * acc[(g * 9 + c) * 8 + k] += : k = 0: 1 (counted cells); 1: TP = ph && gh; 2: FP = ph && !gh; 3: FN = !ph && gh; 4: fix of ev; 5: fix of eo;
+ * 6 / 7: the same two for TP cells only.  fix of e = (uint64_t)((double)e * 4294967296.0 + 0.5) when e <= 16.0f: 32 fractional bits, exact
+ * (an fp32 value times a power of two is exact in fp64).  Any other e (NaN, +-inf, above 16) adds nothing to k = 4..7 and counts as a
+ * REJECTED value, once per velocity and once per offset value.  Capacity: with e <= 16 a word holds 2^28 cells in the worst case, 2^32
+ * cells of errors <= 1 (velocities in [0,1], offsets in [-0.5,0.5]).
+ * Behind the n_groups * 72 words: acc[n_groups * 72 + 2 g] += 1 per sequence of group g, acc[n_groups * 72 + 2 g + 1] += its rejected
+ * values; then one word, += 1 per skipped sequence.  GT_GM_ACC_WORDS words in all.  The call ADDS: zero acc once and walk a set in chunks.
+ * Integer arithmetic throughout: the result depends on neither the launch geometry nor on how a set is cut into calls or on their order.
+ * seq_out (n_seq x 4 uint32, device, or NULL): seq_out[s * 4 + {0,1,2,3}] = the counted cells, TP, FP and FN of sequence s summed over the
+ * nine voices -- STORED, not added, for every s < n_seq: a skipped sequence's counts are written all the same, only acc leaves it out.
+ * Two launches (csrc/gt_group.h): workgroups with 64-bit accumulators in LDS, one owner thread per word, write partials to scratch; a second
+ * kernel adds them onto acc (one writer per word).  No global atomics, no floating-point atomics.  scratch: gt_group_metrics_scratch_words
+ * 64-bit words, device; NO precondition (every word read was written by the same call) -- it need not be zeroed and is not left zero.
+ * No host sync, no allocation; capturable.
+ * Rejected before any launch, acc untouched: hvo_pred, hvo_gt, acc or scratch NULL, n_seq <= 0 or >= 2^26, n_groups < 1 or
+ * > GT_GM_MAX_GROUPS. */
+#define GT_GM_MAX_GROUPS 64
+#define GT_GM_WORDS 8                 /* 64-bit words per (group, voice) */
+/* acc: n_groups*9*8 words, then n_groups*2 words (per group: sequences, rejected values), then 1 word (skipped sequences) */
+#define GT_GM_ACC_WORDS(n_groups) ((n_groups) * (GT_VOICES * GT_GM_WORDS + 2) + 1)
+int64_t gt_group_metrics_scratch_words(int64_t n_seq, int32_t n_groups);      /* 64-bit words */
+int gt_group_metrics(const float* hvo_pred, const float* hvo_gt,
+                     const int32_t* group  /* n_seq, device; NULL: every sequence in group 0 */,
+                     const uint32_t* cells /* n_seq x 9, device; NULL: every cell */,
+                     int64_t n_seq, int32_t n_groups, uint64_t* acc,
+                     uint32_t* seq_out /* n_seq x 4, device, or NULL */,
+                     uint64_t* scratch, gt_stream_t stream);
+
 /* Replaces GrooveMidiDatasetInfilling.__getitem__ + the DataLoader's collate for a dataset resident in HBM
  * (ref:dataset.py:263-264,355-356; ref:train.py:156-158): x[b] = xs[idx[b]], y[b] = ys[idx[b]] for b < batch, both step
  * inputs in ONE launch.  xs (n_seq,32,src_dim), ys (n_seq,32,27) fp32; idx int64 on the device (out-of-range entries are

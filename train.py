@@ -67,7 +67,9 @@ def build_parser():
     p.add_argument("--eval-npz", default=None,
                    help="npz with the evaluation subsets: train_inputs/train_gt, test_inputs/test_gt, validation_inputs/validation_gt "
                         "((n,32,S) / (n,32,27): the evaluators' processed_inputs / processed_gt, ref:evaluator.py:509-511); missing sets are "
-                        "skipped.  With --synthetic and no file: three seeded synthetic subsets")
+                        "skipped.  With --synthetic and no file: three seeded synthetic subsets.  Genre tags: <set>_groups (n integers; the keys "
+                        "are train_groups, test_groups, validation_groups) and group_names (strings; default group<k>) make the evaluation leg "
+                        "also report every metric per group (gt_group_metrics; at most 64 groups)")
     p.add_argument("--eval-size", default=1024, type=int, help="sequences per synthetic / train-derived evaluation subset")
     p.add_argument("--host-loader", action="store_true",
                    help="feed batches through torch's DataLoader from host memory (the reference's way) instead of keeping the "
@@ -291,30 +293,55 @@ def _flag(v):
     return bool(v) and str(v).lower() not in ("false", "0", "no", "none")
 
 
-def load_eval_sets(args, x, y, src_dim, pair=None):
+def load_eval_sets(args, x, y, src_dim, pair=None, info=None, x_mask=None):
     """{"Train_Set" | "Test_Set" | "Validation_Set": (inputs, gt)} for the sets the flags enable (ref:train.py:160-174: three
     pickled evaluators, each holding processed_inputs / processed_gt of a subset).  Sources: --eval-npz; else, with --synthetic,
     seeded synthetic subsets; the train subset defaults to the head of the training tensors.  pair (infilling from full grooves): a set given
-    as ONE array <set>_hvo (n,32,27) is paired once through it -- a fixed state, so every epoch scores the same pairs."""
+    as ONE array <set>_hvo (n,32,27) is paired once through it -- a fixed state, so every epoch scores the same pairs; pair returns
+    (inputs, gt, mask, kept): what the pairing removed (voice bitmasks or cell words) and the indices of the grooves it could pair.
+    info (a dict, filled per set name): "mask" -- that third result (x_mask: the one of the training tensors' own pairing) --, and for a
+    set the file tags with <set>_groups: "groups" (n int32), "names", "n_groups" (the largest id + 1; the file's group_names or group<k>).
+    SystemExit for tags that do not fit their set or name more than 64 groups."""
     import numpy as np
     import torch
     want = {"Train_Set": _flag(args.eval_train), "Test_Set": _flag(args.eval_test), "Validation_Set": _flag(args.eval_validation)}
     key = {"Train_Set": "train", "Test_Set": "test", "Validation_Set": "validation"}
     sets = {}
     z = np.load(args.eval_npz) if args.eval_npz else None
+    info = {} if info is None else info
     for i, (name, on) in enumerate(want.items()):
         if not on:
             continue
         k = key[name]
+        kept, from_file = None, False
         if z is not None and k + "_inputs" in z.files:
             sets[name] = (torch.from_numpy(z[k + "_inputs"]).float(), torch.from_numpy(z[k + "_gt"]).float())
+            from_file = True
         elif z is not None and pair is not None and k + "_hvo" in z.files:
-            sets[name] = pair(torch.from_numpy(z[k + "_hvo"]).float())
+            xi, gi, mask, kept = pair(torch.from_numpy(z[k + "_hvo"]).float())
+            sets[name] = (xi, gi)
+            info.setdefault(name, {})["mask"] = mask
+            from_file = True
         elif name == "Train_Set":
             n = min(args.eval_size, len(x))
             sets[name] = (x[:n], y[:n])
+            if x_mask is not None:
+                info.setdefault(name, {})["mask"] = x_mask[:n]
         elif args.synthetic:
             sets[name] = synthetic_tensors(args.eval_size, src_dim, args.seed + 100 + i)
+        if from_file and k + "_groups" in z.files:
+            g = np.asarray(z[k + "_groups"]).reshape(-1)
+            if kept is not None and len(g) == len(z[k + "_hvo"]):
+                g = g[kept.numpy()]                      # (the grooves the pairing left out take their tags with them)
+            if len(g) != len(sets[name][0]) or not np.issubdtype(g.dtype, np.integer):
+                raise SystemExit("--eval-npz: %s_groups must hold one integer tag per sequence (%d), got %d of %s"
+                                 % (k, len(sets[name][0]), len(g), g.dtype))
+            n_groups = max(1, int(g.max()) + 1)
+            if n_groups > 64:
+                raise SystemExit("--eval-npz: %s_groups names %d groups; the per-group evaluation takes at most 64 (GT_GM_MAX_GROUPS)" % (k, n_groups))
+            names = [str(s) for s in z["group_names"]] if "group_names" in z.files else []
+            names = names[:n_groups] + ["group%d" % j for j in range(len(names), n_groups)]
+            info.setdefault(name, {}).update(groups=torch.from_numpy(g.astype(np.int32)), names=names, n_groups=n_groups)
     return sets
 
 
@@ -364,8 +391,9 @@ def main(argv=None):
             raise SystemExit("--infill-npz draws the pairs on the device: it cannot be combined with --host-loader")
         # (events mode: pair_once_events; its third result is the removed cells, which the evaluation merge below is confined to)
         pair_once = infill.pair_once_events if infill_kw.get("mode") == "events" else infill.pair_once
-        x, y, _ = (t.cpu() for t in pair_once(hvo[:args.eval_size], infill_kw, seed=args.seed, device=device))
+        x, y, x_mask = (t.cpu() for t in pair_once(hvo[:args.eval_size], infill_kw, seed=args.seed, device=device))
     else:
+        x_mask = None
         x, y = load_data(args, hp, params["model"]["embedding_size_src"])
 
     class _Triples(TensorDataset):           # the reference's dataset yields (x, y, idx) (ref:dataset.py:355-356)
@@ -375,8 +403,11 @@ def main(argv=None):
     ds = _Triples(x, y)
     pair = None
     if infill_kw is not None:
-        pair = lambda h: tuple(t.cpu() for t in pair_once(h, infill_kw, seed=args.seed, device=device)[:2])
-    eval_sets = load_eval_sets(args, x, y, params["model"]["embedding_size_src"], pair) if rank == 0 else {}
+        def pair(h):          # (inputs, gt, what was removed -- voice bitmasks or cell words --, the indices of the grooves that could be paired)
+            kept = infill.eligible(h.to(device), infill_kw).cpu()
+            return tuple(t.cpu() for t in pair_once(h, infill_kw, seed=args.seed, device=device)) + (kept,)
+    eval_info = {}
+    eval_sets = load_eval_sets(args, x, y, params["model"]["embedding_size_src"], pair, eval_info, x_mask) if rank == 0 else {}
     test = eval_sets.get("Test_Set", (None, None))
     val = eval_sets.get("Validation_Set", (None, None))
     if infill_kw is not None:
@@ -429,23 +460,52 @@ def main(argv=None):
                                    **{k: res[k] for k in ("precision", "recall", "f_beta", "density_ratio")}}, f)
                 for name, (xin, gt) in eval_sets.items():
                     sc = metrics.evaluate(model, xin, gt)
+                    tagged = eval_info.get(name, {})
+                    grec, glines = {}, []
+                    if "groups" in tagged:
+                        # the reference's per-subset numbers (ref:evaluator.py:171-196): the same predictions counted per genre tag on the device
+                        by_group = metrics.evaluate_groups(model, xin, gt, tagged["groups"], names=tagged["names"])
+                        for gname in tagged["names"]:
+                            gs = by_group[gname]
+                            glines.append("    %s / %s: %d sequences  hits F1 %.4f  accuracy %.4f  velocity MSE on hits %.5f  offset MSE on hits %.5f" %
+                                          (name, gname, gs["Sequences"], gs["Hits_F1_Overall"], gs["Hits_Accuracy_Overall"],
+                                           gs["Velocity_MSE_Hits_Overall"], gs["Offset_MSE_Hits_Overall"]))
+                            grec.update({"%s/%s/%s" % (name, gname, k): v for k, v in gs.items()})
                     if infill_kw is not None and infill_kw.get("mode") == "events":
                         # the finished groove against the source groove: the prediction merged into its input, confined to the removed
                         # cells (gt_infill_merge_cells) -- they are the cells where the target has a hit
                         done = model.infill(xin, cells=(gt[..., :9] != 0))
                         sc.update({"Infill_" + k: v for k, v in metrics.voice_metrics(model, done, xin + gt).items()})
+                        # ... and counted over those cells alone: everywhere else the finished groove is the source by construction
+                        removed_part = metrics.group_metrics(model, done, xin + gt, cells=(gt[..., :9] != 0))["Overall"]
+                        sc.update({"Infill_Removed_" + k: v for k, v in removed_part.items()})
+                    elif infill_kw is not None:
+                        # voices mode: the removed part is whole voices -- the pairing's bitmasks; a set that arrived already paired has them in
+                        # its target, which keeps the removed voices alone (only voices with a hit are ever removed)
+                        mask = tagged.get("mask")
+                        if mask is None:
+                            mask = ((gt[..., :9] != 0).any(1).to(torch.int32) << torch.arange(9, dtype=torch.int32)).sum(1).to(torch.int32)
+                        done = model.infill(xin, removed=mask)
+                        removed_part = metrics.group_metrics(model, done, xin + gt, removed=mask)["Overall"]
+                        sc.update({"Infill_Removed_" + k: v for k, v in removed_part.items()})
                     if cal and cal_set:
                         sc.update(metrics.hit_scores(model, xin, gt, voice_thresholds="calibrated", beta=hp["calibrate_beta"]))
                     rec = {"%s/%s" % (name, k): v for k, v in sc.items()}
+                    rec.update(grec)
                     model.eval_log.append(dict(rec, epoch=ep))
                     print("  %s: hits accuracy %.4f  velocity MSE %.5f  offset MSE %.5f" %
                           (name, sc["Hits_Accuracy_Overall"], sc["Velocity_MSE_Overall"], sc["Offset_MSE_Overall"]))
+                    for line in glines:                 # one line per group of a tagged set
+                        print(line)
                     if wb:
                         wb.log(dict(rec, epoch=ep), commit=False)
                     if _flag(args.dump_eval):
                         import json
                         with open(os.path.join(save_dir, "eval_%s_Epoch_%d.json" % (name, ep)), "w") as f:
                             json.dump(dict(sc, epoch=ep), f)
+                        if "groups" in tagged:
+                            with open(os.path.join(save_dir, "eval_%s_groups_Epoch_%d.json" % (name, ep)), "w") as f:
+                                json.dump(dict(by_group, epoch=ep, set=name, groups=tagged["names"]), f)
             if wb:
                 wb.log({"epoch": ep}, commit=True)
     if wb:

@@ -57,6 +57,14 @@ class GtThresholdRule(ctypes.Structure):
 CURVE_MAX_THRES = 127            # GT_CURVE_MAX_THRES
 CRITERIA = {"f_beta": 0, "density": 1}
 
+GM_MAX_GROUPS = 64               # GT_GM_MAX_GROUPS
+GM_WORDS = 8                     # GT_GM_WORDS: 64-bit words per (group, voice) of gt_group_metrics' acc
+
+
+def gm_acc_words(n_groups):
+    """GT_GM_ACC_WORDS: n_groups x 9 x 8 words, then (sequences, rejected values) per group, then the skipped sequences"""
+    return int(n_groups) * (GT_VOICES * GM_WORDS + 2) + 1
+
 
 class GtLossOpts(ctypes.Structure):
     """gt_loss_opts: host memory, read when gt_loss_ex / gt_train_step_loss is enqueued"""
@@ -122,6 +130,9 @@ _SIGS = {
     "gt_hit_thresholds": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float), ctypes.c_int32,
                                          ctypes.POINTER(GtThresholdRule), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_float)]),
+    "gt_group_metrics_scratch_words": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
+    # hvo_pred, hvo_gt, group, cells, n_seq, n_groups, acc, seq_out, scratch, stream
+    "gt_group_metrics": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     # xs, ys, idx, n_seq, batch, src_dim, x, y, stream
     "gt_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     # hvo_set, idx, n_seq, batch, io, state, x, y, removed, stream

@@ -21,6 +21,7 @@
 #include "gt_common.h"
 #include "gt_curve.h"
 #include "gt_gemm.h"
+#include "gt_group.h"
 #include "gt_misc.h"
 #include "gt_seq_api.h"
 
@@ -2058,6 +2059,29 @@ extern "C" int gt_hit_curve(const float* prob, int32_t prob_stride, const float*
   gt_launch(hit_curve_sum_kernel, dim3((keys + GT_CURVE_THREADS - 1) / GT_CURVE_THREADS), dim3(GT_CURVE_THREADS), s, (const unsigned*)scratch, nwg,
             keys, counts);
   return launch_status("gt_hit_curve");
+}
+// Per-group evaluation counts (gt_group.h): two launches; the accumulator variant (4 / 16 / 64 groups of LDS) follows n_groups.
+extern "C" int64_t gt_group_metrics_scratch_words(int64_t n_seq, int32_t n_groups) {
+  if (n_seq <= 0 || n_seq >= (1ll << 26) || n_groups < 1 || n_groups > GT_GM_MAX_GROUPS) return 0;
+  return (int64_t)gt_gm_wgs(n_seq, n_groups) * GT_GM_ACC_WORDS(n_groups);
+}
+extern "C" int gt_group_metrics(const float* hvo_pred, const float* hvo_gt, const int32_t* group, const uint32_t* cells, int64_t n_seq,
+                                int32_t n_groups, uint64_t* acc, uint32_t* seq_out, uint64_t* scratch, gt_stream_t stream) {
+  if (!hvo_pred || !hvo_gt || !acc || !scratch) return gt_fail("gt_group_metrics: hvo_pred / hvo_gt / acc / scratch must not be NULL");
+  if (n_seq <= 0 || n_seq >= (1ll << 26)) return gt_fail("gt_group_metrics: n_seq %lld out of range", (long long)n_seq);
+  if (n_groups < 1 || n_groups > GT_GM_MAX_GROUPS)
+    return gt_fail("gt_group_metrics: n_groups %d outside 1..%d", (int)n_groups, GT_GM_MAX_GROUPS);
+  const int nwg = gt_gm_wgs(n_seq, n_groups), words = GT_GM_ACC_WORDS(n_groups), variant = gt_gm_variant(n_groups);
+  hipStream_t s = (hipStream_t)stream;
+  gt_prof_tag("group_metrics", 0.0, (double)n_seq * (2.0 * 32 * GT_TGT * 4.0 + (group ? 4.0 : 0.0) + (cells ? 4.0 * GT_VOICES : 0.0) +
+                                                     (seq_out ? 16.0 : 0.0)) + (double)nwg * words * 8.0);
+  auto* kern = variant == 4 ? group_metrics_partial_kernel<4> : variant == 16 ? group_metrics_partial_kernel<16>
+                                                                              : group_metrics_partial_kernel<GT_GM_MAX_GROUPS>;
+  gt_launch(kern, dim3(nwg), dim3(GT_GM_THREADS), s, hvo_pred, hvo_gt, group, cells, n_seq, (int)n_groups, scratch, seq_out);
+  gt_prof_tag("group_metrics_sum", 0.0, (double)nwg * words * 8.0 + words * 16.0);
+  gt_launch(group_metrics_sum_kernel, dim3((words + GT_GM_SUM_WORDS - 1) / GT_GM_SUM_WORDS), dim3(GT_GM_THREADS), s, (const uint64_t*)scratch,
+            nwg, words, acc);
+  return launch_status("gt_group_metrics");
 }
 extern "C" int gt_hit_thresholds(const uint64_t* counts_host, const float* thres, int32_t n_thres, const gt_threshold_rule* rule,
                                  float* thres_out, int32_t* index_out, float* scores_out) {

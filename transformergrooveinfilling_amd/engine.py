@@ -1118,6 +1118,56 @@ class StepEngine:
         self._curve_buf = {q: v for q, v in self._curve_buf.items() if q in self._predict_ws}
         return counts
 
+    def group_metrics(self, hvo_pred, hvo_gt, groups=None, n_groups=None, cells=None, removed=None, acc=None, seq_counts=False, chunk=None):
+        """Per-group evaluation counts of predictions against ground truth, both (N,32,27) HVO tensors (gt_group_metrics;
+        include/groove_hip.h) -> device int64 tensor of GT_GM_ACC_WORDS(n_groups) words; with seq_counts=True also the (N,4) int32 counts
+        (counted cells, TP, FP, FN per sequence).  groups: N integer tags (None: every sequence in group 0); a tag outside 0..n_groups - 1
+        skips its sequence.  n_groups: default the largest tag + 1 (one host read), 1 without groups.  The mask of the cells that count --
+        at most one of: cells, the (N,9) int32 / uint32 bit words of gather_events or an (N,32,9) bool tensor; removed, the (N,) int32
+        voice bitmasks of gather (each removed voice counts whole).  acc: an earlier result over the same n_groups to continue (it is
+        added to in place; counts of disjoint shards add).  chunk: sequences per call (default: all, below the call's 2^26)."""
+        from . import infill
+        p = torch.as_tensor(hvo_pred, dtype=torch.float32).to(self.device).contiguous()
+        g = torch.as_tensor(hvo_gt, dtype=torch.float32).to(self.device).contiguous()
+        if p.shape != g.shape or p.shape[-1] != 27 or p.numel() % (32 * 27) or p.numel() == 0:
+            raise ValueError("group_metrics needs two (N,32,27) HVO tensors with N >= 1, got %s / %s" % (tuple(p.shape), tuple(g.shape)))
+        n = p.numel() // (32 * 27)
+        if cells is not None and removed is not None:
+            raise ValueError("group_metrics takes cells (a mask per cell) or removed (a bitmask of voices per sequence), not both")
+        if removed is not None:
+            removed = torch.as_tensor(removed).to(self.device, torch.int32).reshape(-1)
+            if removed.numel() != n:
+                raise ValueError("removed needs one bitmask per sequence (%d), got %d" % (n, removed.numel()))
+            bit = (removed.view(n, 1) >> torch.arange(_lib.GT_VOICES, device=self.device, dtype=torch.int32).view(1, -1)) & 1
+            cells = (-bit).to(torch.int32).contiguous()                      # a removed voice: the all-ones word
+        elif cells is not None:
+            cells = infill.cell_words(cells, n, self.device)
+        if groups is not None:
+            groups = torch.as_tensor(groups).to(self.device, torch.int32).reshape(-1).contiguous()
+            if groups.numel() != n:
+                raise ValueError("groups needs one tag per sequence (%d), got %d" % (n, groups.numel()))
+        if n_groups is None:
+            n_groups = 1 if groups is None else max(1, int(groups.max().item()) + 1)
+        n_groups = int(n_groups)
+        if not 1 <= n_groups <= _lib.GM_MAX_GROUPS:
+            raise ValueError("n_groups must lie in 1..%d, got %d" % (_lib.GM_MAX_GROUPS, n_groups))
+        words = _lib.gm_acc_words(n_groups)
+        if acc is None:
+            acc = torch.zeros(words, dtype=torch.int64, device=self.device)
+        elif tuple(acc.shape) != (words,) or acc.dtype != torch.int64 or not acc.is_contiguous() or acc.device != p.device:
+            raise ValueError("acc must be a contiguous int64 tensor (%d,) on %s" % (words, self.device))
+        seq = torch.empty(n, 4, dtype=torch.int32, device=self.device) if seq_counts else None
+        chunk = min(n, (1 << 26) - 1) if chunk is None else max(1, min(int(chunk), (1 << 26) - 1))
+        scratch = torch.empty(int(self.lib.cdll.gt_group_metrics_scratch_words(ctypes.c_int64(min(chunk, n)), n_groups)), dtype=torch.int64,
+                              device=self.device)
+        p, g = p.view(n, 32, 27), g.view(n, 32, 27)
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)                                            # (a shorter tail needs no more scratch: the size grows with m)
+            self.lib.call("gt_group_metrics", _ptr(p[i:i + m]), _ptr(g[i:i + m]), _ptr(groups[i:i + m]) if groups is not None else None,
+                          _ptr(cells[i:i + m]) if cells is not None else None, ctypes.c_int64(m), n_groups, _ptr(acc),
+                          _ptr(seq[i:i + m]) if seq is not None else None, _ptr(scratch), self.stream)
+        return (acc, seq) if seq_counts else acc
+
     def _trim_predict_ws(self):
         for m in [k for k, (_, ws, _) in self._predict_ws.items() if 4 * ws.numel() > PREDICT_WS_KEEP]:
             del self._predict_ws[m]               # (stream-ordered free: the caching allocator keeps the block until the launches ran)
