@@ -363,6 +363,40 @@ int gt_group_metrics(const float* hvo_pred, const float* hvo_gt,
                      uint32_t* seq_out /* n_seq x 4, device, or NULL */,
                      uint64_t* scratch, gt_stream_t stream);
 
+/* Groove descriptors and rhythmic distances per sequence: the integers behind the reference's table of rhythmic descriptors for
+ * __Ground_Truth beside __Prediction (get_stats_from_evaluator, written as stats_<run>_Epoch_<n>.csv on the "all" epochs, ref:evaluator.py:516-601)
+ * and behind per-sequence distances of a prediction from its target (the reference keeps a commented get_rhythmic_distances call).  The
+ * reference's GrooveEvaluator is not vendored: the definitions below are this library's own.
+ * hvo_a, hvo_b (or NULL): (n_seq * 32, 27), device, 16-byte aligned.  feat_a, feat_b (or NULL): n_seq x GT_GF_WORDS 64-bit words; pair (or
+ * NULL): n_seq x GT_GF_PAIR_WORDS.  Every output word of every s < n_seq is STORED, not added (reserved words as 0): no zeroed buffer, no
+ * scratch, nothing left behind.  hvo_b with feat_b NULL, with pair NULL or with both NULL is legal (a host computes the ground truth's record
+ * once and afterwards asks for feat_a and pair only).
+ * Conventions: step t = 0..31, voice c = 0..8; a cell is a hit iff hvo[(s * 32 + t) * 27 + c] == 1.0f (the loss's convention; a NaN, 0.5 or
+ * 2.0 is no hit).  At a hit v = column 9 + c, o = column 18 + c; v is valid iff 0.0f <= v && v <= 16.0f, o iff fabsf of o <= 16.0f (a NaN
+ * fails both).  An invalid value at a hit adds nothing to the value words and the profile and counts as rejected; the hit itself counts.
+ * fix of e = (uint64_t)((double)e * 4294967296.0 + 0.5) (gt_group_metrics' fixed point: 32 fractional bits, exact); q of v =
+ * (uint32_t)((double)v * 65536.0 + 0.5); the profile P[t] = the sum over c of q of v over the hits of step t with a valid v (< 2^24).
+ * Squares (v * v, ...) are one fp32 multiply before fix.
+ * feat[s * 32 + k]: 0: hits; 1: voices with at least one hit; 2: steps with at least one hit; 3: hits at t % 4 == 0; 4: hits at t % 4 == 2;
+ * 5: hits at odd t; 6: cells (t < 16, c) hit at both t and t + 16; 7: rejected velocities; 8: rejected offsets; 9: sum of fix of v; 10: of
+ * fix of v * v; 11: of fix of |o|; 12: of o as signed fixed point (+fix of o for o >= 0, -fix of -o otherwise: a two's-complement 64-bit
+ * integer); 13: of fix of o * o; 14: 0; 15 + l, l = 0..16: the circular autocorrelation of the profile, A[l] = sum over t of
+ * P[t] * P[(t + l) mod 32].  Worst case (every cell a hit at v = 16): A[l] about 2^51.3, word 10 about 2^48.2.
+ * pair[s * 8 + k], p = buffer a, g = buffer b: 0: cells whose hits differ (Hamming); 1: cells hit in both; 2: near misses -- a cell hit in p
+ * and not in g while g has a hit of the same voice at t - 1 or t + 1, or the same with p and g exchanged (steps outside 0..31 do not exist:
+ * no wrap-around); 3: sum over ALL cells of fix of dv * dv, dv = v'_p - v'_g in fp32, v' = v at a hit with a valid velocity and 0 elsewhere;
+ * 4: sum of fix of do * do, do = o_p - o_g, over the cells hit in both with both offsets valid; 5: the number of those cells; 6: sum over t
+ * of P_p[t] * P_g[t]; 7: 0.
+ * Integers throughout: the result depends on neither the launch geometry, nor a sequence's position in the set, nor its neighbours.
+ * One launch (csrc/gt_groove.h); no global atomics, no floating-point atomics, one writer per word; no host sync, no allocation; capturable.
+ * Rejected before any launch, outputs untouched: hvo_a or feat_a NULL, n_seq <= 0 or >= 2^26, feat_b or pair given without hvo_b, a
+ * misaligned pointer. */
+#define GT_GF_WORDS 32                /* 64-bit words per sequence and buffer */
+#define GT_GF_PAIR_WORDS 8
+int gt_groove_features(const float* hvo_a, const float* hvo_b /* or NULL */, int64_t n_seq,
+                       uint64_t* feat_a /* n_seq x 32 */, uint64_t* feat_b /* n_seq x 32, or NULL */,
+                       uint64_t* pair /* n_seq x 8, or NULL */, gt_stream_t stream);
+
 /* Replaces GrooveMidiDatasetInfilling.__getitem__ + the DataLoader's collate for a dataset resident in HBM
  * (ref:dataset.py:263-264,355-356; ref:train.py:156-158): x[b] = xs[idx[b]], y[b] = ys[idx[b]] for b < batch, both step
  * inputs in ONE launch.  xs (n_seq,32,src_dim), ys (n_seq,32,27) fp32; idx int64 on the device (out-of-range entries are

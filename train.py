@@ -109,6 +109,11 @@ def build_parser():
                         "disabled): f_beta = the best F-beta, density = as many hits as the ground truth; adds hit precision / recall / F1 at "
                         "those thresholds to each set's record, writes voice_thresholds_Epoch_<n>.json, and checkpoints carry the thresholds")
     p.add_argument("--calibrate_beta", default=1.0, type=float, help="the beta of --calibrate_thresholds f_beta (and of the reported F score)")
+    # the descriptor leg of the evaluation (gt_groove_features).  Also the YAML key eval_descriptors; off by default
+    p.add_argument("--eval_descriptors", default=False,
+                   help="on the full-evaluation epochs of the save schedule, write the table of rhythmic descriptors of each evaluated set -- ground "
+                        "truth beside prediction, with per-sequence rhythmic distances -- as stats_<Set>_<run id>_Epoch_<n>.csv (per group of a "
+                        "tagged set: stats_<Set>_groups_Epoch_<n>.json)")
     p.add_argument("--infill_mode", default=None, choices=["voices", "events"],
                    help="what --infill-npz removes from a groove: voices (default; whole voices, gt_gather_infill) or events (a random share of the "
                         "individual hits across the --infill_voices, default all nine: GrooveMidiDatasetInfillingRandom's pairing, gt_gather_infill_events)")
@@ -159,6 +164,9 @@ def load_hyperparameters(args):
         if not (0.0 < cal_beta < float("inf")):
             raise SystemExit("calibrate_beta must be > 0 and finite, got %r" % cal_beta)
         hp["calibrate_thresholds"], hp["calibrate_beta"] = cal, cal_beta
+    # the descriptor leg, the same way (only where set, as above)
+    if _flag(hp.pop("eval_descriptors", args.eval_descriptors)):
+        hp["eval_descriptors"] = True
     # infilling from full grooves, the same way
     hp["infill_npz"] = hp.get("infill_npz", args.infill_npz)
     hp["infill"] = infill_setup(hp, args)
@@ -345,6 +353,54 @@ def load_eval_sets(args, x, y, src_dim, pair=None, info=None, x_mask=None):
     return sets
 
 
+def write_descriptors(model, name, xin, gt, tagged, infill_kw, gt_records, ep, save_dir, run_id, wb=None):
+    """The descriptor table of one evaluated set: stats_<Set>_<run id>_Epoch_<n>.csv (rows: the seven statistics; columns: every descriptor
+    as __Ground_Truth and __Prediction, every Distance::<name>), stats_<Set>_groups_Epoch_<n>.json for a tagged set, one printed line, and a
+    record of its own on model.eval_log (and W&B).  An infilling run scores the finished groove (model.infill) against the source groove,
+    as the Infill_* scalars do; gt_records keeps the target's records per set on the device."""
+    import json
+    import torch
+    from transformergrooveinfilling_amd import metrics
+    if infill_kw is not None:
+        target = xin + gt
+        if infill_kw.get("mode") == "events":
+            pred = model.infill(xin, cells=(gt[..., :9] != 0))
+        else:
+            mask = tagged.get("mask")
+            if mask is None:
+                mask = ((gt[..., :9] != 0).any(1).to(torch.int32) << torch.arange(9, dtype=torch.int32)).sum(1).to(torch.int32)
+            pred = model.infill(xin, removed=mask)
+    else:
+        target, pred = gt, model.predict_hvo(xin)
+    if name not in gt_records:
+        gt_records[name] = model.engine.groove_features(target)
+    tables = metrics.groove_table(model, pred, target, groups=tagged.get("groups"), names=tagged.get("names"), gt_feat=gt_records[name])
+    tab = tables["Overall"]
+    cols = [k for k, v in tab.items() if isinstance(v, dict)]
+    with open(os.path.join(save_dir, "stats_%s_%s_Epoch_%d.csv" % (name, run_id, ep)), "w") as f:
+        f.write(",".join([""] + ['"%s"' % c for c in cols]) + "\n")
+        for stat in metrics.TABLE_STATS:
+            f.write(",".join([stat] + [repr(tab[c][stat]) for c in cols]) + "\n")
+    if "groups" in tagged:
+        with open(os.path.join(save_dir, "stats_%s_groups_Epoch_%d.json" % (name, ep)), "w") as f:
+            json.dump(dict(tables, epoch=ep, set=name, groups=tagged["names"]), f)
+    rec = {}
+    for k, v in tab.items():
+        if k.startswith("Distance::"):
+            rec["%s/Distance/%s_mean" % (name, k[len("Distance::"):])] = v["mean"]
+        elif isinstance(v, dict):
+            rec["%s/Descriptor/%s_mean" % (name, k)] = v["mean"]
+        else:
+            rec["%s/Descriptor/%s" % (name, k)] = v
+    model.eval_log.append(dict(rec, epoch=ep))
+    if wb:
+        wb.log(dict(rec, epoch=ep), commit=False)
+    print("  %s descriptors: Hamming %.2f  fuzzy %.2f  velocity L2 %.4f  offset RMS %.4f  W1 of NoI %.3f / step density %.4f / velocity mean %.4f" %
+          (name, tab["Distance::Hamming"]["mean"], tab["Distance::Fuzzy Hamming"]["mean"], tab["Distance::Velocity L2"]["mean"],
+           tab["Distance::Offset RMS"]["mean"], tab["Statistical::NoI__W1"], tab["Statistical::Total Step Density__W1"],
+           tab["Statistical::Poly Velocity Mean__W1"]))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     hp = load_hyperparameters(args)
@@ -425,6 +481,7 @@ def main(argv=None):
     bce_kw, loss_options = loss_setup(hp)
     bce_kw = {k: torch.tensor(v, device=device) for k, v in bce_kw.items()}
     bce, mse = torch.nn.BCEWithLogitsLoss(reduction="none", **bce_kw), torch.nn.MSELoss(reduction="none")
+    gt_records = {}                           # --eval_descriptors: the ground truth's records per set, computed once, kept on the device
     part, full = save_schedule(hp["epochs"], only_final=bool(args.only_final_eval) and str(args.only_final_eval) != "False")
     save_dir = args.save_dir or (wb.run.dir if wb else os.path.join(ROOT, "checkpoints"))
     os.makedirs(save_dir, exist_ok=True)
@@ -506,6 +563,12 @@ def main(argv=None):
                         if "groups" in tagged:
                             with open(os.path.join(save_dir, "eval_%s_groups_Epoch_%d.json" % (name, ep)), "w") as f:
                                 json.dump(dict(by_group, epoch=ep, set=name, groups=tagged["names"]), f)
+            # the descriptor leg (the second leg of ref:evaluator.py:516-601, get_stats_from_evaluator's table on the "all" epochs): the
+            # records of every sequence on the device (gt_groove_features), one copy per set, the table on the host
+            if hp.get("eval_descriptors") and ep in full:
+                for name, (xin, gt) in eval_sets.items():
+                    write_descriptors(model, name, xin, gt, eval_info.get(name, {}), infill_kw, gt_records, ep, save_dir,
+                                      wb.run.id if wb else "local", wb)
             if wb:
                 wb.log({"epoch": ep}, commit=True)
     if wb:

@@ -59,6 +59,8 @@ CRITERIA = {"f_beta": 0, "density": 1}
 
 GM_MAX_GROUPS = 64               # GT_GM_MAX_GROUPS
 GM_WORDS = 8                     # GT_GM_WORDS: 64-bit words per (group, voice) of gt_group_metrics' acc
+GF_WORDS = 32                    # GT_GF_WORDS: 64-bit words per sequence and buffer of gt_groove_features' records
+GF_PAIR_WORDS = 8                # GT_GF_PAIR_WORDS
 
 
 def gm_acc_words(n_groups):
@@ -133,6 +135,8 @@ _SIGS = {
     "gt_group_metrics_scratch_words": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     # hvo_pred, hvo_gt, group, cells, n_seq, n_groups, acc, seq_out, scratch, stream
     "gt_group_metrics": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    # hvo_a, hvo_b, n_seq, feat_a, feat_b, pair, stream
+    "gt_groove_features": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     # xs, ys, idx, n_seq, batch, src_dim, x, y, stream
     "gt_gather_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     # hvo_set, idx, n_seq, batch, io, state, x, y, removed, stream

@@ -21,6 +21,7 @@
 #include "gt_common.h"
 #include "gt_curve.h"
 #include "gt_gemm.h"
+#include "gt_groove.h"
 #include "gt_group.h"
 #include "gt_misc.h"
 #include "gt_seq_api.h"
@@ -2082,6 +2083,20 @@ extern "C" int gt_group_metrics(const float* hvo_pred, const float* hvo_gt, cons
   gt_launch(group_metrics_sum_kernel, dim3((words + GT_GM_SUM_WORDS - 1) / GT_GM_SUM_WORDS), dim3(GT_GM_THREADS), s, (const uint64_t*)scratch,
             nwg, words, acc);
   return launch_status("gt_group_metrics");
+}
+// Groove descriptors and rhythmic distances per sequence (gt_groove.h): one launch, every output word stored by one thread.
+extern "C" int gt_groove_features(const float* hvo_a, const float* hvo_b, int64_t n_seq, uint64_t* feat_a, uint64_t* feat_b, uint64_t* pair,
+                                  gt_stream_t stream) {
+  if (!hvo_a || !feat_a) return gt_fail("gt_groove_features: hvo_a / feat_a must not be NULL");
+  if (n_seq <= 0 || n_seq >= (1ll << 26)) return gt_fail("gt_groove_features: n_seq %lld out of range", (long long)n_seq);
+  if (!hvo_b && (feat_b || pair)) return gt_fail("gt_groove_features: feat_b / pair need hvo_b");
+  if (((uintptr_t)hvo_a | (uintptr_t)hvo_b) & 15u) return gt_fail("gt_groove_features: hvo_a / hvo_b must be 16-byte aligned");
+  if (((uintptr_t)feat_a | (uintptr_t)feat_b | (uintptr_t)pair) & 7u) return gt_fail("gt_groove_features: feat_a / feat_b / pair must be 8-byte aligned");
+  const bool has_b = hvo_b && (feat_b || pair);
+  gt_prof_tag("groove_features", 0.0, (double)n_seq * ((has_b ? 2.0 : 1.0) * 32 * GT_TGT * 4.0 +
+                                                       8.0 * (GT_GF_WORDS * (feat_b ? 2.0 : 1.0) + (pair ? GT_GF_PAIR_WORDS : 0.0))));
+  gt_launch(groove_features_kernel, dim3(gt_gf_wgs(n_seq)), dim3(GT_GF_THREADS), (hipStream_t)stream, hvo_a, hvo_b, n_seq, feat_a, feat_b, pair);
+  return launch_status("gt_groove_features");
 }
 extern "C" int gt_hit_thresholds(const uint64_t* counts_host, const float* thres, int32_t n_thres, const gt_threshold_rule* rule,
                                  float* thres_out, int32_t* index_out, float* scores_out) {

@@ -1168,6 +1168,35 @@ class StepEngine:
                           _ptr(seq[i:i + m]) if seq is not None else None, _ptr(scratch), self.stream)
         return (acc, seq) if seq_counts else acc
 
+    def groove_features(self, hvo_a, hvo_b=None, feat_b=True, pair=True, chunk=None):
+        """Groove descriptors and rhythmic distances per sequence (gt_groove_features; include/groove_hip.h): the integer record of every
+        sequence of hvo_a (N,32,27) -> device int64 tensor (N,32).  With hvo_b (the same shape): also its records (N,32) (feat_b=True) and
+        the words that compare a with b, (N,8) (pair=True) -- returned as a tuple in that order, each only where asked for (a ground
+        truth whose record is already known: feat_b=False).  Every word is stored by the call: nothing to zero, no scratch.
+        chunk: sequences per call (default: all, below the call's 2^26)."""
+        a = torch.as_tensor(hvo_a, dtype=torch.float32).to(self.device).contiguous()
+        if a.shape[-1] != 27 or a.numel() % (32 * 27) or a.numel() == 0:
+            raise ValueError("groove_features needs an (N,32,27) HVO tensor with N >= 1, got %s" % (tuple(a.shape),))
+        n = a.numel() // (32 * 27)
+        a = a.view(n, 32, 27)
+        b = None
+        if hvo_b is not None:
+            b = torch.as_tensor(hvo_b, dtype=torch.float32).to(self.device).contiguous()
+            if b.numel() != a.numel() or b.shape[-1] != 27:
+                raise ValueError("groove_features needs two HVO tensors of one shape, got %s / %s" % (tuple(a.shape), tuple(b.shape)))
+            b = b.view(n, 32, 27)
+        want_fb, want_pair = b is not None and bool(feat_b), b is not None and bool(pair)
+        fa = torch.empty(n, _lib.GF_WORDS, dtype=torch.int64, device=self.device)
+        fb = torch.empty(n, _lib.GF_WORDS, dtype=torch.int64, device=self.device) if want_fb else None
+        pw = torch.empty(n, _lib.GF_PAIR_WORDS, dtype=torch.int64, device=self.device) if want_pair else None
+        chunk = min(n, (1 << 26) - 1) if chunk is None else max(1, min(int(chunk), (1 << 26) - 1))
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)
+            self.lib.call("gt_groove_features", _ptr(a[i:i + m]), _ptr(b[i:i + m]) if (want_fb or want_pair) else None, ctypes.c_int64(m),
+                          _ptr(fa[i:i + m]), _ptr(fb[i:i + m]) if want_fb else None, _ptr(pw[i:i + m]) if want_pair else None, self.stream)
+        out = (fa,) + ((fb,) if want_fb else ()) + ((pw,) if want_pair else ())
+        return out[0] if len(out) == 1 else out
+
     def _trim_predict_ws(self):
         for m in [k for k, (_, ws, _) in self._predict_ws.items() if 4 * ws.numel() > PREDICT_WS_KEEP]:
             del self._predict_ws[m]               # (stream-ordered free: the caching allocator keeps the block until the launches ran)

@@ -162,3 +162,143 @@ def evaluate(model, inputs, gt_hvo, use_thres=True, thres=0.5):
     device (chunked), reduce per voice on the device, return the dictionary."""
     pred = model.predict_hvo(inputs, use_thres=use_thres, thres=thres)
     return voice_metrics(model, pred, torch.as_tensor(gt_hvo))
+
+
+# ---- groove descriptors and rhythmic distances (gt_groove_features) -------------------------------------------------------------------------
+# The second leg of the reference's log_eval (ref:evaluator.py:516-601): on the "all" epochs it writes get_stats_from_evaluator's table of
+# rhythmic descriptors -- mean, std, min, max, median and quartiles, __Ground_Truth beside __Prediction -- and keeps a commented call to
+# get_rhythmic_distances.  The GrooveEvaluator that defines those descriptors is un-vendored, so the definitions below are THIS PACKAGE'S
+# OWN, named after the reference's columns where a counterpart exists (as the keys above are).  The device yields integers per sequence
+# (engine.groove_features); everything here is fp64 from a host copy of them, and a quantity whose denominator is zero is 0.
+DESCRIPTORS = ("Statistical::NoI", "Statistical::Total Step Density", "Statistical::Avg Voice Density", "Statistical::Weak to Strong Ratio",
+               "Statistical::Symmetry", "Statistical::Poly Velocity Mean", "Statistical::Poly Velocity std", "Statistical::Poly Offset Mean",
+               "Statistical::Poly Offset std", "Micro-Timing::Accuracy", "Auto-Correlation::Max", "Auto-Correlation::Centroid",
+               "Auto-Correlation::Skewness", "Auto-Correlation::Beat", "Auto-Correlation::Bar")
+DISTANCES = ("Hamming", "Fuzzy Hamming", "Jaccard", "Velocity L2", "Offset RMS", "Profile Cosine")
+TABLE_STATS = ("mean", "std", "min", "max", "median", "q1", "q3")
+_FIX = 4294967296.0
+
+
+def _words(t, width):
+    import numpy as np
+    a = t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    if a.ndim != 2 or a.shape[1] != width or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("expected an (N,%d) integer array, got %s of %s" % (width, a.shape, a.dtype))
+    return a.astype(np.int64).astype(np.float64)                   # (every word is below 2^53: exact)
+
+
+def _ratio(num, den):
+    import numpy as np
+    return np.divide(num, den, out=np.zeros(np.broadcast(num, den).shape, np.float64), where=den != 0)
+
+
+def groove_descriptors(feat):
+    """Rhythmic descriptors per sequence from the (N,32) records of engine.groove_features -> ``{name: (N,) float64}`` over DESCRIPTORS.
+    This package's own definitions (the reference's GrooveEvaluator is un-vendored), named after the reference's table columns.  With w<k>
+    word k of the record, nv = hits - rejected velocities, no = hits - rejected offsets, a[l] = A[l] / A[0] the normalised circular
+    autocorrelation of the velocity profile:
+    NoI = voices with a hit; Total Step Density = steps with a hit / 32; Avg Voice Density = hits / (32 * voices); Weak to Strong Ratio =
+    hits at odd steps / hits at even steps; Symmetry = 2 * (cells hit in both halves of the bar) / hits; Poly Velocity Mean / std and Poly
+    Offset Mean / std over the hits with a valid value (std = sqrt(max(0, E[x^2] - mean^2))); Micro-Timing::Accuracy = the mean |offset|;
+    Auto-Correlation::Max = the largest a[l], l = 1..16; Centroid = sum l a[l] / sum a[l] and Skewness = the third standardised moment of
+    the lag under the weights a[l] / sum a, both over l = 1..16; Beat = a[4]; Bar = a[16].  A zero denominator gives 0."""
+    import numpy as np
+    w = _words(feat, 32)
+    hits, nv, no = w[:, 0], w[:, 0] - w[:, 7], w[:, 0] - w[:, 8]
+    vmean, omean = _ratio(w[:, 9] / _FIX, nv), _ratio(w[:, 12] / _FIX, no)
+    a = _ratio(w[:, 15:32], w[:, 15:16])                            # (N,17): a[0] = 1 wherever the profile is not empty
+    lag = np.arange(1, 17, dtype=np.float64)
+    tot = a[:, 1:].sum(1)
+    p = _ratio(a[:, 1:], tot[:, None])
+    cen = (p * lag).sum(1)
+    var = (p * (lag - cen[:, None]) ** 2).sum(1)
+    m3 = (p * (lag - cen[:, None]) ** 3).sum(1)
+    vals = (w[:, 1], w[:, 2] / 32.0, _ratio(hits, 32.0 * w[:, 1]), _ratio(w[:, 5], w[:, 3] + w[:, 4]), _ratio(2.0 * w[:, 6], hits),
+            vmean, np.sqrt(np.maximum(0.0, _ratio(w[:, 10] / _FIX, nv) - vmean ** 2)),
+            omean, np.sqrt(np.maximum(0.0, _ratio(w[:, 13] / _FIX, no) - omean ** 2)),
+            _ratio(w[:, 11] / _FIX, no), a[:, 1:].max(1), cen, _ratio(m3, var ** 1.5), a[:, 4], a[:, 16])
+    return dict(zip(DESCRIPTORS, vals))
+
+
+def groove_distances(feat_a, feat_b, pair):
+    """Rhythmic distances per sequence of grooves a from grooves b, from the records and pair words of engine.groove_features ->
+    ``{name: (N,) float64}`` over DISTANCES (this package's own definitions): Hamming = cells whose hits differ; Fuzzy Hamming = Hamming -
+    near misses / 2 (a hit one step beside its target counts half); Jaccard = 1 - |both| / |either|; Velocity L2 = the 2-norm of the
+    velocity difference over all cells (0 where there is no hit); Offset RMS over the cells hit in both; Profile Cosine = 1 - the cosine of
+    the two velocity profiles.  A zero denominator gives 0."""
+    import numpy as np
+    fa, fb, p = _words(feat_a, 32), _words(feat_b, 32), _words(pair, 8)
+    union = p[:, 0] + p[:, 1]
+    norm = np.sqrt(fa[:, 15] * fb[:, 15])
+    vals = (p[:, 0], p[:, 0] - p[:, 2] / 2.0, np.where(union != 0, 1.0 - _ratio(p[:, 1], union), 0.0), np.sqrt(p[:, 3] / _FIX),
+            np.sqrt(_ratio(p[:, 4] / _FIX, p[:, 5])), np.where(norm != 0, 1.0 - _ratio(p[:, 6], norm), 0.0))
+    return dict(zip(DISTANCES, vals))
+
+
+def _table_stats(x):
+    import numpy as np
+    if x.size == 0:
+        return {k: 0.0 for k in TABLE_STATS}
+    q1, med, q3 = np.percentile(x, [25, 50, 75])
+    return {"mean": float(x.mean()), "std": float(x.std()), "min": float(x.min()), "max": float(x.max()), "median": float(med),
+            "q1": float(q1), "q3": float(q3)}
+
+
+def descriptor_table(desc_gt, desc_pred, dist=None, groups=None, names=None):
+    """The reference's descriptor table (get_stats_from_evaluator) from per-sequence descriptors -> ``{"Overall" | group name: {column:
+    ...}}``.  Columns: ``<name>__Ground_Truth`` and ``<name>__Prediction`` (and ``Distance::<name>`` for every entry of dist) hold
+    ``{mean, std, min, max, median, q1, q3}`` of the sample (std of the population; numpy.percentile in its linear default);
+    ``<name>__W1`` is one float, the mean absolute difference of the two sorted samples -- the 1-Wasserstein distance of the two empirical
+    distributions, which have the same N.  groups: N integer tags (a tag outside 0..n_groups - 1 is in "Overall" only); names: the group
+    names (default ``group<k>``, n_groups = the largest tag + 1).  An empty group holds zeros."""
+    import numpy as np
+    if set(desc_gt) != set(desc_pred):
+        raise ValueError("desc_gt and desc_pred must hold the same descriptors")
+    cols = {k: (np.asarray(desc_gt[k], np.float64).reshape(-1), np.asarray(desc_pred[k], np.float64).reshape(-1)) for k in desc_gt}
+    dist = {} if dist is None else {k: np.asarray(v, np.float64).reshape(-1) for k, v in dist.items()}
+    sizes = {len(v) for pr in cols.values() for v in pr} | {len(v) for v in dist.values()}
+    if len(sizes) != 1:
+        raise ValueError("every sample must hold one value per sequence, got sizes %s" % sorted(sizes))
+    n = sizes.pop()
+    sel = [("Overall", np.ones(n, bool))]
+    if groups is not None:
+        gid = (groups.cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)).astype(np.int64).reshape(-1)
+        if gid.shape[0] != n:
+            raise ValueError("groups needs one tag per sequence (%d), got %d" % (n, gid.shape[0]))
+        n_groups = len(names) if names is not None else max(1, int(gid.max()) + 1)
+        names = ["group%d" % k for k in range(n_groups)] if names is None else [str(s) for s in names]
+        if len(set(names)) != n_groups or "Overall" in names:
+            raise ValueError("names: distinct group names other than \"Overall\", got %r" % (names,))
+        sel += [(names[k], gid == k) for k in range(n_groups)]
+    res = {}
+    for gname, m in sel:
+        tab = {}
+        for k, (g, p) in cols.items():
+            tab[k + "__Ground_Truth"], tab[k + "__Prediction"] = _table_stats(g[m]), _table_stats(p[m])
+            tab[k + "__W1"] = float(np.abs(np.sort(g[m]) - np.sort(p[m])).mean()) if m.any() else 0.0
+        for k, v in dist.items():
+            tab["Distance::" + k] = _table_stats(v[m])
+        res[gname] = tab
+    return res
+
+
+def groove_table(model, hvo_pred, hvo_gt, groups=None, names=None, gt_feat=None):
+    """descriptor_table of predictions (N,32,27) beside their ground truth, with the distances of each prediction from its target: ONE
+    engine.groove_features call, ONE D2H copy of the integer records.  gt_feat: the ground truth's (N,32) records from an earlier call
+    (they stay on the device; the call then computes the predictions' records and the pair words only)."""
+    eng = model.engine
+    if gt_feat is None:
+        fa, fb, pw = eng.groove_features(hvo_pred, hvo_gt)
+    else:
+        fa, pw = eng.groove_features(hvo_pred, hvo_gt, feat_b=False)
+        fb = torch.as_tensor(gt_feat).to(fa.device)
+    host = torch.cat([fa, fb, pw], 1).cpu().numpy()
+    fa, fb, pw = host[:, :32], host[:, 32:64], host[:, 64:]
+    return descriptor_table(groove_descriptors(fb), groove_descriptors(fa), groove_distances(fa, fb, pw), groups=groups, names=names)
+
+
+def evaluate_descriptors(model, inputs, gt_hvo, groups=None, names=None, gt_feat=None, **predict_kwargs):
+    """The descriptor leg of the evaluation: predict the whole set on the device (chunked), one gt_groove_features call, one D2H copy of the
+    records, then descriptor_table.  predict_kwargs go to model.predict_hvo (use_thres, thres, voice_thresholds, ...)."""
+    pred = model.predict_hvo(inputs, **predict_kwargs)
+    return groove_table(model, pred, torch.as_tensor(gt_hvo), groups=groups, names=names, gt_feat=gt_feat)
