@@ -315,7 +315,12 @@ def run_ranks(fn, world, *args):
 
 
 # ---- GT_TRACE_DISPATCH=1 (csrc/gt_common.h; DESIGN.md "Dispatch trace"): "[dispatch] <family> key value ..." on stderr, one line per launch
-# (family "wgrad_queue": one per queued weight-gradient problem instead) -----------------------------------------------------------------
+# (family "wgrad_queue": one per queued weight-gradient problem instead).  GT_TRACE_DISPATCH=2, what trace_dispatch and the ledger ask for:
+# the same lines, the seq_fwd / seq_bwd ones with SEQ_INST_KEYS behind the level-1 keys ---------------------------------------------------
+TRACE_LEVEL = "2"
+# the instantiation kernel<DP, HDC, EXACT, ...> and the branches inside it: head-dim class, d_model equals its class, attention form (mfma /
+# mfma-pad / valu), the fused loss rides in this launch
+SEQ_INST_KEYS = ("hc", "exact", "attn", "loss")
 DISPATCH_KEYS = {
     "kernel": ("grid", "gy", "gz", "block"),
     "gemm_cfg": ("BM", "BN", "BK", "M", "N", "K", "form", "epi", "prec", "splitk", "row", "rowx", "edge"),
@@ -333,15 +338,16 @@ DISPATCH_KEYS = {
     "attn_bwd": ("kernel", "pairs"),
     "heads": ("M", "d", "prec", "loss"),
     "seq_pack": ("B", "d", "F", "L"),
-    "seq_fwd": ("phase", "split", "quad", "ride", "fuse_b0", "B", "d", "F", "L"),
-    "seq_bwd": ("phase", "split", "quad", "ride", "riders", "fuse_b0", "B", "d", "F", "L"),
+    "seq_fwd": ("phase", "split", "quad", "ride", "fuse_b0", "B", "d", "F", "L") + SEQ_INST_KEYS,
+    "seq_bwd": ("phase", "split", "quad", "ride", "riders", "fuse_b0", "B", "d", "F", "L") + SEQ_INST_KEYS,
     "seq_tail": ("kind", "B", "d", "F", "L"),
     "update": ("kind", "algo", "n"),
 }
 
 
 def parse_dispatch(stderr_text):
-    """[(family, {key: int | str})] of the "[dispatch]" lines in a captured stderr; every line must have exactly its family's documented keys."""
+    """[(family, {key: int | str})] of the "[dispatch]" lines in a captured stderr (a level-2 trace: TRACE_LEVEL); every line must have exactly
+    its family's documented keys."""
     out = []
     for ln in stderr_text.splitlines():
         if not ln.startswith("[dispatch] "):
@@ -355,7 +361,7 @@ def parse_dispatch(stderr_text):
 
 
 def trace_dispatch(fn):
-    """fn() with GT_TRACE_DISPATCH=1 and file descriptor 2 sent to a temporary file (the library writes the lines with fprintf: below
+    """fn() with GT_TRACE_DISPATCH=2 and file descriptor 2 sent to a temporary file (the library writes the lines with fprintf: below
     sys.stderr) -- works under pytest's capture and in a plain subprocess alike.  Returns (fn's result, parsed [dispatch] lines); whatever
     else arrived on stderr meanwhile is passed on, the trace lines too when fn raises."""
     import tempfile
@@ -365,7 +371,7 @@ def trace_dispatch(fn):
     text, failed = "", True
     with tempfile.TemporaryFile(mode="w+b") as tmp:
         os.dup2(tmp.fileno(), 2)
-        os.environ["GT_TRACE_DISPATCH"] = "1"
+        os.environ["GT_TRACE_DISPATCH"] = TRACE_LEVEL
         try:
             out = fn()
             failed = False
@@ -413,7 +419,7 @@ def ledger_append(trace):
 
 
 def ledger_call(fn):
-    """fn() under GT_TRACE_DISPATCH=1 with file descriptor 2 in a temporary file, as trace_dispatch runs it; its launches go to the ledger.
+    """fn() under GT_TRACE_DISPATCH=2 with file descriptor 2 in a temporary file, as trace_dispatch runs it; its launches go to the ledger.
     What arrived on stderr is passed on to file descriptor 2 afterwards -- the [dispatch] lines only where the caller had the trace on
     already (a capfd test, or an enclosing trace_dispatch, reads them there)."""
     import tempfile
@@ -423,7 +429,7 @@ def ledger_call(fn):
     text = ""
     with tempfile.TemporaryFile(mode="w+b") as tmp:
         os.dup2(tmp.fileno(), 2)
-        os.environ["GT_TRACE_DISPATCH"] = "1"
+        os.environ["GT_TRACE_DISPATCH"] = TRACE_LEVEL
         try:
             return fn()
         finally:
@@ -436,7 +442,7 @@ def ledger_call(fn):
             os.close(saved)
             tmp.seek(0)
             text = tmp.read().decode(errors="replace")
-            keep = old is not None and old[:1] == "1"
+            keep = old is not None and old[:1] in ("1", "2")
             rest = "".join(ln + "\n" for ln in text.splitlines() if keep or not ln.startswith("[dispatch] "))
             if rest:
                 os.write(2, rest.encode())

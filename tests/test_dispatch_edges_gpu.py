@@ -10,6 +10,7 @@ import time
 
 import pytest
 
+import harness
 import parity
 from harness import Runner, cfg_dict, dispatched, parse_dispatch
 from transformergrooveinfilling_amd import _lib
@@ -31,7 +32,7 @@ def _traced(capfd, request, *checks):
     """Run the checks (callables) with the dispatch trace (and the [gemm64] lines) on; returns (parsed [dispatch] lines, whole stderr).
     The environment and the process-wide schedule switches a Runner(seq=...) sets are put back whatever happens."""
     lib = _lib.get_lib()
-    os.environ["GT_TRACE_DISPATCH"] = "1"
+    os.environ["GT_TRACE_DISPATCH"] = harness.TRACE_LEVEL
     os.environ["GT_TRACE_GEMM64"] = "1"
     figures = {}
     t0 = time.time()
@@ -309,7 +310,7 @@ def test_seq_bucketed_backward_past_quad(capfd, request):
 
 def test_step_handoffs_stay_inside_their_call(capfd):
     """the GPU twin of tests/test_emu_kernels.py::test_step_handoffs_stay_inside_their_call (same shape, same launch sequences)"""
-    os.environ["GT_TRACE_DISPATCH"] = "1"
+    os.environ["GT_TRACE_DISPATCH"] = harness.TRACE_LEVEL
     try:
         parity.check_step_handoffs("hip", lambda: parse_dispatch(capfd.readouterr().err))
     finally:

@@ -3,6 +3,7 @@ libgroove_hip.so, compiled as host C++, checked against the oracle.  This is the
 sanitiser/debug build of the kernels -- the product never loads it.  Small shapes only."""
 import pytest
 
+import harness
 import parity
 from harness import cfg_dict
 
@@ -385,7 +386,7 @@ def test_dispatch_trace_shape(capfd):
     import numpy as np
     from harness import Runner, dispatched, parse_dispatch
     from oracle import numpy_groove as ng
-    os.environ["GT_TRACE_DISPATCH"] = "1"
+    os.environ["GT_TRACE_DISPATCH"] = harness.TRACE_LEVEL
     try:
         cfg = cfg_dict(128, 4, 64, 2, dropout=0.1)
         r = Runner(cfg, 2, "emu")
@@ -419,7 +420,7 @@ def test_step_handoffs_stay_inside_their_call(capfd):
     reaches no other call: parity.check_step_handoffs, launch by launch from the trace.  GPU twin: tests/test_dispatch_edges_gpu.py."""
     import os
     from harness import parse_dispatch
-    os.environ["GT_TRACE_DISPATCH"] = "1"
+    os.environ["GT_TRACE_DISPATCH"] = harness.TRACE_LEVEL
     try:
         parity.check_step_handoffs("emu", lambda: parse_dispatch(capfd.readouterr().err))
     finally:
@@ -435,7 +436,7 @@ def test_config_flag_no_ln_xchg_overrules_forced_exchange(capfd):
     from transformergrooveinfilling_amd import _lib
     lib = harness.emu_lib()
     gemms = ("gemm_cfg", "gemm32", "gemm32h", "gemm32row", "gemm64", "gemm64h")
-    os.environ["GT_TRACE_DISPATCH"] = "1"
+    os.environ["GT_TRACE_DISPATCH"] = harness.TRACE_LEVEL
     lib.cdll.gt_set_ln_exchange(1)
     try:
         capfd.readouterr()
@@ -460,7 +461,7 @@ def test_config_flag_no_quad(capfd):
     from oracle import numpy_groove as ng
     lib = harness.emu_lib()
     cfg = cfg_dict(128, 4, 64, 1)
-    os.environ["GT_TRACE_DISPATCH"] = "1"
+    os.environ["GT_TRACE_DISPATCH"] = harness.TRACE_LEVEL
     try:
         capfd.readouterr()
         r = harness.Runner(dict(cfg, dropout=0.1), 2, "emu")                   # (the control: one train step on the library's own choice)
@@ -495,7 +496,7 @@ def test_generic_large_tiles_with_edges_variant():
                           stdout=subprocess.DEVNULL)
     out = _emu_subprocess("parity.check_step('emu', cfg_dict(64, 4, 100, 1), 3, 0.2, seq=False)\n"
                           "parity.check_step_bf16('emu', cfg_dict(64, 4, 100, 1), 3, 0.2)\n",
-                          dict(GT_EMU_LIB_PATH=so, GT_TRACE_DISPATCH="1"))
+                          dict(GT_EMU_LIB_PATH=so, GT_TRACE_DISPATCH=harness.TRACE_LEVEL))
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-3000:]
     tr = parse_dispatch(out.stderr)
     for prec in (0, 1):

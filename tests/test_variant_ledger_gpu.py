@@ -9,6 +9,7 @@ import time
 import pytest
 
 import parity
+import seq_variants as sv
 import variant_ledger as vl
 from harness import cfg_dict, dispatched, trace_dispatch
 from transformergrooveinfilling_amd import _lib
@@ -27,12 +28,7 @@ def _switches_back():
     lib.cdll.gt_set_seq_ride(-1)
 
 
-def ran(trace, sig):
-    """the trace's lines with this signature: harness.dispatched on the keys the signature keeps as they are, signature() on the rest"""
-    tok = sig.split()
-    fam, kv = tok[0], {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in zip(tok[1::2], tok[2::2])}
-    exact = {k: v for k, v in kv.items() if k not in vl.COLLAPSE}
-    return [d for d in dispatched(trace, fam, **exact) if vl.signature(fam, d) == sig]
+ran = sv.ran
 
 
 def step(cfg, B, p=0.1, **kw):
@@ -130,7 +126,34 @@ def test_variant(case):
         trace = trace + own
     missing = [s for s in sigs if not ran(trace, s)]
     assert not missing, "not launched: %s\nlaunched: %s" % (missing, sorted(set(vl.signatures(trace))))
+    _time(case, t0)
+
+
+def _time(case, t0):
     times = os.environ.get("GT_VARIANT_LEDGER_TIMES")
     if times:
         with open(times, "a") as f:
             f.write("%s\t%.1f\n" % (case, time.time() - t0))
+
+
+# ---- the sequence-resident kernels by head class, form and fused loss (section [seq-universe] of the record): tests/seq_variants.py holds the
+# table -- its small cases run on the emulator build too (tests/test_seq_variants.py) -------------------------------------------------------
+@pytest.mark.parametrize("case", list(sv.CASES))
+def test_seq_variant(case):
+    t0 = time.time()
+    sv.check_trace(case, sv.run("hip", case))
+    _time("seq:" + case, t0)
+
+
+# the signatures of [seq-before] that table does not reach, each at the smallest shape of the enumeration that does (seq_variants.before_cases)
+BEFORE = sv.before_cases()
+
+
+@pytest.mark.parametrize("case", list(BEFORE))
+def test_seq_before(case):
+    spec, sigs = BEFORE[case]
+    t0 = time.time()
+    trace = sv.run("hip", spec, case)
+    for sig in sigs:
+        sv.check_lines(trace, sig)
+    _time("seq:" + case, t0)

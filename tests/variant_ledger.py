@@ -26,9 +26,10 @@ RECORD = os.path.join(ROOT, "profiles", "variant_ledger.txt")
 RERECORD = ("GT_VARIANT_LEDGER=<file> GT_VARIANT_LEDGER_TIMES=<times> python -m pytest tests -m gpu (on an MI355X), then "
             "python tests/variant_ledger.py <file> <times> > profiles/variant_ledger.txt")
 GAP_TESTS = "tests/test_variant_ledger_gpu.py"          # the cases written for the gaps: a signature only they run was uncovered before them
+SEQ_TESTS = GAP_TESTS + "::test_seq_"                   # ... and the ones written for the seq universe (test_seq_variant, test_seq_before)
 
 KEEP = ("BM", "BN", "BK", "form", "epi", "prec", "src", "splitk", "row", "rowx", "edge", "cls", "tail", "variant", "in16", "rpw", "kernel", "kind",
-        "algo", "split", "quad", "ride", "fuse_b0", "loss", "riders", "phase")
+        "algo", "split", "quad", "ride", "fuse_b0", "loss", "riders", "phase", "hc", "exact", "attn")
 KEEP_D = ("ln_fwd", "ln_bwd", "ln_param_reduce", "heads", "seq_pack", "seq_fwd", "seq_bwd", "seq_tail")
 COLLAPSE = dict(splitk=1, riders=0, phase=0)             # key -> the largest value that stays itself; anything above becomes that + 1
 
@@ -90,6 +91,99 @@ def grid_trace():
 def universe():
     """the set of signatures a configuration of the sweep grid can launch (dry trace: the emulator's 256 CUs, an MI355X's count)"""
     return set(grid_trace())
+
+
+# ---- the seq universe: the sequence-resident kernels at the resolution at which they are instantiated, off the sweep grid too ------------
+# The grid has no d_model 48 / 80 / 96 / 112 and forces no schedule, yet the C ABI reaches every instantiation the launchers of
+# groove_seq_fwd.hip / groove_seq_bwd.hip / groove_seq64.hip name.  Every (d_model, n_heads) seq_supported admits x the sizes below x the
+# library's schedule, SPLIT forced and SPLIT forbidden x every entry-point form that launches these kernels.
+SEQ_D = tuple(range(16, 129, 16))
+SEQ_F = (16, 48, 256, 512)
+SEQ_L = (1, 2)
+SEQ_B = (2, 65, 129)                              # 65 / 129: the far sides of the QUAD (4 B <= CUs) and SPLIT (2 B <= CUs) rules at 256 CUs
+SEQ_FORCE = ((), (("split", 1),), (("split", 0),))
+
+
+def seq_models():
+    """(d_model, n_heads) of every width 16 ... 128 and head count 1 ... 16 dividing it whose head_dim seq_supported admits"""
+    return [(d, H) for d in SEQ_D for H in range(1, 17) if d % H == 0 and (d // H < 16 or d // H in (16, 32, 64))]
+
+
+def seq_case_name(d, H, F, L, B, force=(), S=16):
+    return "d%d H%d F%d L%d+0 S%d B%d prec 0 flags 0%s" % (d, H, F, L, S, B, "".join(" %s %d" % kv for kv in force))
+
+
+def _seq_child():
+    """(child process: GT_EMU_DRY=1 GT_TRACE_DISPATCH=2) "## case" and the seq_* lines of every form, for every case of the enumeration"""
+    import ctypes
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    sys.path.insert(0, ROOT)
+    import dispatch_trace as dt
+    from transformergrooveinfilling_amd import _lib
+    lib = _lib.GrooveLib(os.environ.get("GT_EMU_LIB_PATH") or os.path.join(ROOT, "tests", "emu", "libgroove_emu.so"))
+    lib.cdll.gt_set_seq(1)                        # what harness.Runner sets
+    drv, s0, pen = dt.Driver(lib, True), ctypes.c_void_p(0), ctypes.c_float(0.5)
+    for d, H in seq_models():
+        for F in SEQ_F:
+            for L in SEQ_L:
+                for B in SEQ_B:
+                    cfg = _lib.make_config(B, 16, d, H, F, L, 0, dt.DROPOUT, 0, 0)
+                    cp, M = ctypes.byref(cfg), 32 * B
+                    total, _ = lib.param_layout(cfg)
+                    ws, state = drv.buf(lib.workspace_floats(cfg)), drv.state()
+                    params, grads, m, v = (drv.buf(total) for _ in range(4))
+                    pe, x, y, hvo, d_hvo, tgt, stats = drv.buf(32 * d), drv.buf(M * 16), drv.buf(M * 27), drv.buf(M * 27), drv.buf(M * 27), drv.buf(M * 27), drv.buf(8)
+                    c = lib.cdll
+                    step = lambda algo, skip: c.gt_train_step(cp, algo, params, grads, m, v, pe, x, y, pen, hvo, stats, tgt, ws, state, skip, s0)
+                    for force in SEQ_FORCE:
+                        for k, val in force:
+                            getattr(c, dt.SETTERS[k])(val)
+                        two = len(lib.grad_buckets(cfg)) == 2
+
+                        def forms():
+                            rc = [c.gt_workspace_init(cp, ws, s0), c.gt_forward(cp, params, pe, x, None, hvo, ws, state, 1, s0),
+                                  c.gt_loss(cp, hvo, y, pen, stats, d_hvo, s0), c.gt_backward(cp, params, grads, x, None, hvo, d_hvo, ws, state, 1, 0, s0),
+                                  c.gt_backward(cp, params, grads, x, None, hvo, d_hvo, ws, state, 1, 1, s0), step(0, 0), step(1, 0)]
+                            return rc + ([step(1, 2), step(1, 3)] if two else [])
+                        rcs, text = dt.traced(forms)
+                        for k, _ in force:
+                            getattr(c, dt.SETTERS[k])(-1)
+                        assert not any(rcs), (d, H, F, L, B, force, rcs, c.gt_last_error())
+                        print("## " + seq_case_name(d, H, F, L, B, force))
+                        print("\n".join(sorted({ln for ln in text.splitlines() if ln.startswith("[dispatch] seq_")})))
+                    drv.keep = []
+
+
+_seq = None
+
+
+def seq_trace():
+    """{seq_* signature: smallest case name that reaches it} over the enumeration above (dry: the emulator's 256 CUs; cached per process)"""
+    global _seq
+    if _seq is None:
+        from harness import emu_lib, parse_dispatch
+        emu_lib()
+        text = subprocess.run([sys.executable, os.path.abspath(__file__), "--seq-child"], check=True, stdout=subprocess.PIPE, universal_newlines=True,
+                              env=dict(os.environ, PYTHONPATH=ROOT, GT_EMU_DRY="1", GT_TRACE_DISPATCH="2")).stdout
+        found, name, memo = {}, None, {}
+        for ln in text.splitlines():
+            if ln.startswith("## "):
+                name = ln[3:]
+            elif ln.startswith("[dispatch] seq_"):
+                if ln not in memo:
+                    (fam, kv), = parse_dispatch(ln)
+                    memo[ln] = signature(fam, kv)
+                s = memo[ln]
+                if s not in found or shape_key(name) < shape_key(found[s]):
+                    found[s] = name
+        assert len(found) > 50, len(found)
+        _seq = found
+    return _seq
+
+
+def seq_universe():
+    """the set of seq_* signatures some configuration of the enumeration launches"""
+    return set(seq_trace())
 
 
 # ---- the record file ---------------------------------------------------------------------------------------------------------------
@@ -161,9 +255,32 @@ def write_record(recording, reasons, times, out):
     out.write("\n[off-grid]\n# %d signatures the suite ran that the grid cannot reach (forced switches, off-grid widths and batches): signature | tests | one of them\n" % len(off))
     for s in off:
         p(s, len(tests(s)), tests(s)[0] if tests(s) else "-")
-    out.write("\n[cases]\n# wall time of each gap case on an MI355X: case | seconds\n")
+    out.write("\n[cases]\n# wall time of each gap case on an MI355X (\"seq:\": a case of the seq universe): case | seconds\n")
     for k in sorted(times):
         p(k, "%.1f" % times[k])
+    # ---- the seq universe: the same four sections.  "Before": no test but the cases written for it (test_seq_variant, test_seq_before) ran it
+    seq = seq_trace()
+    mine = lambda t: t.startswith(SEQ_TESTS)
+    sbefore = [s for s in sorted(seq) if not [t for t in tests(s) if not mine(t)]]
+    sleft = [s for s in sbefore if not tests(s)]
+    out.write("\n[seq-universe]\n# signature | tests that ran it | one of them, or UNCOVERED | (UNCOVERED: smallest shape of the enumeration that reaches it | why it stays)\n")
+    for s in sorted(seq):
+        t = tests(s)
+        if t:
+            p(s, len(t), ([x for x in t if not mine(x)] or t)[0])
+        else:
+            p(s, 0, "UNCOVERED", seq[s], reasons.get(s, "NO REASON"))
+    out.write("\n[seq-before]\n# %d of %d signatures had no oracle case before %s*: signature | smallest shape that reaches it\n" % (len(sbefore), len(seq), SEQ_TESTS))
+    for s in sbefore:
+        p(s, seq[s])
+    out.write("\n[seq-closed]\n# %d of them closed: signature | the case that runs it\n" % (len(sbefore) - len(sleft)))
+    for s in sbefore:
+        if tests(s):
+            t = tests(s)
+            p(s, ([x for x in t if "::test_seq_variant[" in x] or t)[0])
+    out.write("\n[seq-remaining]\n# %d remain: signature | smallest shape | reason\n" % len(sleft))
+    for s in sleft:
+        p(s, seq[s], reasons.get(s, "NO REASON"))
 
 
 HEADER = """Variant ledger: every launch signature a configuration of the sweep grid can make the library launch, and the oracle case that ran it on an MI355X.
@@ -183,11 +300,25 @@ Sections: "universe", one line per signature; "before", the signatures no test r
 "closed", the case that now runs each; "remaining", what still has none, with the reason; "off-grid", signatures the suite runs that no grid shape
 reaches (forced switches, off-grid widths and batches, SGD: the grid's driver steps with Adam); "cases", the wall time of each new case.
 
+The seq universe ("seq-universe", "seq-before", "seq-closed", "seq-remaining": the same four sections) is the second universe, for the
+sequence-resident kernels alone at the resolution at which they are instantiated.  A seq_fwd / seq_bwd signature also names the head-dim class
+(hc), whether d_model equals its class 32 / 64 / 128 (exact), the attention form (attn: mfma, mfma-pad, valu) and whether the fused loss rides
+in the launch (loss).  Its shapes (tests/variant_ledger.py seq_trace(), dry): every (d_model, heads) pair the path admits -- d_model 16 ... 128
+in steps of 16, heads 1 ... 16 dividing it, head_dim < 16 or 16 / 32 / 64: 38 pairs, the widths 48 / 80 / 96 / 112 no grid has among them --
+x dim_feedforward 16 / 48 / 256 / 512 x 1 / 2 layers x batch 2 / 65 / 129 (the far sides of the QUAD and SPLIT rules at 256 CUs) x the
+library's schedule, gt_set_seq_split(1) and (0) x forward + loss + backward, gt_backward(accumulate 1), gt_train_step under SGD and Adam and
+the bucketed step (skip_update 2, 3) where gt_grad_buckets returns 2.  "seq-before": what no test but tests/test_variant_ledger_gpu.py's
+test_seq_variant (the table of tests/seq_variants.py) and test_seq_before (one case per remaining signature, at the smallest shape) had run.
+
+Whether those cases bite -- two mutations of csrc/gt_seq.h and what they did to them -- is in profiles/README.md, at this file's line.
+
 """
 
 
 def main(argv):
     import importlib
+    if argv[1:] == ["--seq-child"]:
+        return _seq_child()
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     gaps = importlib.import_module("test_variant_ledger_gpu")
     times = {}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """dispatch_trace.py -- the host dispatch of every entry-point form, over the shapes the dispatch rules split on, as one text.
 
-Drives the C ABI directly (no engine, no parity check) with GT_TRACE_DISPATCH=1 GT_TRACE_GEMM64=1 and prints, per shape and form, a
+Drives the C ABI directly (no engine, no parity check) with GT_TRACE_DISPATCH=2 GT_TRACE_GEMM64=1 and prints, per shape and form, a
 "## shape | form" marker followed by the library's trace lines.  Two builds that print the same text make the same launches in the same
 order: a change of host code that is meant to move no launch is checked by comparing this output before and after.
 
@@ -246,7 +246,7 @@ def run_group(name, dry):
 
 def run_grid(dry):
     """every group of grid_groups(), each in a child process; dry: all of them at once (host code only, one CPU each)"""
-    e = dict(os.environ, GT_TRACE_DISPATCH="1", GT_TRACE_GEMM64="1", **({"GT_EMU_DRY": "1"} if dry else {}))
+    e = dict(os.environ, GT_TRACE_DISPATCH="2", GT_TRACE_GEMM64="1", **({"GT_EMU_DRY": "1"} if dry else {}))
     cmd = lambda name: [sys.executable, os.path.abspath(__file__), "--group", name] + (["--dry"] if dry else [])
     names = list(grid_groups())
     if not dry:
@@ -276,7 +276,7 @@ def main():
         return run_grid(a.dry)
     seen = {}
     for name, (env, _, _) in groups(256).items():
-        e = dict(os.environ, GT_TRACE_DISPATCH="1", GT_TRACE_GEMM64="1", **env)
+        e = dict(os.environ, GT_TRACE_DISPATCH="2", GT_TRACE_GEMM64="1", **env)
         if a.dry:
             e["GT_EMU_DRY"] = "1"
         cmd = [sys.executable, os.path.abspath(__file__), "--group", name] + (["--dry"] if a.dry else [])

@@ -1147,6 +1147,28 @@ static SeqPlan seq_plan(const gt_config& c) {
   p.fuse_b0 = p.quad && p.ride && hd == 32;
   return p;
 }
+// The attention form a sequence-resident launch of this plan takes, for the dispatch trace only (nothing launches by it).  A RESTATEMENT of
+// two kernel-side rules of gt_seq.h -- keep it in step with them: SeqHd<HDC>::PAD (class 0, head_dim < 16: the zero-padded MFMA form) and the
+// `vattn` / `va` condition of seq_fwd_kernel / seq_bwd_kernel (the vector-ALU form: the SPLIT kernels of DP 32 / 64 with 16 heads of DP / 16).
+static const char* seq_attn_form(const gt_config& c, const SeqPlan& p) {
+  if (p.hc != 0) return "mfma";
+  const bool valu = p.split && (c.d_model == 32 || c.d_model == 64) && c.n_heads == 16;      // (head_dim == DP / 16 follows)
+  return valu ? "valu" : "mfma-pad";
+}
+// d_model equals its class (kernel<DP, HDC, EXACT>: DP 32 / 64 / 128) -- the trace's "exact"
+static int seq_exact(const gt_config& c) { return c.d_model == 32 || c.d_model == 64 || c.d_model == 128; }
+// The tail of a seq_fwd / seq_bwd trace line: " hc <class> exact <0/1> attn <form> loss <0/1>" at GT_TRACE_DISPATCH=2, nothing at 1 -- whoever
+// reads the level-1 trace (its keys are checked one by one by the readers that exist) sees the lines it always saw.
+struct SeqInst { char s[64]; };
+// quad_b0: the QUAD launch of backward phase 0 -- ONE instantiation, <128, 32, true, true, true>, for every head class (gt_seq_launch_bwd), and
+// no attention in that phase: the line names what is launched, "hc 32 ... attn none", not the plan's class.
+static SeqInst seq_inst(const gt_config& c, const SeqPlan& p, bool loss, bool quad_b0 = false) {
+  SeqInst t;
+  t.s[0] = 0;
+  if (gt_dispatch_level() >= 2)
+    snprintf(t.s, sizeof(t.s), " hc %d exact %d attn %s loss %d", quad_b0 ? 32 : p.hc, seq_exact(c), quad_b0 ? "none" : seq_attn_form(c, p), (int)loss);
+  return t;
+}
 // What a fused train step hands to its forward and takes back from it (train_step_impl; gt_forward passes none).
 struct FwdStep {
   // in: the loss to take along in the launch that runs the output layer (y == nullptr: none), and GT_STEP_PACKS_CURRENT -- the
@@ -1226,8 +1248,10 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
       SeqArgs ap = a;
       ap.phase = p;
       if (p > (a.quad_pro ? -1 : 0)) gt_prof_tag("seq_fwd", 0.0, 0.0);          // (flops and bytes of the whole forward are on the first phase's tag)
-      gt_dispatch("seq_fwd phase %d split 1 quad %d ride %d fuse_b0 %d B %d d %d F %d L %d", p, sp.quad, sp.ride, fuse_b0 && p == x.c.n_enc_layers - 1,
-                  x.c.batch, x.d, x.F, x.c.n_enc_layers);
+      // (hc exact attn: the instantiation and the attention form; loss: this launch runs the output layer and takes the fused loss along)
+      gt_dispatch("seq_fwd phase %d split 1 quad %d ride %d fuse_b0 %d B %d d %d F %d L %d%s", p, sp.quad, sp.ride,
+                  fuse_b0 && p == x.c.n_enc_layers - 1, x.c.batch, x.d, x.F, x.c.n_enc_layers,
+                  seq_inst(x.c, sp, a.loss_y != nullptr && p == x.c.n_enc_layers - 1).s);
       if (fuse_b0 && p == x.c.n_enc_layers - 1) {
         ap.fuse_b0 = 1;
         gt_seq_launch_fb(ap, 4 * x.c.batch, x.s);
@@ -1238,7 +1262,8 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
     }
     return 0;
   }
-  gt_dispatch("seq_fwd phase 0 split 0 quad 0 ride 0 fuse_b0 0 B %d d %d F %d L %d", x.c.batch, x.d, x.F, x.c.n_enc_layers);
+  gt_dispatch("seq_fwd phase 0 split 0 quad 0 ride 0 fuse_b0 0 B %d d %d F %d L %d%s", x.c.batch, x.d, x.F, x.c.n_enc_layers,
+              seq_inst(x.c, sp, a.loss_y != nullptr).s);
   gt_seq_launch_fwd(a, x.d, sp.hc, false, x.c.batch, x.s);
   return 0;
 }
@@ -1285,7 +1310,9 @@ static int seq_backward(const Ctx& x, const float* xin, int accumulate, int phas
       SeqArgs ap = a;
       ap.phase = p;
       if (p > p_lo && !(b0_done && p == 1)) gt_prof_tag("seq_bwd", 0.0, 0.0);
-      gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d", p, p == 0 && sp.quad, p == 0 ? 0 : R, b0_done, B, d, x.F, L);
+      // (loss 0: no backward launch carries the loss -- the key is there so that both families read alike)
+      gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d%s", p, p == 0 && sp.quad,
+                  p == 0 ? 0 : R, b0_done, B, d, x.F, L, seq_inst(x.c, sp, false, p == 0 && sp.quad).s);
       // phase 0 has no riders: four workgroups per sequence there (column partners, gt_seq.h QUAD) while they fit the chip
       if (p == 0 && sp.quad) gt_seq_launch_bwd(ap, d, sp.hc, true, 2 * a.nseq, x.s, true);
       else gt_seq_launch_bwd(ap, d, sp.hc, true, a.nseq + (p == 0 ? 0 : R), x.s);
@@ -1315,7 +1342,8 @@ static int seq_backward(const Ctx& x, const float* xin, int accumulate, int phas
     SeqArgs ap = a;
     ap.phase = p;
     if (p > 0) gt_prof_tag("seq_bwd", 0.0, 0.0);
-    gt_dispatch("seq_bwd phase %d split %d quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d", p, sp.split, B, d, x.F, L);
+    gt_dispatch("seq_bwd phase %d split %d quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d%s", p, sp.split, B, d, x.F, L,
+                seq_inst(x.c, sp, false).s);
     gt_seq_launch_bwd(ap, d, sp.hc, sp.split, nwg, x.s);
   }
   wgrad(x, ws + W.dlogits, GT_TGT, ws + W.memory, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);

@@ -101,7 +101,10 @@ static inline void gt_prof_tag(const char* label, double flops, double bytes) {
 // more than the grid describes its launch with gt_dispatch() just before it; gt_launch() prints a "kernel" line for every launch nobody
 // described, so the number of lines without the "wgrad_queue" family (queued problems, gt_dispatch_note) IS the number of launches.
 extern thread_local bool g_dispatch_named;                   // the next launch has its line already
-static inline bool gt_dispatch_on() { const char* e = getenv("GT_TRACE_DISPATCH"); return e && e[0] == '1'; }
+// GT_TRACE_DISPATCH=2: the same lines, and the seq_fwd / seq_bwd ones go on with the kernel instantiation and the branches inside it
+// (" hc .. exact .. attn .. loss ..", seq_inst in groove_hip.hip); level 1 stays what its readers parse key by key.
+static inline int gt_dispatch_level() { const char* e = getenv("GT_TRACE_DISPATCH"); return !e ? 0 : e[0] == '1' ? 1 : e[0] == '2' ? 2 : 0; }
+static inline bool gt_dispatch_on() { return gt_dispatch_level() > 0; }
 __attribute__((format(printf, 2, 3))) static inline void gt_dispatch_line(bool names_launch, const char* fmt, ...) {
   char line[320];
   va_list ap;
