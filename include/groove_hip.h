@@ -493,33 +493,14 @@ int gt_infill_merge_cells(const float* hvo_pred, const float* hvo_in, const uint
  * HIP events on its own stream.  gt_profile_report synchronises and writes one text row per kernel
  * class: "label launches total_ms total_flops total_bytes".  Not graph-capturable while on. */
 int gt_profile_enable(int on);
-/* Sequence-resident kernels (csrc/gt_seq.h): for encoder-only fp32 models with d_model <= 128 (% 16), dim_feedforward <= 512
- * (% 16), src_dim <= 32 and head_dim 16 / 32 / 64 or below 16, ONE workgroup per sequence runs the whole forward (and one the
- * whole backward) in a single launch -- or, in the SPLIT mode below, two workgroups per sequence and one launch per layer and
- * direction; gt_step_launches() gives the launch count of a train step.  Default (neither this call nor env GT_SEQ): d_model <= 64
- * and d_model == 128 always, the other widths of the 128 class from batch 64 up.  on = 1 forces them wherever supported, on = 0
- * switches them off (env GT_SEQ=1 / GT_SEQ=0 do the same).  Same results as the one-kernel-per-op path to fp32 rounding. */
-int gt_set_seq(int on);
-/* Two workgroups per sequence (16 token rows each) and one launch per layer and direction for the sequence-resident kernels at
- * d_model 128 or 32: -1 = default (when 2 x batch workgroups fit the CUs once; d_model 32 only with dim_feedforward >= 256), 0 = off,
- * 1 = on (env GT_SEQ_SPLIT=0/1 does the same).  Same results bit for bit: the split is over token rows. */
-int gt_set_seq_split(int on);
-/* FOUR workgroups per sequence in the forward of the SPLIT mode at d_model 128 (csrc/gt_seq.h, QUAD): the two workgroups of a 16-row
- * half are column partners that each compute half of dim_feedforward and swap their partial FFN2 results through one in-launch pair
- * exchange per layer (8-byte tagged granules, agent-scope stores / loads) -- the forward then fills 4 x batch CUs instead of 2 x batch.
- * -1 = default (whenever 4 x batch workgroups fit the CUs at once and dim_feedforward % 32 == 0), 0 = off, 1 = on under the same
- * condition (env GT_SEQ_QUAD=0/1).  Results agree with the SPLIT mode to fp32 rounding (the FFN2 contraction is summed as two halves);
- * bitwise repeatable run to run.  Needs gt_workspace_init on the workspace. */
-int gt_set_seq_quad(int on);
 /* The pair exchange polls with a bound: a partner workgroup that never arrives (the two were not resident at the same time: another
  * stream's kernel, a CU mask, another process holds CUs) makes the waiting workgroup give up, raise the error word at the head of the
  * "seq_xchg" workspace region (gt_ws_find) and go on with garbage partials.  Fail-safe (round 5): with the word set -- it stays set until
  * the host zeroes the region with gt_workspace_init -- the fused update (gt_train_step, gt_optimizer_step_ws) leaves parameters and
  * optimizer moments untouched and only clears the consumed gradients; the same when gradient element n_floats - 1 (padding behind the
  * 27-float output bias; a data-parallel host writes its error flag there before the all-reduce) is non-zero, so every rank skips
- * together.  gt_set_xchg_spin_max: polls before giving up (<= 0: the default, 2^22 = seconds; tests lower it). */
-int gt_set_xchg_spin_max(int polls);
-/* "xchg_err" (gt_ws_find) = two 32-bit words at the head of whichever exchange region a shape has: [0] the error word, [1] the number of
+ * together.  (The bound: 2^22 polls = seconds.)
+ * "xchg_err" (gt_ws_find) = two 32-bit words at the head of whichever exchange region a shape has: [0] the error word, [1] the number of
  * updates skipped because of it (or of a data-parallel guard) since the last gt_workspace_init.
  * Data-parallel hosts: grads[n_floats - 1] = 1 if this workspace's exchange error word is set, else 0 -- enqueue between the backward
  * (gt_train_step(skip_update = 1 / 2)) and the gradient all-reduce; a no-op for shapes without an exchange region. */
@@ -559,47 +540,16 @@ typedef struct gt_opt_hparams {
 } gt_opt_hparams;
 int gt_optimizer_prepare(const gt_config* cfg, int algo, float* params, float* grads, float* mbuf, const float* ws,
                          const gt_step_state* state, const gt_opt_hparams* hp, gt_stream_t stream);
-/* LayerNorm inside the producing Linear / dgrad (csrc/gt_gemm64.h, round 5): at d_model 256 / 512, where the 64 x 64-tile kernels apply and
- * the whole grid is resident at once (a GPU's share of a data-parallel batch: 2048 tokens), the N / 64 workgroups of a row block exchange
- * their row partials inside the launch (tagged 8-byte granules, agent-scope stores / polling loads; "rowx" workspace region, zeroed once
- * by gt_workspace_init) and each normalises its own tile -- no row pass of its own.  -1 = default (on where it applies: 3/4 .. 2 tiles of 64 x 64 per CU), 0 = off (env GT_LN_XCHG=0): the norm as a
- * row pass of its own; 1-1.5 % of the step at 2048 tokens (csrc/groove_hip.hip, ln_xchg).  Same
- * bounded-spin / error-word / skipped-update contract as the pair exchange above ("xchg_err" names the word of whichever a shape has). */
-int gt_set_ln_exchange(int on);
-/* Test aid: nblocks workgroups that each pin 96 KB of LDS (no sequence workgroup fits beside one) for `usec` microseconds -- a second
- * stream holding CUs while a four-workgroups-per-sequence launch is in flight. */
-int gt_debug_occupy_cus(int nblocks, int usec, gt_stream_t stream);
-/* gt_config.precision = 1 (BASELINE configs[4]) at d_model 256 / 512 with every Linear of a layer on the big-tile kernel: bf16 copies of
- * the GEMM operands.  The producers of every activation / gradient a Linear, dgrad or weight gradient of an encoder layer consumes write
- * it in bf16 (8 tensors per layer), a per-step kernel writes bf16 copies of the layers' weights and of their transposes, and the GEMMs
- * stage those (csrc/gt_gemm32.h gemm32h_kernel: half the bytes per flop).  level 1: the copies sit BESIDE the fp32 tensors; level 2 (the
- * default): the tensors nothing but a GEMM reads -- ctx, hact, dhid, dqkv, the dropout-masked dz copies -- are stored in bf16 ALONE (the
- * reference's torch autograd keeps the same intermediates, in fp32: nothing of its interface sees them).  0: off.  -1: the environment
- * (GT_BF16_SHADOWS=0/1/2) or the default.  Outputs, losses and gradients are bit-identical at every level.  Changes gt_workspace_bytes and
- * which gt_ws_find names are live: set it before sizing a workspace.  gt_operand_shadow_level: the level in force for a configuration. */
-int gt_set_operand_shadows(int level);
-/* Bumped by every call that changes a switch the workspace layout depends on (today: gt_set_operand_shadows).  A host that keeps workspaces
- * across calls compares it with the value it saw when it sized them and re-makes them on a mismatch (StepEngine.slot does). */
+/* The process-wide schedule switches (gt_set_*) and the test / measurement aids (gt_debug_*) are declared in groove_hip_debug.h: no host
+ * that trains or predicts needs them.  What such a host may have to ASK stays here. */
+/* Advances whenever the level in force of a switch the workspace layout depends on changes (today: the bf16 operand shadows).  A host that keeps
+ * workspaces across calls compares it with the value it saw when it sized them and re-makes them on a mismatch (StepEngine.slot does). */
 int gt_layout_epoch(void);
+/* The level of bf16 operand shadows in force for a configuration: 0 none, 1 beside the fp32 tensors, 2 (the default where precision >= 1 applies
+ * them) the GEMM-only tensors stored in bf16 ALONE -- which decides gt_workspace_bytes and which gt_ws_find names are live. */
 int gt_operand_shadow_level(const gt_config* cfg);
 /* The precision a configuration really runs at: 2 only where gt_config.precision = 2 applies (see there), else 1 / 0. */
 int gt_precision_in_force(const gt_config* cfg);
-/* Weight gradients as RIDER workgroups (csrc/gt_seq_wg.h): in the SPLIT mode at d_model 128 the backward phases' launches carry, on
- * the CUs their 2 x batch sequence workgroups leave idle, the weight gradients whose operands the earlier phases completed; one
- * workgroup owns a 32 x 64 gradient tile over ALL tokens (no atomics: bitwise reproducible), and a tail launch does what cannot ride
- * (layer 0's in-proj, the input layer), the LayerNorm parameter gradients and the step-counter bump.  -1 = default (when at least 64
- * CUs are idle beside the sequence workgroups), 0 = off (the grouped dispatch at the end of backward), 1 = on wherever supported
- * (env GT_SEQ_RIDE=0/1 does the same).  Same results to fp32 rounding (another summation order over the tokens). */
-int gt_set_seq_ride(int on);
-/* Measurement aid (tools/wg_unit_bench.py): the rider units of backward phase `phase` as a launch of their own (token range split
- * `ksplit` ways), ADDING into grads; operands = what the last backward on this workspace left there. */
-int gt_debug_seq_wg_phase(const gt_config* cfg, const float* params, float* grads, const float* x, float* ws, int phase, int ksplit,
-                          gt_stream_t stream);
-/* Bitwise-reproducible weight gradients: each output tile of a weight gradient is owned by ONE workgroup that walks all tokens
- * (no split over the token dimension), so the fp32 atomic adds have a single contributor per element.  Everything else of the
- * step is reproducible already (fixed-order reductions).  Off by default: the small shapes lose their token parallelism
- * (env GT_DETERMINISTIC=1 does the same). */
-int gt_set_deterministic(int on);
 /* Kernel launches of one gt_train_step for this configuration when it runs on the sequence-resident path (7 whole-sequence; SPLIT: 2 L + 4 with rider weight gradients, 2 L + 6
  * without; one less with GT_STEP_PACKS_CURRENT), 0 when
  * it runs one kernel per operation (dozens to hundreds).  A host that replays the step as a captured hipGraph can use it to

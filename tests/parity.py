@@ -306,8 +306,8 @@ def _deterministic(lib, on):
         try:
             yield
         finally:
-            if on:                                   # (back to what the environment asks for: the library's default)
-                lib.cdll.gt_set_deterministic(1 if os.environ.get("GT_DETERMINISTIC", "")[:1] == "1" else 0)
+            if on:                                   # (unset: back to what the environment asks for, else the library's default)
+                lib.cdll.gt_set_deterministic(-1)
     return cm()
 
 

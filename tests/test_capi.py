@@ -22,9 +22,11 @@ def lib():
 
 
 def test_exports_every_declared_symbol(lib):
-    hdr = open(os.path.join(ROOT, "include", "groove_hip.h")).read()
-    declared = set(re.findall(r"\b(gt_[a-z_]+)\s*\(", hdr))
+    public, debug = (open(os.path.join(ROOT, "include", h)).read() for h in ("groove_hip.h", "groove_hip_debug.h"))
+    declared = set(re.findall(r"\b(gt_[a-z_]+)\s*\(", public + debug))
     assert declared == set(_lib.EXPORTS)
+    # the contract declares no process-wide switch and no test aid: those live in the debug header
+    assert re.findall(r"\b(gt_(?:set|debug)_[a-z_]+)\s*\(", public) == []
     for name in declared:
         assert hasattr(lib.cdll, name), name
     assert lib.cdll.gt_version() >= 1

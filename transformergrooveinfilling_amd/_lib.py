@@ -1,4 +1,5 @@
-"""ctypes binding of libgroove_hip.so (C ABI declared in include/groove_hip.h).
+"""ctypes binding of libgroove_hip.so (C ABI declared in include/groove_hip.h; the process-wide gt_set_* switches and the
+gt_debug_* aids in include/groove_hip_debug.h).
 
 The product path has NO CPU fallback: if the HIP library is missing this module raises, it never
 substitutes another implementation.  (tests/ may call ``load(path)`` with the host-emulator build

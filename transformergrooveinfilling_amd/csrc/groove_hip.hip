@@ -231,20 +231,16 @@ static bool seq_supported(const gt_config& c);
 // instead of 4 (+ 2), every consumer (Linear, dgrad, weight gradient, the FFN2 dgrad's zero test of hact) takes the bf16 tensor.  Outputs,
 // losses and gradients are bit for bit those of level 0 / 1 (the fp32-source GEMMs round the same values at fragment assembly):
 // C5 bs 512 4.06 -> 3.6 ms.  gt_ws_find names the bf16 tensors "<name>16"; the fp32 regions of those six stay allocated, unwritten.
-static int g_bf16_shadows = -1;
-// every change of a switch the workspace LAYOUT depends on bumps this counter: a host that caches workspaces compares it before it reuses one
-// (StepEngine.slot re-makes the slot: offsets move with the shadow level, and a workspace sized for another level is too small or mis-read)
+static int bf16_shadow_level() { return (int)gt_switch(GT_SW_OPERAND_SHADOWS); }
+// every change of the shadow level IN FORCE -- the one switch the workspace LAYOUT depends on -- bumps this counter: a host that caches workspaces
+// compares it before it reuses one (StepEngine.slot re-makes the slot: offsets move with the level, and a workspace sized for another is too small or mis-read)
 static int g_layout_epoch = 0;
 extern "C" int gt_layout_epoch() { return g_layout_epoch; }
 extern "C" int gt_set_operand_shadows(int level) {
-  const int nv = level < 0 ? -1 : level > 2 ? 2 : level;
-  if (nv != g_bf16_shadows) ++g_layout_epoch;
-  g_bf16_shadows = nv;
+  const int was = bf16_shadow_level();
+  gt_switch_set(GT_SW_OPERAND_SHADOWS, level > 2 ? 2 : level);
+  if (bf16_shadow_level() != was) ++g_layout_epoch;
   return 0;
-}
-static int bf16_shadow_level() {
-  if (g_bf16_shadows < 0) { const char* e = getenv("GT_BF16_SHADOWS"); g_bf16_shadows = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }
-  return g_bf16_shadows;
 }
 // precision = 1 where the shadows do not apply: fp32 W^T copies of the encoder layers' matrices, so that the dgrads run in the NT form
 // (results: the same products, summed in the NT kernel's k order)
@@ -553,7 +549,7 @@ static void wgrad(const Ctx& x, const float* dY, int ldy, const float* X, int ld
   if (x.wb) wgrad_queue(*x.wb, g, x.s);
   else gemm_launch<true, true, EPI_ATOMIC>(g, x.s);
 }
-extern "C" int gt_set_deterministic(int on) { g_deterministic = on != 0; return 0; }
+extern "C" int gt_set_deterministic(int on) { return gt_switch_set_flag(GT_SW_DETERMINISTIC, on); }
 
 // dX = dY W   ("NN")
 // out16 (precision = 2): the result stored in bf16 ALONE at out16 (dense rows of N); dX is then not written
@@ -603,19 +599,13 @@ static void dgrad_store(const Ctx& x, const float* dY, int ldy, const float* W, 
 // (tagged granules, coalesced); the three-hop "data, drain, ready word" form was neutral (1.494 vs 1.494, bf16 0.984 vs 0.968), a first form with
 // per-row granules (16 scattered polls per lane) cost 13 us per launch (1.811 ms).  C3 (d_model 256, 8192 tokens): 5.20 ms on the row-owning tiles, 5.29
 // on 64x64 tiles + row pass, 5.44 with the three-hop exchange, 5.06 with this one (row_fused below).
-static int g_ln_xchg = -1;
-extern "C" int gt_set_ln_exchange(int on) { g_ln_xchg = on < 0 ? -1 : on != 0; return 0; }
+extern "C" int gt_set_ln_exchange(int on) { return gt_switch_set_flag(GT_SW_LN_XCHG, on); }
 static int seq_cu_count();
 static int xchg_cus();
-static int g_xchg_spin_max = 0;
 // polling bound of an in-launch exchange: gt_set_xchg_spin_max's while positive, else the exchange's compiled default
-static int xchg_spin_max(int dflt) { return g_xchg_spin_max > 0 ? g_xchg_spin_max : dflt; }
+static int xchg_spin_max(int dflt) { const long v = gt_switch(GT_SW_XCHG_SPIN_MAX); return v > 0 ? (int)v : dflt; }
 // 0 = off, 1 = on where it applies (the default), 2 = forced (gt_set_ln_exchange(1) / GT_LN_XCHG=1: no lower bound on the tile count -- tests)
-static int ln_xchg_mode() {
-  if (g_ln_xchg >= 0) return g_ln_xchg ? 2 : 0;
-  static const int env = [] { const char* e = getenv("GT_LN_XCHG"); return !e ? 1 : e[0] == '0' ? 0 : 2; }();
-  return env;
-}
+static int ln_xchg_mode() { const long v = gt_switch(GT_SW_LN_XCHG); return v < 0 ? 1 : v ? 2 : 0; }
 static bool ln_xchg(const Ctx& x) { return ln_xchg_mode() != 0 && !(x.c.flags & GT_CFG_NO_LN_XCHG) && x.W.rowx >= 0; }
 static void ln_xchg_args(const Ctx& x, GemmArgs& g) {
   g.rowx = reinterpret_cast<unsigned*>(x.ws + x.W.rowx);
@@ -624,10 +614,8 @@ static void ln_xchg_args(const Ctx& x, GemmArgs& g) {
 // which geometry the row exchange runs on for this (M, N): 64 = the 64x64 kernels of gt_gemm64.h, 128 = the big tile (round 6), 0 = none
 static int ln_xchg_tile(const GemmArgs& g) {
   if (gemm64_ln_shape(g, xchg_cus(), ln_xchg_mode() == 2)) return 64;
-  static const bool off128 = [] { const char* e = getenv("GT_LN_XCHG128"); return e && e[0] == '0'; }();     // (A/B switches)
-  static const bool off32 = [] { const char* e = getenv("GT_LN_XCHG32"); return e && e[0] == '0'; }();
-  if (!off128 && gemm32_ln_shape(g, xchg_cus())) return 128;
-  return (!off32 && gemm_xln32_shape(g, xchg_cus())) ? 32 : 0;
+  if (gt_switch(GT_SW_LN_XCHG128) && gemm32_ln_shape(g, xchg_cus())) return 128;     // (A/B switches)
+  return (gt_switch(GT_SW_LN_XCHG32) && gemm_xln32_shape(g, xchg_cus())) ? 32 : 0;
 }
 // Which kernel takes the Linear / dgrad g with the LayerNorm (EPI_RES_LN) / its backward (EPI_RES_LNBWD) in its epilogue: the ONE statement of that rule
 // (linear_res_ln and dgrad_lnbwd pick, then run).  H: bf16-source, both operand shadows; else fp32-source -- not for a bf16-ONLY input (in_only16).
@@ -895,7 +883,7 @@ static void attention_bwd(const Ctx& x, const float* q, int ldq, const float* k,
   gt_prof_tag("attn_bwd", 10.0 * x.M * 32 * x.d, 4.0 * (7.0 * x.M * x.d + 1024.0 * x.c.batch * x.H));
   const dim3 grid(x.c.batch * x.H);
   // head_dim 64 with the chip full: the LDS-staged form (every operand byte requested once, 16 bytes at a time)
-  static const int lds_min = [] { const char* e = getenv("GT_ATTN_BWD_LDS_MIN"); return e ? atoi(e) : GT_ATTN_BWD_LDS_MIN; }();
+  const int lds_min = (int)gt_switch(GT_SW_ATTN_BWD_LDS_MIN, GT_ATTN_BWD_LDS_MIN);
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (in16) {                                        // precision = 2: q / k / v / dctx stored in bf16 alone, widened on their way into LDS
     a.q16 = reinterpret_cast<const uint16_t*>(q); a.k16 = a.q16 + (k - q); a.v16 = a.q16 + (v - q); a.dctx16 = reinterpret_cast<const uint16_t*>(dctx);
@@ -1003,8 +991,7 @@ static GemmArgs ffn2d_args(const Ctx& x, const LayerP& p, const LayerW& w, const
 // write / read them (gemm32_store_epilogue), so BOTH launches must be on one: decided here, from the two argument blocks, for the
 // forward and the backward alike.  GT_FFN_KBITS=0: off.
 static uint16_t* ffn_kbits(const Ctx& x, const LayerP& p, const LayerW& w, const float* xin, int gl) {
-  static const bool on = [] { const char* e = getenv("GT_FFN_KBITS"); return !(e && e[0] == '0'); }();
-  if (!on || x.W.kbits < 0 || x.M % 32 != 0) return nullptr;
+  if (!gt_switch(GT_SW_FFN_KBITS) || x.W.kbits < 0 || x.M % 32 != 0) return nullptr;
   bool ok1, ok2, nt;
   const GemmArgs a = ffn1_args(x, p, w, xin, gl, &ok1);
   const Tmp t = tmp_set(x, gl);
@@ -1037,23 +1024,15 @@ static int self_attn_fwd(const Ctx& x, const LayerP& p, const LayerW& w, const f
 }
 
 // ---- sequence-resident kernels (gt_seq.h): one workgroup per sequence walks the whole encoder -------------------------------
-// g_seq: 0 = off (GT_SEQ=0 / gt_set_seq(0)), 1 = every supported shape (GT_SEQ=1 / gt_set_seq(1): tests), 2 = by measurement (default):
+// GT_SW_SEQ: 0 = off (GT_SEQ=0 / gt_set_seq(0)), 1 = every supported shape (GT_SEQ=1 / gt_set_seq(1): tests), unset = by measurement (default):
 // always at d_model <= 64 (C1 1.9x, ClosedHH YAML 1.15x over one kernel per op) and at d_model 128 (two workgroups per sequence
 // while they fit the chip: bs 16 1.11x, 64 1.18x, 128 1.36x; one per sequence beyond: bs 192 1.53x); at the other widths of the
 // 128 class a sequence's matmuls are bound by the fp32 MFMA rate of the ONE CU its workgroup runs on: from 64 sequences per GPU up.
-static int g_seq = -1;
-extern "C" int gt_set_seq(int on) { g_seq = on != 0; return 0; }
+extern "C" int gt_set_seq(int on) { return gt_switch_set_flag(GT_SW_SEQ, on); }
 // SPLIT mode (d_model 128, and d_model 32 with dim_feedforward >= 256): 2 x batch workgroups of 16 token rows, one launch per layer
 // and direction (+1).  Default (-1): when the pairs fit the chip once (2 x batch <= CUs) -- there a sequence per CU leaves most of
 // the MFMA rate idle.
-static int g_seq_split = -1;
-extern "C" int gt_set_seq_split(int on) { g_seq_split = on < 0 ? -1 : on != 0; return 0; }
-// a three-state schedule switch (g_seq_split / g_seq_ride / g_seq_quad): its setter's value, else the environment's -- read while the switch
-// is unset and then kept in it -- else -1: by shape
-static int seq_switch(int& sw, const char* env) {
-  if (sw < 0) { const char* e = getenv(env); if (e) sw = e[0] != '0'; }
-  return sw;
-}
+extern "C" int gt_set_seq_split(int on) { return gt_switch_set_flag(GT_SW_SEQ_SPLIT, on); }
 // CUs of the CURRENT device (the caller's torch device; cached per device ordinal: a process may drive several GPUs)
 static int seq_cu_count() {
 #ifdef GT_EMU
@@ -1083,7 +1062,7 @@ static int xchg_cus() {
 }
 static bool seq_split(const gt_config& c) {
   if (c.d_model != 128 && c.d_model != 32 && c.d_model != 64) return false;
-  if (seq_switch(g_seq_split, "GT_SEQ_SPLIT") >= 0) return g_seq_split != 0;
+  if (const long sw = gt_switch(GT_SW_SEQ_SPLIT); sw >= 0) return sw != 0;
   // d_model 32 / 64 by shape.  With 16 heads (head_dim 2 / 4) ALWAYS: these kernels alone have the vector-ALU attention, which the zero-padded MFMA
   // form of the whole-sequence kernels loses to at every F (round 6: d32 / H16 / F 64 0.222 -> 0.162 ms, F 128 0.232 -> 0.169; the ClosedHH YAML
   // and the reference CLI's default shape -- d64 / H16 / F 256: 0.370 -> 0.260 -- are the wide end of the same family).  Otherwise only where a
@@ -1094,10 +1073,9 @@ static bool seq_split(const gt_config& c) {
   return 2 * c.batch <= seq_cu_count();
 }
 // Riders (gt_seq_wg.h): the SPLIT backward phases of the d_model-128 kernels carry the weight gradients on the CUs the sequence
-// workgroups leave idle.  g_seq_ride: -1 = by shape (enough idle CUs that a phase's units get a rider each or nearly), 0 off, 1 on
+// workgroups leave idle.  GT_SW_SEQ_RIDE: -1 = by shape (enough idle CUs that a phase's units get a rider each or nearly), 0 off, 1 on
 // wherever the kernels support it (GT_SEQ_RIDE=0/1, gt_set_seq_ride).
-static int g_seq_ride = -1;
-extern "C" int gt_set_seq_ride(int on) { g_seq_ride = on < 0 ? -1 : on != 0; return 0; }
+extern "C" int gt_set_seq_ride(int on) { return gt_switch_set_flag(GT_SW_SEQ_RIDE, on); }
 #ifndef GT_SEQ_RIDE_MIN_IDLE
 #define GT_SEQ_RIDE_MIN_IDLE 96      /* batch <= 80: a phase's units find a rider each (bs 96, 64 idle CUs: 0.324 ms riding vs 0.270 grouped) */
 #endif
@@ -1106,31 +1084,30 @@ extern "C" int gt_set_seq_ride(int on) { g_seq_ride = on < 0 ? -1 : on != 0; ret
 #endif
 static bool seq_ride(const gt_config& c) {
   if (c.d_model != 128 || c.dim_ff % 16 != 0) return false;     // (seq_plan asks for a SPLIT schedule only)
-  const int ride = seq_switch(g_seq_ride, "GT_SEQ_RIDE"), idle = seq_cu_count() - 2 * c.batch;
+  const int ride = (int)gt_switch(GT_SW_SEQ_RIDE), idle = seq_cu_count() - 2 * c.batch;
   if (ride >= 0) return ride != 0 && idle >= 1;
   return idle >= GT_SEQ_RIDE_MIN_IDLE;
 }
 // QUAD forward (gt_seq.h): four workgroups per sequence -- row halves x column partners that share the FFN through one pair exchange per
 // layer -- while ALL of them fit the chip at once (one workgroup per CU: the partners spin on each other).  -1 = by shape, 0 / 1 forced
 // (GT_SEQ_QUAD, gt_set_seq_quad; forcing it on still requires the grid to fit).
-static int g_seq_quad = -1;
-extern "C" int gt_set_seq_quad(int on) { g_seq_quad = on < 0 ? -1 : on != 0; return 0; }
+extern "C" int gt_set_seq_quad(int on) { return gt_switch_set_flag(GT_SW_SEQ_QUAD, on); }
 static bool seq_quad(const gt_config& c) {
   if (c.d_model != 128 || c.dim_ff % 32 != 0 || 4 * c.batch > xchg_cus() || (c.flags & GT_CFG_NO_QUAD)) return false;     // (of a SPLIT schedule: seq_plan)
-  return seq_switch(g_seq_quad, "GT_SEQ_QUAD") != 0;
+  return gt_switch(GT_SW_SEQ_QUAD) != 0;
 }
 // bound of the pair exchange's polling loop (0 / negative: the compiled default).  A test lowers it to see the time-out path -- error
 // word, skipped update, host recovery -- without waiting seconds.
-extern "C" int gt_set_xchg_spin_max(int polls) { g_xchg_spin_max = polls; return 0; }
+extern "C" int gt_set_xchg_spin_max(int polls) { return gt_switch_set(GT_SW_XCHG_SPIN_MAX, polls); }
 static bool seq_supported(const gt_config& c) {
   const int hd = c.d_model / c.n_heads;
   return c.n_dec_layers == 0 && c.precision == 0 && c.d_model % 16 == 0 && c.d_model <= 128 && c.dim_ff % 16 == 0 &&
          c.dim_ff <= GT_SEQ_FMAX && c.src_dim <= 32 && (hd < 16 || hd == 16 || hd == 32 || hd == 64);
 }
 static bool use_seq(const gt_config& c) {
-  if (g_seq < 0) { const char* e = getenv("GT_SEQ"); g_seq = !e ? 2 : e[0] == '0' ? 0 : 1; }
-  if (g_seq == 2 && c.d_model > 64 && c.d_model != 128 && c.batch < 64) return false;   // (128 itself: the SPLIT kernels win from batch 16 up)
-  return g_seq && seq_supported(c);
+  const long sw = gt_switch(GT_SW_SEQ);
+  if (sw < 0 && c.d_model > 64 && c.d_model != 128 && c.batch < 64) return false;   // (by measurement; 128 itself: the SPLIT kernels win from batch 16 up)
+  return sw != 0 && seq_supported(c);
 }
 // The rules above, asked once for a call (a checked gt_config).  Nothing is kept between calls: the process-wide setters and the
 // environment answer every time as they always did.
@@ -1147,27 +1124,25 @@ static SeqPlan seq_plan(const gt_config& c) {
   p.fuse_b0 = p.quad && p.ride && hd == 32;
   return p;
 }
-// The attention form a sequence-resident launch of this plan takes, for the dispatch trace only (nothing launches by it).  A RESTATEMENT of
-// two kernel-side rules of gt_seq.h -- keep it in step with them: SeqHd<HDC>::PAD (class 0, head_dim < 16: the zero-padded MFMA form) and the
-// `vattn` / `va` condition of seq_fwd_kernel / seq_bwd_kernel (the vector-ALU form: the SPLIT kernels of DP 32 / 64 with 16 heads of DP / 16).
-static const char* seq_attn_form(const gt_config& c, const SeqPlan& p) {
-  if (p.hc != 0) return "mfma";
-  const bool valu = p.split && (c.d_model == 32 || c.d_model == 64) && c.n_heads == 16;      // (head_dim == DP / 16 follows)
-  return valu ? "valu" : "mfma-pad";
-}
-// d_model equals its class (kernel<DP, HDC, EXACT>: DP 32 / 64 / 128) -- the trace's "exact"
-static int seq_exact(const gt_config& c) { return c.d_model == 32 || c.d_model == 64 || c.d_model == 128; }
-// The tail of a seq_fwd / seq_bwd trace line: " hc <class> exact <0/1> attn <form> loss <0/1>" at GT_TRACE_DISPATCH=2, nothing at 1 -- whoever
-// reads the level-1 trace (its keys are checked one by one by the readers that exist) sees the lines it always saw.
+// The instantiation a sequence-resident launch of this call's plan runs (gt_seq_kernel_id).  quad: four workgroups per sequence in THIS launch --
+// every forward phase of a QUAD plan, of its backward phase 0 alone.  The same id goes to the launcher and into the trace line.
+static SeqKernelId seq_kernel(const Ctx& x, bool quad, bool bwd) { return gt_seq_kernel_id(x.d, x.plan.hc, x.plan.split, quad, bwd); }
+// The tail of a seq_fwd / seq_bwd trace line, printed from the id the launcher gets: " hc <class> exact <0/1> attn <form> loss <0/1>" at
+// GT_TRACE_DISPATCH=2, nothing at 1 -- whoever reads the level-1 trace (its keys are checked one by one by the readers that exist) sees the lines it
+// always saw.  attn: "mfma", or for class 0 "valu" / "mfma-pad" (gt_seq_valu_attn); "none" for the QUAD backward launch, whose phase has no attention.
 struct SeqInst { char s[64]; };
-// quad_b0: the QUAD launch of backward phase 0 -- ONE instantiation, <128, 32, true, true, true>, for every head class (gt_seq_launch_bwd), and
-// no attention in that phase: the line names what is launched, "hc 32 ... attn none", not the plan's class.
-static SeqInst seq_inst(const gt_config& c, const SeqPlan& p, bool loss, bool quad_b0 = false) {
+static SeqInst seq_inst(const Ctx& x, const SeqKernelId& id, bool bwd, bool loss) {
   SeqInst t;
   t.s[0] = 0;
-  if (gt_dispatch_level() >= 2)
-    snprintf(t.s, sizeof(t.s), " hc %d exact %d attn %s loss %d", quad_b0 ? 32 : p.hc, seq_exact(c), quad_b0 ? "none" : seq_attn_form(c, p), (int)loss);
+  if (gt_dispatch_level() >= 2) {
+    const char* attn = (bwd && id.quad) ? "none" : id.hdc != 0 ? "mfma" : gt_seq_valu_attn(id.split, id.dp, x.hd, x.H) ? "valu" : "mfma-pad";
+    snprintf(t.s, sizeof(t.s), " hc %d exact %d attn %s loss %d", id.hdc, (int)id.exact, attn, (int)loss);
+  }
   return t;
+}
+// a launcher's -1: the id names no instantiation of gt_seq_inst.h (nothing seq_supported admits gets here)
+static int seq_no_kernel(const char* what, const SeqKernelId& id) {
+  return gt_fail("%s: no kernel <%d, %d, %d, %d, %d> is compiled (gt_seq_inst.h)", what, id.dp, id.hdc, (int)id.exact, (int)id.split, (int)id.quad);
 }
 // What a fused train step hands to its forward and takes back from it (train_step_impl; gt_forward passes none).
 struct FwdStep {
@@ -1239,11 +1214,11 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
   const bool fuse_b0 = sp.fuse_b0 && a.loss_y != nullptr;
   // (its dgrad products -- output layer, FFN2, FFN1, out-proj of the last layer -- are counted where they run)
   gt_prof_tag("seq_fwd", fl + (fuse_b0 ? seq_b0_flops(x) : 0.0), 4.0 * x.M * (x.c.src_dim + x.c.n_enc_layers * (9.0 * x.d + x.F) + 27.0));
+  const SeqKernelId id = seq_kernel(x, sp.quad, false);          // (every forward launch of the call runs the same instantiation)
   if (sp.split) {
     // GT_SEQ_QUAD_PRO=1: input layer + in-proj(0) as a prologue launch of their own instead of four times over inside phase 0 --
     // measured neutral at the headline shape (0.2076 vs 0.2073 ms: one more launch for 17 k fewer cycles of phase 0), so off
-    static const int quad_pro = [] { const char* e = getenv("GT_SEQ_QUAD_PRO"); return (e && e[0] == '1') ? 1 : 0; }();
-    a.quad_pro = sp.quad ? quad_pro : 0;
+    a.quad_pro = sp.quad ? (int)gt_switch(GT_SW_SEQ_QUAD_PRO) : 0;
     for (int p = a.quad_pro ? -1 : 0; p < x.c.n_enc_layers; ++p) {   // one launch per encoder layer (gt_seq.h, SPLIT) [+ QUAD's prologue]
       SeqArgs ap = a;
       ap.phase = p;
@@ -1251,21 +1226,20 @@ static int seq_forward(const Ctx& x, const float* pe, const float* src, float* h
       // (hc exact attn: the instantiation and the attention form; loss: this launch runs the output layer and takes the fused loss along)
       gt_dispatch("seq_fwd phase %d split 1 quad %d ride %d fuse_b0 %d B %d d %d F %d L %d%s", p, sp.quad, sp.ride,
                   fuse_b0 && p == x.c.n_enc_layers - 1, x.c.batch, x.d, x.F, x.c.n_enc_layers,
-                  seq_inst(x.c, sp, a.loss_y != nullptr && p == x.c.n_enc_layers - 1).s);
+                  seq_inst(x, id, false, a.loss_y != nullptr && p == x.c.n_enc_layers - 1).s);
       if (fuse_b0 && p == x.c.n_enc_layers - 1) {
         ap.fuse_b0 = 1;
         gt_seq_launch_fb(ap, 4 * x.c.batch, x.s);
         st->b0_done = true;
-      } else {
-        gt_seq_launch_fwd(ap, x.d, sp.hc, true, (sp.quad ? 4 : 2) * x.c.batch, x.s, sp.quad);
+      } else if (gt_seq_launch_fwd(ap, id, (sp.quad ? 4 : 2) * x.c.batch, x.s)) {
+        return seq_no_kernel("seq_fwd", id);
       }
     }
     return 0;
   }
   gt_dispatch("seq_fwd phase 0 split 0 quad 0 ride 0 fuse_b0 0 B %d d %d F %d L %d%s", x.c.batch, x.d, x.F, x.c.n_enc_layers,
-              seq_inst(x.c, sp, a.loss_y != nullptr).s);
-  gt_seq_launch_fwd(a, x.d, sp.hc, false, x.c.batch, x.s);
-  return 0;
+              seq_inst(x, id, false, a.loss_y != nullptr).s);
+  return gt_seq_launch_fwd(a, id, x.c.batch, x.s) ? seq_no_kernel("seq_fwd", id) : 0;
 }
 // the whole backward chain of every sequence in ONE launch (SPLIT: one per phase).  The weight gradients (contractions over all
 // sequences) and the LayerNorm parameter gradients ride in the phases and finish in the tail launch (sp.ride: nothing is left for the
@@ -1310,12 +1284,13 @@ static int seq_backward(const Ctx& x, const float* xin, int accumulate, int phas
       SeqArgs ap = a;
       ap.phase = p;
       if (p > p_lo && !(b0_done && p == 1)) gt_prof_tag("seq_bwd", 0.0, 0.0);
-      // (loss 0: no backward launch carries the loss -- the key is there so that both families read alike)
-      gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d%s", p, p == 0 && sp.quad,
-                  p == 0 ? 0 : R, b0_done, B, d, x.F, L, seq_inst(x.c, sp, false, p == 0 && sp.quad).s);
       // phase 0 has no riders: four workgroups per sequence there (column partners, gt_seq.h QUAD) while they fit the chip
-      if (p == 0 && sp.quad) gt_seq_launch_bwd(ap, d, sp.hc, true, 2 * a.nseq, x.s, true);
-      else gt_seq_launch_bwd(ap, d, sp.hc, true, a.nseq + (p == 0 ? 0 : R), x.s);
+      const bool quad = p == 0 && sp.quad;
+      const SeqKernelId id = seq_kernel(x, quad, true);
+      // (loss 0: no backward launch carries the loss -- the key is there so that both families read alike)
+      gt_dispatch("seq_bwd phase %d split 1 quad %d ride 1 riders %d fuse_b0 %d B %d d %d F %d L %d%s", p, quad,
+                  p == 0 ? 0 : R, b0_done, B, d, x.F, L, seq_inst(x, id, true, false).s);
+      if (gt_seq_launch_bwd(ap, id, quad ? 2 * a.nseq : a.nseq + (p == 0 ? 0 : R), x.s)) return seq_no_kernel("seq_bwd", id);
     }
     if (phase == 1) {      // bucket 0 reaches to the END of the buffer: the output layer's gradient now, by a launch of its own
       a.phase = 0; a.tail_phase = 0; a.tail_ksplit = 2; a.bump = nullptr;
@@ -1338,13 +1313,14 @@ static int seq_backward(const Ctx& x, const float* xin, int accumulate, int phas
     return 0;
   }
   gt_prof_tag("seq_bwd", fl, 4.0 * M * (L * (14.0 * d + 2.0 * x.F) + 27.0));
+  const SeqKernelId id = seq_kernel(x, false, true);           // (without riders no backward phase runs four workgroups per sequence)
   for (int p = 0; p <= (sp.split ? L : 0); ++p) {              // SPLIT: one launch per phase; else the one launch
     SeqArgs ap = a;
     ap.phase = p;
     if (p > 0) gt_prof_tag("seq_bwd", 0.0, 0.0);
     gt_dispatch("seq_bwd phase %d split %d quad 0 ride 0 riders 0 fuse_b0 0 B %d d %d F %d L %d%s", p, sp.split, B, d, x.F, L,
-                seq_inst(x.c, sp, false).s);
-    gt_seq_launch_bwd(ap, d, sp.hc, sp.split, nwg, x.s);
+                seq_inst(x, id, true, false).s);
+    if (gt_seq_launch_bwd(ap, id, nwg, x.s)) return seq_no_kernel("seq_bwd", id);
   }
   wgrad(x, ws + W.dlogits, GT_TGT, ws + W.memory, d, grads + P.out_w, grads + P.out_b, GT_TGT, d);
   for (int j = L - 1; j >= 0; --j) {

@@ -3,19 +3,15 @@
 // compile to the same instructions either way -- ran 0.4-0.5 % slower (0.1994 vs 0.1986 ms, objects of the two builds mixed and matched on one
 // box: the slow-down follows the two translation units' code objects, not the host code).
 #define GT_SEQ_TU_64
-#include "gt_seq.h"
+#include "gt_seq_inst.h"
 
-void gt_seq_launch_fwd64(const SeqArgs& a, int hc, unsigned nblocks, hipStream_t s) {
+int gt_seq_launch_fwd64(const SeqArgs& a, const SeqKernelId& id, unsigned nblocks, hipStream_t s) {
   const dim3 grid(nblocks), block(GT_SEQ_NT);
-  if (hc == 0) gt_launch(seq_fwd_kernel<64, 0, true, true>, grid, block, s, a);
-  else if (hc == 16) gt_launch(seq_fwd_kernel<64, 16, true, true>, grid, block, s, a);
-  else if (hc == 32) gt_launch(seq_fwd_kernel<64, 32, true, true>, grid, block, s, a);
-  else gt_launch(seq_fwd_kernel<64, 64, true, true>, grid, block, s, a);
+  switch (gt_seq_kernel_key(id)) { GT_SEQ_SPLIT64(GT_SEQ_CASE_FWD) }
+  return -1;
 }
-void gt_seq_launch_bwd64(const SeqArgs& a, int hc, unsigned nblocks, hipStream_t s) {
+int gt_seq_launch_bwd64(const SeqArgs& a, const SeqKernelId& id, unsigned nblocks, hipStream_t s) {
   const dim3 grid(nblocks), block(GT_SEQ_NT);
-  if (hc == 0) gt_launch(seq_bwd_kernel<64, 0, true, true>, grid, block, s, a);
-  else if (hc == 16) gt_launch(seq_bwd_kernel<64, 16, true, true>, grid, block, s, a);
-  else if (hc == 32) gt_launch(seq_bwd_kernel<64, 32, true, true>, grid, block, s, a);
-  else gt_launch(seq_bwd_kernel<64, 64, true, true>, grid, block, s, a);
+  switch (gt_seq_kernel_key(id)) { GT_SEQ_SPLIT64(GT_SEQ_CASE_BWD) }
+  return -1;
 }

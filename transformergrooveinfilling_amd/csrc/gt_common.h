@@ -44,7 +44,7 @@ __host__ __device__ static inline float gt_bf2f(uint16_t h) {
   return c.f;
 }
 
-#include "../../include/groove_hip.h"
+#include "../../include/groove_hip_debug.h"      // (the contract, groove_hip.h, and the switches / aids beside it)
 
 // GT_BARRIER(): stage barrier of the sequence-resident kernels (gt_seq.h): waits for this wave's LDS traffic
 // only -- __syncthreads() would also drain its vector-memory queue (vmcnt(0)), which prefetches and saves keep in flight

@@ -25,6 +25,7 @@
 // the accumulators through LDS and runs LayerNorm forward/backward with 64-lane wave reductions.
 #pragma once
 #include "gt_common.h"
+#include "gt_switches.h"
 #include <type_traits>
 #include <stdio.h>
 #include <stdlib.h>
@@ -815,19 +816,13 @@ static inline void gemm_launch_cfg(const GemmArgs& g, int splitk, hipStream_t s)
 #define GT_WGRAD128H_MIN_CHUNK 1024     /* bf16 operands: measured at 2048 tokens (C5 bs 64): chunks >= 512 / 1024 / 2048 -> 0.958 / 0.946 / 0.984 ms (precision 2:
                                            0.952 / 0.927 / 0.968); fp32 (C4 bs 64): 1.494 / 1.508 / 1.572 -- stays at 512 */
 #endif
-static inline long gt_env_long(const char* name, long dflt);
-static int g_deterministic = -1;
-static inline bool gt_deterministic() {
-  if (g_deterministic < 0) { const char* e = getenv("GT_DETERMINISTIC"); g_deterministic = (e && e[0] == '1') ? 1 : 0; }
-  return g_deterministic != 0;
-}
+static inline bool gt_deterministic() { return gt_switch(GT_SW_DETERMINISTIC) != 0; }
 static inline int wgrad_split(GemmArgs& g, long target, int tile = 32) {
   if (gt_deterministic()) target = 1;
   const long tiles = (long)((g.M + tile - 1) / tile) * ((g.N + tile - 1) / tile);
   long want = (target + tiles - 1) / tiles;
   // (128x128 tiles: token chunks of at least GT_WGRAD128_MIN_CHUNK -- every chunk ends in 64 KB of fp32 atomics per tile)
-  static const long c128 = gt_env_long("GT_WGRAD128_MIN_CHUNK", GT_WGRAD128_MIN_CHUNK), c128h = gt_env_long("GT_WGRAD128H_MIN_CHUNK", GT_WGRAD128H_MIN_CHUNK);
-  const long ch128 = g.bf16 ? c128h : c128;
+  const long ch128 = g.bf16 ? gt_switch(GT_SW_WGRAD128H_MIN_CHUNK, GT_WGRAD128H_MIN_CHUNK) : gt_switch(GT_SW_WGRAD128_MIN_CHUNK, GT_WGRAD128_MIN_CHUNK);
   const long maxs = tile >= 128 ? (g.K + ch128 - 1) / ch128 : tile >= 64 ? (g.K + 255) / 256 : (g.K + 127) / 128;
   if (want > maxs) want = maxs;
   if (want < 1) want = 1;
@@ -980,10 +975,8 @@ static inline void gemm64h_launch(const GemmArgs& g, hipStream_t s);
                                    N 256 7.7 vs 8.6 -- but M 2048 N 1536 12.9 vs 11.7, M 8192 N 768 18.6 vs 13.7, M 16384 N 512 29 vs 18.6: at the bf16 MFMA rate
                                    the 64x64 tile's doubled operand bytes per flop bind as soon as the big tile has a round of its own) */
 #endif
-static inline long gt_env_long(const char* name, long dflt) { const char* e = getenv(name); return (e && e[0]) ? atol(e) : dflt; }
 static inline bool gemm64_range(long t64, bool h) {
-  static const long lo = gt_env_long("GT_T64R_MIN", GT_T64R_MIN), hi = gt_env_long("GT_T64R_MAX", GT_T64R_MAX), hih = gt_env_long("GT_T64H_MAX", GT_T64H_MAX);
-  return t64 >= lo && t64 <= (h ? hih : hi);
+  return t64 >= gt_switch(GT_SW_T64R_MIN, GT_T64R_MIN) && t64 <= (h ? gt_switch(GT_SW_T64H_MAX, GT_T64H_MAX) : gt_switch(GT_SW_T64R_MAX, GT_T64R_MAX));
 }
 // Which kernel class takes a problem with a standard (non-row) epilogue, and its k_chunk: the ONE statement of the tile rules (gemm_launch
 // switches on it, gemm_on_big_kernel asks it).  The ring tiles of gt_gemm32.h / gt_gemm64.h first -- interior problems of the store-class

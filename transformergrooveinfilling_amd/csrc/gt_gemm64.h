@@ -559,8 +559,7 @@ __device__ __forceinline__ void gemm32_ln_epilogue(const GemmArgs& g, f32x16 (&a
 #define GT_LN128_MIN GT_T128_BIG_MIN
 #endif
 static inline bool gemm32_ln_shape(const GemmArgs& g, int cus) {
-  static const long lo = gt_env_long("GT_LN128_MIN", GT_LN128_MIN);
-  const long tiles = (long)(g.M / 128) * (g.N / 128);
+  const long lo = gt_switch(GT_SW_LN128_MIN, GT_LN128_MIN), tiles = (long)(g.M / 128) * (g.N / 128);
   return (g.N == 256 || g.N == 512) && g.M % 128 == 0 && tiles <= 2l * cus && tiles >= lo;
 }
 static inline bool gemm32_ln_ok(const GemmArgs& g, int epi) {
@@ -731,7 +730,7 @@ __device__ __forceinline__ void gemm_xln32_epilogue(const GemmArgs& g, const int
 // host side: the 32x32-tile form applies where a d_model-wide Linear runs on the generic kernel's 32x32 tiles anyway (fewer than GT_T64_MIN
 // tiles of 64x64), N is a multiple of 32 up to 512, and the whole grid is resident with room to spare (<= 2 tiles per CU; at least half the CUs get one)
 static inline bool gemm_xln32_shape(const GemmArgs& g, int cus) {
-  static const long lo_env = gt_env_long("GT_LN32_MIN", -1);          // (tests lower the bound: the emulator runs small shapes)
+  const long lo_env = gt_switch(GT_SW_LN32_MIN, -1);          // (tests lower the bound: the emulator runs small shapes)
   const long tiles = (long)(g.M / 32) * (g.N / 32), t64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64), lo = lo_env >= 0 ? lo_env : cus / 2;
   return g.N % 32 == 0 && g.N >= 64 && g.N <= 512 && g.M % 32 == 0 && t64 < GT_T64_MIN && tiles <= 2l * cus && tiles >= lo;
 }

@@ -808,7 +808,7 @@ __device__ __forceinline__ void seq_ln_part(const float* sP, float* part, const 
 // addresses.  Wave pair p = wave >> 1 takes head h4 + p, wave & 1 the query (role 2: key) tile
 // (SPLIT backward: the role, on the workgroup's own tile).
 // HDC: head-dim class the kernel is compiled for -- 0: head_dim < 16 (operands zero-padded to 16 columns), else 16 / 32 / 64
-// (PAD and the `vattn` condition of the kernels below are restated on the host for the dispatch trace: seq_attn_form in groove_hip.hip)
+// (class 0 -- SeqKernelId's hdc == 0 -- means PAD: head_dim < 16, zero-padded to the 16-wide MFMA form unless the kernels' `vattn` / `va` hold)
 template <int HDC> struct SeqHd { static constexpr int HD = HDC ? HDC : 16; static constexpr bool PAD = HDC == 0; };
 // PAD: columns >= head_dim read as 0 (the address is clamped to the head's first column: always inside the tile)
 template <bool PAD>
@@ -1547,8 +1547,8 @@ __device__ __forceinline__ bool seq_fwd_body(const SeqArgs& a, float* const lds)
     if (preo) bopre = seq_tiles_first<NK>(kf_out, d, d, wave, lane);
     bool vattn = false;
     if constexpr (PAD && SPLIT && (DP == 32 || DP == 64)) {        // (SPLIT kernels only: in the whole-sequence kernels the extra live range spills)
-      // (16 heads of 2 at d_model 32, of 4 at d_model 64: the backward's P staging is written for 16 heads; the host's trace restates this
-      //  condition and the one in front of it -- seq_attn_form in groove_hip.hip: change both together)
+      // (16 heads of 2 at d_model 32, of 4 at d_model 64: the backward's P staging is written for 16 heads; this condition and the one in
+      //  front of it are gt_seq_valu_attn of gt_seq_api.h, the host's one copy for the trace: change them together)
       vattn = a.hd == DP / 16 && a.H == 16;
       if (vattn) {
         const uint32_t key = seq_key(dk, site0 + GT_SITE_ATTN);

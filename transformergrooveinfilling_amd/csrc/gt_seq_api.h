@@ -50,18 +50,35 @@ struct SeqArgs {
 };
 // tiles of one weight-gradient problem in the rider decomposition (32 x 64 outputs per workgroup)
 static inline int gt_seq_wg_tiles(int rows, int cols) { return ((rows + 31) / 32) * ((cols + 63) / 64); }
-// launchers (one instantiation per d_model class / head-dim class / EXACT / SPLIT); hc = head-dim class 0 (< 16) / 16 / 32 / 64
+// One instantiation of seq_fwd_kernel / seq_bwd_kernel (gt_seq.h): its template arguments <DP, HDC, EXACT, SPLIT, QUAD>.  dp: d_model class 32 / 64 /
+// 128; hdc: head-dim class 0 (head_dim < 16: SeqHd's PAD form) / 16 / 32 / 64; exact: d_model == dp; split / quad: two / four workgroups per sequence.
+// The launchers switch on it, the dispatch trace prints it (seq_inst in groove_hip.hip), gt_seq_inst.h lists the ids that exist.
+struct SeqKernelId { int dp, hdc; bool exact, split, quad; };
+constexpr int gt_seq_kernel_key(int dp, int hdc, bool exact, bool split, bool quad) { return dp << 10 | hdc << 3 | (int)exact << 2 | (int)split << 1 | (int)quad; }
+// THE rule from a launch to its instantiation.  hc: the plan's head-dim class; split / quad: workgroups per sequence of THIS launch; bwd: a backward launch
+static inline SeqKernelId gt_seq_kernel_id(int d_model, int hc, bool split, bool quad, bool bwd) {
+  // backward phase 0 of the QUAD schedule: no attention in that phase, so one head-dim class serves all
+  if (bwd && quad) return SeqKernelId{128, 32, true, true, true};
+  const int dp = d_model <= 32 ? 32 : d_model <= 64 ? 64 : 128;
+  return SeqKernelId{dp, (dp == 32 && hc != 0 && hc != 16) ? 32 : hc, d_model == dp, split, quad};
+}
+// The one attention rule that is no template argument: the PAD-class SPLIT kernels of DP 32 / 64 take the vector-ALU form for 16 heads of DP / 16,
+// every other PAD-class launch the zero-padded MFMA form.  The host's ONE copy, for the trace; the kernels keep their own two expressions --
+// `vattn` of seq_fwd_body (gt_seq.h:1552) and `va` of seq_bwd_body (gt_seq.h:2398), each under `if constexpr (PAD && SPLIT && (DP == 32 || DP == 64))`
+// -- because calling this function there compiles to other instructions (compare / branch senses in four places of the d_model-64 kernels).
+constexpr bool gt_seq_valu_attn(bool split, int dp, int hd, int H) { return split && (dp == 32 || dp == 64) && hd == dp / 16 && H == 16; }
 void gt_seq_launch_pack(const SeqArgs& a, unsigned nblocks, hipStream_t s);
 // optimizer update (algo 0 sgd / 1 adam, the arithmetic of gt_misc.h's kernels) + the next step's fragment-ordered weights
 void gt_seq_launch_update_pack(const SeqArgs& a, int algo, float* params, float* grads, float* m, float* v, int64_t n, const gt_step_state* st,
                                int step_advanced, hipStream_t s);
-void gt_seq_launch_fwd(const SeqArgs& a, int d_model, int hc, bool split, unsigned nblocks, hipStream_t s, bool quad = false);
+// launch the instantiation `id` names; -1 (nothing launched) if gt_seq_inst.h lists no such instantiation
+int gt_seq_launch_fwd(const SeqArgs& a, const SeqKernelId& id, unsigned nblocks, hipStream_t s);
 // floats of the QUAD forward's pair-exchange region for a batch: 8 header granules + 4 x batch slots of 4 x 512 8-byte granules
 static inline int64_t gt_seq_xchg_floats(int batch) { return 16 + (int64_t)4 * batch * 4 * 512 * 2; }
 // the last forward phase + backward phase 0 of the QUAD schedule in ONE launch (a.fuse_b0 = 1; head-dim class 32 only)
 void gt_seq_launch_fb(const SeqArgs& a, unsigned nblocks, hipStream_t s);
-void gt_seq_launch_bwd(const SeqArgs& a, int d_model, int hc, bool split, unsigned nblocks, hipStream_t s, bool quad = false);
+int gt_seq_launch_bwd(const SeqArgs& a, const SeqKernelId& id, unsigned nblocks, hipStream_t s);
 void gt_seq_launch_tail(const SeqArgs& a, unsigned nblocks, hipStream_t s);
-// the SPLIT kernels of d_model 64 (groove_seq64.hip: a code object of their own); hc = head-dim class 0 / 16 / 32 / 64
-void gt_seq_launch_fwd64(const SeqArgs& a, int hc, unsigned nblocks, hipStream_t s);
-void gt_seq_launch_bwd64(const SeqArgs& a, int hc, unsigned nblocks, hipStream_t s);
+// the SPLIT kernels of d_model 64 (groove_seq64.hip: a code object of their own); gt_seq_launch_fwd / bwd hand them their ids
+int gt_seq_launch_fwd64(const SeqArgs& a, const SeqKernelId& id, unsigned nblocks, hipStream_t s);
+int gt_seq_launch_bwd64(const SeqArgs& a, const SeqKernelId& id, unsigned nblocks, hipStream_t s);
